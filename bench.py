@@ -31,10 +31,29 @@ collective on the data path (column independence, leopard16.go:778-792):
                   roofline against 0.67-0.69 at 2048 stripes).
   --split stripes each rank encodes B whole stripes of its own -> "weak".
 
-Prints one JSON line (rank 0).  `roofline` is for the dominant (only) kernel:
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps and prints one JSON line (rank 0) with the headline figure:
+`value` = data bytes encoded / wall time of the N steps, `ms_per_step` = that
+wall time / N.  `roofline` is for the dominant (only) kernel:
 achieved = algorithmic bytes per launch ((k+p)*bytes-per-row: read k rows,
 write p rows) / its mean duration (one HIP event pair on the launch stream
-around the timed launches, divided by their count).  `single_stripe` repeats
+around the timed launches, divided by their count).
+
+--dump-outputs DIR writes, right after the timed steps, what the last step
+left in the resident parity rows [stripes, p, row bytes] (the encode's only
+output), as .npy files in DIR (suffixed _rank<r> when N > 1):
+  parity_row_sums.npy  float64 [stripes, p]: the byte sum of every parity row
+                       (exact), so every output byte weighs in;
+  parity_sample.npy    float32 [<= 8 stripes, p, columns]: the parity bytes of
+                       a fixed, seeded choice of stripes and byte columns (the
+                       first and last of each always among them), 32 MiB at
+                       the most.
+The inputs come from a seeded generator, so two runs with the same arguments
+encode the same bytes and their dumps compare file for file.
+
+Everything below takes runs of its own and is measured with --full only (each
+part can be left out of a --full run with its --no-* option); a plain run
+reports those keys as null.  `single_stripe` repeats
 the kernel timing with one stripe per launch (the reference's Encode
 granularity).  Resident rows sit at a stride of row bytes + --row-pad (3.5 KiB
 by default); `unpadded_rows` times the same launch on rows
@@ -447,6 +466,38 @@ def _stream_rates(st, data, par, sink, rsink, erased, K, P, rate) -> dict:
     return stream_rates
 
 
+DUMP_SAMPLE_ELEMS = 8 << 20  # parity_sample.npy: at most 8 Mi float32 = 32 MiB
+
+
+def dump_outputs(torch, out_dir: str, parity, rank: int, world: int) -> None:
+    """--dump-outputs: the parity rows [B, p, W] as the last timed step left
+    them -> out_dir/parity_row_sums.npy (float64 [B, p], exact byte sums of
+    every row) and out_dir/parity_sample.npy (float32 [stripes, p, columns]:
+    a fixed seeded choice of stripes and byte columns, the first and last of
+    each included)."""
+    import numpy as np
+
+    B, P, W = parity.shape
+    rng = np.random.default_rng(0xD0C5)
+
+    def pick(n, want):
+        if n <= want:
+            return np.arange(n)
+        return np.unique(np.concatenate(([0, n - 1], rng.choice(n, want - 2, replace=False))))
+
+    stripes = pick(B, 8)
+    cols = pick(W, max(2, DUMP_SAMPLE_ELEMS // (len(stripes) * P)))
+    torch.cuda.synchronize()
+    sums = parity.sum(dim=-1, dtype=torch.int64).cpu().numpy().astype(np.float64)
+    rows = parity[torch.from_numpy(stripes).to(parity.device)]
+    sample = rows[:, :, torch.from_numpy(cols).to(parity.device)].cpu().numpy().astype(np.float32)
+    del rows
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(out_dir, f"parity_row_sums{tag}.npy"), sums)
+    np.save(os.path.join(out_dir, f"parity_sample{tag}.npy"), sample)
+
+
 def free_port() -> int:
     import socket
 
@@ -506,7 +557,8 @@ def dry_run(args, rank: int, world: int) -> None:
                           "roofline": {"traffic": got[0]["traffic"], "traffic_key": got[0]["traffic_key"],
                                        "per_rank_traffic": [r["traffic"] for r in got]},
                           "per_rank_frac": [None] * world,
-                          "cpu_baseline": None if args.no_cpu else cpu_baseline(K, P, S, args.cpu_seconds, threads)}),
+                          "cpu_baseline": (cpu_baseline(K, P, S, args.cpu_seconds, threads)
+                                           if args.full and not args.no_cpu else None)}),
               flush=True)
     dist.barrier()
     dist.destroy_process_group()
@@ -522,17 +574,22 @@ def main():
                     help="multi-GPU layout: byte ranges of N x --stripes stripes (weak, default), byte ranges of "
                          "--stripes stripes (strong), or whole stripes per rank (weak)")
     ap.add_argument("--stripes", type=int, default=256, help="stripes encoded per step (one launch per rank)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the unpadded layout, one stripe per "
+                         "launch, the other workloads, the host-resident rates and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the parity the last timed step computed to DIR/*.npy (row sums and a seeded sample)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: min(16, os.cpu_count())")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-single", action="store_true", help="skip the one-stripe-per-launch figure")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-single", action="store_true", help="--full: skip the one-stripe-per-launch figure")
     ap.add_argument("--row-pad", type=int, default=3584,
                     help="bytes between consecutive resident rows (HBM layout: row stride = row bytes + pad; "
-                         "64-byte multiple); the unpadded layout is timed too and reported beside it")
-    ap.add_argument("--no-unpadded", action="store_true", help="skip timing the unpadded layout")
+                         "64-byte multiple); --full times the unpadded layout too and reports it beside it")
+    ap.add_argument("--no-unpadded", action="store_true", help="--full: skip timing the unpadded layout")
     ap.add_argument("--dry-run", action="store_true", help="rank layout only: gloo on the CPU, no GPU")
-    ap.add_argument("--no-other", action="store_true", help="skip the C4 / C5 kernel figures (one GPU only)")
-    ap.add_argument("--no-host", action="store_true", help="skip the host-resident (PCIe-inclusive) figures")
+    ap.add_argument("--no-other", action="store_true", help="--full: skip the C4 / C5 kernel figures (one GPU only)")
+    ap.add_argument("--no-host", action="store_true", help="--full: skip the host-resident (PCIe-inclusive) figures")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="process group of an N-rank run: nccl (RCCL, one GPU per rank, the product) or gloo "
                          "(a rehearsal of the same rank code on fewer GPUs than ranks: rank r uses GPU r %% count)")
@@ -540,6 +597,8 @@ def main():
                     help="one GPU: encode rank 0's byte range of an N-rank split (the launch shape each rank of an "
                          "N-GPU run has, for its rocprofv3 PMC passes); not a job-throughput figure")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))  # before any GPU call in this process
@@ -626,13 +685,15 @@ def main():
     for _ in range(args.warmup):
         codec.encode_dev_batch(slab, stream)
     el, kern_ms = timed(slab, args.steps)
+    if args.dump_outputs:  # before anything else writes to these rows
+        dump_outputs(torch, args.dump_outputs, slab[:, K:], rank, world)
     flat_ms = None
-    if pad and not args.no_unpadded:
+    if args.full and pad and not args.no_unpadded:
         for _ in range(args.warmup):
             codec.encode_dev_batch(flat, stream)
         _, flat_ms = timed(flat, max(20, args.steps // 2))
     one_ms = None
-    if not args.no_single:
+    if args.full and not args.no_single:
         for _ in range(10):
             codec.encode_dev_batch(slab[:1], stream)
         _, one_ms = timed(slab[:1], max(50, args.steps))
@@ -649,14 +710,14 @@ def main():
     el, kern_ms, one_ms, flat_ms = float(t[0]), float(t[1]), float(t[2]) or None, float(t[3]) or None
 
     other = host = calib = None
-    if world == 1 and not args.no_other:
+    if args.full and world == 1 and not args.no_other:
         del buf, slab, flat
         torch.cuda.empty_cache()
         calib = copy_rate(torch, dev, stream)
         other = other_workloads(torch, rs, dev, stream)
         other["C2_encode"] = c2_encode(torch, rs, dev, stream)
         torch.cuda.empty_cache()
-    if world == 1 and not args.no_host:
+    if args.full and world == 1 and not args.no_host:
         host = host_resident(rs)
 
     ms_per_step = el / args.steps * 1e3
@@ -733,8 +794,9 @@ def main():
                 "kernel_ms": round(one_ms, 5),
                 "frac": round((K + P) * W / (one_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
             },
-            # rank 0 of a one-GPU run only, after the timed region
-            "cpu_baseline": None if args.no_cpu or world > 1 else cpu_baseline(K, P, S, args.cpu_seconds, threads),
+            # --full, rank 0 of a one-GPU run only, after the timed region
+            "cpu_baseline": (cpu_baseline(K, P, S, args.cpu_seconds, threads)
+                             if args.full and not args.no_cpu and world == 1 else None),
             "other_workloads": other,
             "host_resident": host,
         }

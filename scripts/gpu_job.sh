@@ -9,7 +9,8 @@
 # a time-limit kill).  Steps:
 #   tests[=PATTERN]      python -m pytest tests -m gpu (-k PATTERN)
 #   smoke                __graft_entry__.smoke()
-#   bench[=ARGS]         python bench.py ARGS (comma-separated args: bench=--stripes,128)
+#   bench[=ARGS]         python bench.py ARGS (comma-separated args: bench=--stripes,128;
+#                        bench=--full adds every figure beside the headline)
 #   trace[=ARGS]         rocprofv3 --kernel-trace --stats of bench.py --no-cpu --no-single
 #                        --no-unpadded --no-other --no-host ARGS
 #   ops=CFG              rocprofv3 kernel trace of scripts/time_ops.py --configs CFG

@@ -9,7 +9,7 @@ OUT=gpurun_out/rehearse
 rm -rf $OUT; mkdir -p $OUT
 run() {  # name, args...
   local n=$1; shift
-  timeout -k 10 300 python bench.py "$@" --backend gloo --stripes 16 --steps 10 --warmup 2 --no-host --no-cpu > $OUT/$n.json 2> $OUT/$n.err
+  timeout -k 10 300 python bench.py "$@" --full --backend gloo --stripes 16 --steps 10 --warmup 2 --no-host --no-cpu > $OUT/$n.json 2> $OUT/$n.err
   local rc=$?; echo "$n rc=$rc"; tail -c 700 $OUT/$n.json; echo; [ $rc -eq 0 ] || { tail -20 $OUT/$n.err; exit $rc; }
 }
 run g2_bytes_weak --gpus 2 && run g4_bytes_weak --gpus 4 && run g2_bytes --gpus 2 --split bytes && \

@@ -1,6 +1,7 @@
 #!/bin/bash
-# Round-end evidence on one GPU: pytest -m gpu, smoke, bench.py (the judged
-# line), the rocprofv3 kernel-trace/stats summary of the same bench command,
+# Round-end evidence on one GPU: pytest -m gpu, smoke, bench.py --full (the
+# judged line with every other figure beside it), the rocprofv3
+# kernel-trace/stats summary of the same bench command,
 # and the FETCH_SIZE / WRITE_SIZE PMC passes (one counter per run,
 # MI355X_MICROARCH.md HBM section).  Collect with
 # `python scripts/collect_profiles.py --round N`.
@@ -14,7 +15,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 rc=$?; echo "pytest rc=$rc"; tail -2 $OUT/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' > $OUT/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -2 $OUT/smoke.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py $BARGS > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python bench.py --full $BARGS > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; echo "bench rc=$rc"; cat $OUT/bench.json; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --no-cpu --no-single --no-unpadded --no-other --no-host $BARGS > $OUT/trace_bench.json 2> $OUT/trace.err
 rc=$?; echo "trace rc=$rc"; cat $OUT/trace_bench.json; [ $rc -eq 0 ] || exit $rc

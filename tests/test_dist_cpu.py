@@ -153,7 +153,7 @@ def test_bench_launcher_starts_n_ranks(gpus, workload):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--dry-run",
-                          "--workload", workload, "--cpu-seconds", "0.4", "--cpu-threads", "2"],
+                          "--workload", workload, "--full", "--cpu-seconds", "0.4", "--cpu-threads", "2"],
                          capture_output=True, text=True, timeout=240, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]

@@ -291,6 +291,13 @@ int rs_debug_dec_plan(int mtrunc, const uint32_t *need, uint64_t *code);
  * would copy them.  Pointer queries only, nothing is launched. */
 int rs_debug_zc_rows(uint8_t *const *rows, int nrows, size_t S);
 
+/* 1 when the bit-sliced encode kernel's 32-bit buffer offsets reach every
+ * row it addresses for a strided device encode of shard_size-byte rows
+ * row_stride apart (the last chunk's padding rows and the last 2 KiB tile's
+ * lanes past the row end included), 0 otherwise and outside 9 <= p <= 32: the
+ * host's own check before that kernel is launched.  Host only. */
+int rs_debug_encode_bs_fits(int data_shards, int parity_shards, size_t row_stride, size_t shard_size);
+
 /* Test-only kernel-path overrides (process-wide), so the parity tests can run
  * the variants other geometries select on the same small inputs:
  *   "bs" 0/1          bit-sliced GF(2^16) encode off / on (default 1; read by rs_new),

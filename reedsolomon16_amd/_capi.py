@@ -79,6 +79,7 @@ def lib() -> C.CDLL:
     L.rs_debug_dec_plan.argtypes = [i32, vp, vp]
     L.rs_debug_set_path.argtypes = [C.c_char_p, i32]
     L.rs_debug_zc_rows.argtypes = [P(vp), i32, sz]
+    L.rs_debug_encode_bs_fits.argtypes = [i32, i32, sz, sz]
     _lib = L
     return L
 

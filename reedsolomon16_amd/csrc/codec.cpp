@@ -1811,6 +1811,7 @@ int rs_encode_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t st
     if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
     if (S == 0) return RS_ERR_SHARD_NO_DATA;
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (row_stride < S) return RS_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     if (int ie = ensure_device(c)) return ie;
@@ -1861,6 +1862,7 @@ int rs_verify_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t st
     *ok = 0;
     if (S == 0) return RS_ERR_SHARD_NO_DATA;
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (row_stride < S) return RS_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     if (int ie = ensure_device(c)) return ie;
@@ -2334,6 +2336,10 @@ int rs_debug_zc_rows(uint8_t *const *rows, int nrows, size_t S) {
     for (int i = 0; i < nrows; i++) idx[i] = i;
     ZcRows z{};
     return zc_rows(rows, idx, S, z) ? 1 : 0;
+}
+
+int rs_debug_encode_bs_fits(int k, int p, size_t row_stride, size_t S) {
+    return encode_bs_fits(k, p, row_stride, S) ? 1 : 0;
 }
 
 int rs_debug_set_path(const char *knob, int value) {

@@ -577,8 +577,8 @@ __global__ void __launch_bounds__(256, 2) k_encode_reg(EncodeArgs a) {
 
     // Stage chunk c's rows: rows past the chunk's count and pieces past the
     // row end are zero-filled.
-    // Buffer descriptor over this stripe's data rows (strided mode; the host
-    // guarantees (k-1)*stride + shard_size < 2^32).
+    // Buffer descriptor over this stripe's data rows (strided mode): right only while (k-1)*stride +
+    // shard_size < 2^32, which the host does NOT check (known defect, DESIGN.md section 4, range limits).
     const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(
         ROWTAB ? nullptr : (void *)(a.data.base + soff), 0,
         ROWTAB ? 0 : (int)(uint32_t)((uint64_t)(a.k - 1) * a.data.stride + a.shard_size), 0x00020000);

@@ -251,6 +251,55 @@ int rs_verify_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, siz
 /* Name of the kernel path the codec uses for encode ("reg-m32", "lds", "multipass", ...). */
 const char *rs_encode_path(const rs_codec *codec);
 
+/* ---------------- Incremental update (beyond the reference) ----------------
+ * The reference's Leopard codecs reject Update and EncodeIdx (ErrNotSupported,
+ * leopard16.go:227-229, 273-275; rs_update / rs_encode_idx mirror that and
+ * stay).  The limit is the Go code's, not the code's mathematics: a Leopard
+ * encode is a GF-linear map from data rows to parity rows, so a change D in
+ * data row j changes parity row i by G[i][j] * D, symbol by symbol, with one
+ * field constant G[i][j] per (parity row, data row): the parity symbol the
+ * reference's own encode produces for the unit symbol 1 in row j.  The three
+ * calls below apply exactly that, for device rows on a single-device codec.
+ * Checked before any device call, in this order: NULL codec or arrays, a
+ * multi-device codec, NULL row pointers, bad indices / counts / strides ->
+ * RS_ERR_INVALID_ARG; shard_size == 0 -> RS_ERR_SHARD_NO_DATA; shard_size % 64
+ * -> RS_ERR_INVALID_SHARD_SIZE.  RS_ERR_PANIC where the reference's encode of
+ * the geometry panics.  Stream semantics are rs_encode_dev_batch's:
+ * asynchronous on a caller stream or RS_NULL_STREAM, complete on return for
+ * NULL.  Nothing waits for the kernel; the per-index-list tables are cached
+ * (16 lists per codec, least recently used). */
+
+/* Update (the reference rejects it: leopard16.go:273-275; sound here by the
+ * linearity above): parity ^= G * (new ^ old) for the data rows with
+ * d_new[i] != NULL.  d_shards: k+p device pointers; a data entry must hold the
+ * OLD row where d_new[i] != NULL and may be NULL elsewhere; every parity entry
+ * non-NULL, updated in place.  Data rows are not written (klauspost Update
+ * semantics).  No changed row: RS_OK, nothing launched. */
+int rs_update_dev(rs_codec *codec, uint8_t *const *d_shards, uint8_t *const *d_new /* k */, size_t shard_size,
+                  void *stream);
+
+/* EncodeIdx (the reference rejects it: leopard16.go:227-229; sound here
+ * because parity is the XOR over data rows j of G[:, j] * row j):
+ * parity ^= G[:, idx] * data_row.  Feed each data row exactly once into zeroed
+ * parity rows and the result is Encode's. */
+int rs_encode_idx_dev(rs_codec *codec, const uint8_t *d_data_row, int idx, uint8_t *const *d_parity /* p */,
+                      size_t shard_size, void *stream);
+
+/* Batched Update (no counterpart in the reference; the same linearity): the
+ * same changed indices idx[0..nidx) (distinct, in [0, k)) in every stripe of
+ * an rs_encode_dev_batch slab; new row j of stripe z (for data shard idx[j])
+ * at d_new + z*new_stripe_stride + j*new_row_stride.  Updates parity AND
+ * stores the new rows into the slab, which ends as the encoded stripe of the
+ * new data.  d_new must not overlap the slab.
+ * When to re-encode instead (measured at 128+32 x 1 MiB, 256 stripes,
+ * profiles/update_c3.txt): one changed row costs 0.44 of a full
+ * rs_encode_dev_batch, five 0.53, six 0.59, seven 0.78; from t = 8 changed
+ * rows on (1.0-1.02; 0.84 on the fastest box seen, where it is t = 9) the full
+ * encode is as fast or faster, so store the rows and re-encode instead. */
+int rs_update_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, size_t stripe_stride, int nstripes,
+                        const int *idx, int nidx, const uint8_t *d_new, size_t new_row_stride,
+                        size_t new_stripe_stride, size_t shard_size, void *stream);
+
 /* ---------------- Host-only diagnostics (no device calls; used by CPU tests) ---------------- */
 /* Field tables as built by the engine (initLUTs/initFFTSkew, leopard16.go:940-1031). */
 int rs_debug_field_tables(int field_bits, uint16_t *log_out, uint16_t *exp_out, uint16_t *skew_out,
@@ -269,6 +318,11 @@ uint32_t rs_debug_sub_swap(uint32_t x);
  * Returns RS_ERR_PANIC where the reference panics. */
 int rs_debug_error_locators(int field_bits, int data_shards, int parity_shards, const uint8_t *erased,
                             uint32_t *out);
+/* Column idx of the encode's generator matrix: out[i] = G[i][idx] for the p parity
+ * rows, the symbols the reference's encode produces for the unit symbol 1 in data
+ * row idx (the constants of the incremental update).  RS_ERR_INVALID_ARG for bad
+ * arguments, RS_ERR_PANIC where the reference's encode panics. */
+int rs_debug_generator(int field_bits, int data_shards, int parity_shards, int idx, uint32_t *out /* p symbols */);
 
 /* Checks the half-wave split schedules of the GF(2^16) encode kernel
  * (logm 2..5) against the plain butterfly order on random symbols and

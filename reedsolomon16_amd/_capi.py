@@ -52,6 +52,10 @@ def lib() -> C.CDLL:
     L.rs_reconstruct_dev_batch.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint8), sz, i32, vp]
     L.rs_verify_dev_batch.argtypes = [vp, vp, sz, sz, i32, sz, P(i32), vp]
     L.rs_encode_dev_batch.argtypes = [vp, vp, sz, sz, i32, sz, vp]
+    L.rs_update_dev.argtypes = [vp, P(vp), P(vp), sz, vp]
+    L.rs_encode_idx_dev.argtypes = [vp, vp, i32, P(vp), sz, vp]
+    L.rs_update_dev_batch.argtypes = [vp, vp, sz, sz, i32, P(i32), i32, vp, sz, sz, sz, vp]
+    L.rs_debug_generator.argtypes = [i32, i32, i32, i32, vp]
     L.rs_set_host_segment.argtypes = [vp, sz]
     L.rs_set_reference_inversion_cache.argtypes = [vp, i32]
     L.rs_split_shard_size.argtypes = [vp, sz, P(sz)]

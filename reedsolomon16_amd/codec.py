@@ -202,6 +202,26 @@ def _dev_rows(rows, total: int):
     return ptrs, S or 0
 
 
+def _dev_rows_opt(rows, count: int):
+    """A list of `count` contiguous uint8 CUDA tensors, None for the entries a
+    call does not touch -> (ptr array with NULLs, shard size or None when every
+    entry is None).  All rows given must have one size."""
+    if len(rows) != count:
+        raise ErrTooFewShards("need %d shards, got %d" % (count, len(rows)))
+    ptrs = (C.c_void_p * count)()
+    S = None
+    for i, t in enumerate(rows):
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype.itemsize != 1 or not t.is_contiguous():
+            raise TypeError("device shards must be contiguous uint8 CUDA tensors")
+        if S is not None and t.numel() != S:
+            raise ErrShardSize("device shards differ in size: %d and %d bytes" % (S, t.numel()))
+        ptrs[i] = t.data_ptr()
+        S = t.numel()
+    return ptrs, S
+
+
 RS_NULL_STREAM = C.c_void_p(-1).value  # include/rs_mi355x.h: HIP's null stream, asynchronous
 
 
@@ -699,6 +719,50 @@ class ReedSolomon:
         n, _, S = slab.shape
         _check(self._L.rs_encode_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, S,
                                            _stream_handle(stream)))
+
+    # ---------------- incremental update of device rows (beyond the reference:
+    # its Leopard codecs reject Update / EncodeIdx; the encode is GF-linear, so
+    # a changed data row moves each parity row by one constant times the change)
+    def update_dev(self, rows, new_rows, stream=None) -> None:
+        """parity ^= G * (new ^ old) for the data rows with new_rows[i] not None
+        (rs_update_dev).  rows: k+p tensors, None allowed for data rows that do
+        not change; a changed entry holds the OLD row.  new_rows: k entries.
+        Parity rows are updated in place, data rows are not written."""
+        ptrs, S = _dev_rows_opt(rows, self.total_shards())
+        nptrs, Sn = _dev_rows_opt(new_rows, self.data_shards())
+        if S is not None and Sn is not None and S != Sn:
+            raise ErrShardSize("new rows of %d bytes for shards of %d" % (Sn, S))
+        _check(self._L.rs_update_dev(self._h, ptrs, nptrs, S or 0, _stream_handle(stream)))
+
+    def encode_idx_dev(self, data_row, idx: int, parity_rows, stream=None) -> None:
+        """parity ^= G[:, idx] * data_row (rs_encode_idx_dev): feeding every data
+        row once into zeroed parity rows gives encode_dev's parity."""
+        if not data_row.is_cuda or data_row.dtype.itemsize != 1 or not data_row.is_contiguous():
+            raise TypeError("device shards must be contiguous uint8 CUDA tensors")
+        ptrs, S = _dev_rows_opt(parity_rows, self.parity_shards())
+        if S is not None and S != data_row.numel():
+            raise ErrShardSize("parity rows of %d bytes for a data row of %d" % (S, data_row.numel()))
+        _check(self._L.rs_encode_idx_dev(self._h, data_row.data_ptr(), int(idx), ptrs, data_row.numel(),
+                                         _stream_handle(stream)))
+
+    def update_dev_batch(self, slab, idx: Sequence[int], new, stream=None) -> None:
+        """Replace data shards `idx` of every stripe of a [nstripes, k+p, S] slab
+        by new[:, j] (new: [nstripes, len(idx), S]) and update the parity rows
+        to match, in place (rs_update_dev_batch).  Both are uint8 CUDA tensors
+        with contiguous rows; strides come from the tensors."""
+        if slab.dim() != 3 or slab.shape[1] != self.total_shards():
+            raise TypeError("slab must be a [nstripes, k+p, S] uint8 CUDA tensor")
+        if not slab.is_cuda or slab.dtype.itemsize != 1 or slab.stride(2) != 1:
+            raise TypeError("slab rows must be contiguous uint8 on a CUDA device")
+        idx = [int(i) for i in idx]
+        n, _, S = slab.shape
+        if new.dim() != 3 or tuple(new.shape) != (n, len(idx), S):
+            raise TypeError("new must be a [nstripes, len(idx), S] uint8 CUDA tensor")
+        if not new.is_cuda or new.dtype.itemsize != 1 or new.stride(2) != 1:
+            raise TypeError("new rows must be contiguous uint8 on a CUDA device")
+        arr = (C.c_int * max(len(idx), 1))(*idx)
+        _check(self._L.rs_update_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, arr, len(idx),
+                                           new.data_ptr(), new.stride(1), new.stride(0), S, _stream_handle(stream)))
 
 
 class EncodeTicket:

@@ -87,21 +87,11 @@ struct RecPlan {
     std::vector<uint32_t> tw_in, tw_out;
 };
 
-// A cached reconstruct plan with its per-pattern tables (scale-in / reveal
-// images, rebuilt-row positions) resident in HBM: rs_reconstruct_dev of a
-// pattern seen before uploads only its row pointers.
-struct DevPlan {
-    RecPlan pl;
-    DevBuf<uint8_t> blob;
-    const uint32_t *tw_in = nullptr, *tw_out = nullptr;
-    const int *pos = nullptr;
-    const int *src_idx = nullptr, *dst_idx = nullptr;  // pl.src_shard / pl.dst_shard (strided launches)
-    uint32_t need[8] = {};
-    const uint32_t *need_w = nullptr;  // the revealed-row mask, n / 32 words (kernels read it for n > 256)
-    const int *rev = nullptr;          // output index of each work row, -1: not revealed (n > 256)
-    // One event per stream that launched with this plan, recorded after each
-    // such launch: an eviction frees blob only after the last launch on every
-    // one of those streams (one event alone would cover only the latest).
+// The streams that launched with a cached device blob.  One event per stream,
+// recorded after each such launch: an eviction frees the blob only after the
+// last launch on every one of those streams (one event alone would cover only
+// the latest).
+struct StreamUses {
     std::vector<std::pair<hipStream_t, hipEvent_t>> used;
     hipError_t mark_used(hipStream_t s) {
         for (auto &u : used)
@@ -123,11 +113,43 @@ struct DevPlan {
         used.emplace_back(s, ev);
         return hipEventRecord(ev, s);
     }
-    ~DevPlan() {
+    // Host wait for the last launch on every stream (before the blob is freed).
+    void drain() {
         for (auto &u : used) {
             (void)hipEventSynchronize(u.second);
             (void)hipEventDestroy(u.second);
         }
+        used.clear();
+    }
+};
+
+// A cached reconstruct plan with its per-pattern tables (scale-in / reveal
+// images, rebuilt-row positions) resident in HBM: rs_reconstruct_dev of a
+// pattern seen before uploads only its row pointers.
+struct DevPlan : StreamUses {
+    RecPlan pl;
+    DevBuf<uint8_t> blob;
+    const uint32_t *tw_in = nullptr, *tw_out = nullptr;
+    const int *pos = nullptr;
+    const int *src_idx = nullptr, *dst_idx = nullptr;  // pl.src_shard / pl.dst_shard (strided launches)
+    uint32_t need[8] = {};
+    const uint32_t *need_w = nullptr;  // the revealed-row mask, n / 32 words (kernels read it for n > 256)
+    const int *rev = nullptr;          // output index of each work row, -1: not revealed (n > 256)
+    ~DevPlan() {
+        drain();
+        blob.release();
+    }
+};
+
+// The device tables of an incremental update for one ordered list of changed
+// data rows: p x t multiply-by-G[i][idx[j]] images (make_update_tables) and
+// the indices themselves (the strided kernel reads them).
+struct UpdPlan : StreamUses {
+    DevBuf<uint8_t> blob;
+    const uint32_t *tw = nullptr;
+    const int *idx = nullptr;
+    ~UpdPlan() {
+        drain();
         blob.release();
     }
 };
@@ -205,6 +227,9 @@ struct rs_codec {
     hipEvent_t ring_ev[kRing] = {};
     bool ring_used[kRing] = {};
     int ring_next = 0;
+    // incremental-update tables keyed by the ordered list of changed indices
+    // (bounded LRU, as dplan_cache); their row pointers use the ring above
+    std::list<std::pair<std::vector<int>, std::unique_ptr<UpdPlan>>> uplan_cache;
 
     // error-locator cache keyed by erasure pattern (bounded LRU)
     std::list<std::pair<std::vector<uint8_t>, std::vector<uint32_t>>> el_cache;
@@ -258,6 +283,7 @@ struct rs_codec {
         rc_blob.release();
         if (rc_host) (void)hipHostFree(rc_host);
         dplan_cache.clear();  // each plan waits for its last launch
+        uplan_cache.clear();
         for (int i = 0; i < kRing; i++)
             if (ring_ev[i]) {
                 (void)hipEventSynchronize(ring_ev[i]);
@@ -1042,6 +1068,32 @@ int launch_rec_plan(rs_codec *c, DevPlan *dpl, uint8_t *base, uint64_t stride, u
     return RS_OK;
 }
 
+// The next slot of the per-call row-pointer ring with room for `want` bytes:
+// its pinned host half h and its HBM half g, free once the copy and the kernel
+// of the slot's previous call are done.  The caller fills h, copies it to g on
+// its stream, launches, and records ring_ev[slot] there (ring_used[slot] = true).
+int ring_acquire(rs_codec *c, size_t want, int &slot, uint8_t *&h, uint8_t *&g) {
+    const size_t bytes = (want + 255) & ~(size_t)255;
+    if (c->ring_slot < bytes) {
+        for (int i = 0; i < rs_codec::kRing; i++)
+            if (c->ring_used[i]) HIP_TRY(hipEventSynchronize(c->ring_ev[i]));
+        if (c->ring_host) HIP_TRY(hipHostFree(c->ring_host));
+        c->ring_host = nullptr;
+        c->ring_slot = 0;
+        HIP_TRY(c->ring_dev.ensure(bytes * rs_codec::kRing));
+        HIP_TRY(hipHostMalloc((void **)&c->ring_host, bytes * rs_codec::kRing, hipHostMallocDefault));
+        c->ring_slot = bytes;
+    }
+    const int i = c->ring_next;
+    c->ring_next = (i + 1) % rs_codec::kRing;
+    if (!c->ring_ev[i]) HIP_TRY(hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming));
+    if (c->ring_used[i]) HIP_TRY(hipEventSynchronize(c->ring_ev[i]));  // its copy and kernel are done
+    slot = i;
+    h = c->ring_host + (size_t)i * c->ring_slot;
+    g = c->ring_dev.p + (size_t)i * c->ring_slot;
+    return RS_OK;
+}
+
 // rs_reconstruct_dev with rec_lds_ok (one LDS-resident launch): the plan's tables
 // stay in HBM; equally strided shards (an AllocAligned slab, a torch 2-D
 // tensor) go to the kernel as base + stride, other layouts' row pointers
@@ -1095,23 +1147,9 @@ int reconstruct_device_lds(rs_codec *c, uint8_t *const *d, const std::vector<uin
             return RS_OK;
         }
     }
-    const size_t bytes = ((size_t)(n + nd) * sizeof(void *) + 255) & ~(size_t)255;
-    if (c->ring_slot < bytes) {
-        for (int i = 0; i < rs_codec::kRing; i++)
-            if (c->ring_used[i]) HIP_TRY(hipEventSynchronize(c->ring_ev[i]));
-        if (c->ring_host) HIP_TRY(hipHostFree(c->ring_host));
-        c->ring_host = nullptr;
-        c->ring_slot = 0;
-        HIP_TRY(c->ring_dev.ensure(bytes * rs_codec::kRing));
-        HIP_TRY(hipHostMalloc((void **)&c->ring_host, bytes * rs_codec::kRing, hipHostMallocDefault));
-        c->ring_slot = bytes;
-    }
-    const int i = c->ring_next;
-    c->ring_next = (i + 1) % rs_codec::kRing;
-    if (!c->ring_ev[i]) HIP_TRY(hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming));
-    if (c->ring_used[i]) HIP_TRY(hipEventSynchronize(c->ring_ev[i]));  // its copy and kernel are done
-    uint8_t *h = c->ring_host + (size_t)i * c->ring_slot;
-    uint8_t *g = c->ring_dev.p + (size_t)i * c->ring_slot;
+    int i = 0;
+    uint8_t *h = nullptr, *g = nullptr;
+    if (int e = ring_acquire(c, (size_t)(n + nd) * sizeof(void *), i, h, g)) return e;
     const uint8_t **src = (const uint8_t **)h;
     uint8_t **dst = (uint8_t **)h + n;
     for (int r = 0; r < n; r++) src[r] = pl.src_shard[r] >= 0 ? d[pl.src_shard[r]] : nullptr;
@@ -1123,6 +1161,108 @@ int reconstruct_device_lds(rs_codec *c, uint8_t *const *d, const std::vector<uin
     HIP_TRY(hipEventRecord(c->ring_ev[i], s));
     c->ring_used[i] = true;
     HIP_TRY(dp->mark_used(s));
+    return RS_OK;
+}
+
+// ---- Incremental update (rs_update_dev / rs_encode_idx_dev / rs_update_dev_batch)
+// Cached device tables for the ordered index list `idx`, built and uploaded on first use.
+int upd_plan(rs_codec *c, const std::vector<int> &idx, UpdPlan **out) {
+    for (auto it = c->uplan_cache.begin(); it != c->uplan_cache.end(); ++it) {
+        if (it->first == idx) {
+            c->uplan_cache.splice(c->uplan_cache.begin(), c->uplan_cache, it);
+            *out = c->uplan_cache.front().second.get();
+            return RS_OK;
+        }
+    }
+    const int t = (int)idx.size();
+    const size_t s_tw = (size_t)c->p * t * c->twd * 4;
+    const size_t o_idx = (s_tw + 255) & ~(size_t)255, total = o_idx + (((size_t)t * 4 + 255) & ~(size_t)255);
+    std::vector<uint8_t> h(total, 0);
+    make_update_tables(*c->F, c->k, c->p, idx.data(), t, c->enc_ifft_logs, c->enc_fft_logs, (uint32_t *)h.data());
+    std::memcpy(h.data() + o_idx, idx.data(), (size_t)t * 4);
+    auto up = std::make_unique<UpdPlan>();
+    HIP_TRY(up->blob.ensure(total));
+    HIP_TRY(hipMemcpy(up->blob.p, h.data(), total, hipMemcpyHostToDevice));
+    up->tw = (const uint32_t *)up->blob.p;
+    up->idx = (const int *)(up->blob.p + o_idx);
+    c->uplan_cache.emplace_front(idx, std::move(up));
+    if (c->uplan_cache.size() > 16) c->uplan_cache.pop_back();  // waits for the plan's last launch
+    *out = c->uplan_cache.front().second.get();
+    return RS_OK;
+}
+
+// Changed rows per plan: a plan's tables take p * t * twd * 4 bytes, so a long
+// index list on a codec with many parity rows runs as several plans (each its
+// own cache entry), one after the other on the stream.
+int upd_piece(const rs_codec *c) {
+    constexpr size_t kUpdPlanBytes = 32u << 20;
+    const size_t per_row = (size_t)c->p * c->twd * 4;
+    return (int)std::max<size_t>(kUpdGroup, kUpdPlanBytes / per_row / kUpdGroup * kUpdGroup);
+}
+
+// Pointer form: parity rows par[0..p), differences old[j] ^ nw[j] of data rows
+// idx[j] (old == nullptr: the rows nw themselves, EncodeIdx).  The row
+// pointers travel through a ring slot, so nothing waits for the kernel.
+int update_device_rows(rs_codec *c, uint8_t *const *par, const std::vector<int> &idx, const uint8_t *const *old,
+                       const uint8_t *const *nw, uint64_t S, hipStream_t s) {
+    const int piece = upd_piece(c), p = c->p;
+    for (size_t j0 = 0; j0 < idx.size(); j0 += piece) {
+        const int t = (int)std::min<size_t>(piece, idx.size() - j0);
+        UpdPlan *up = nullptr;
+        if (int e = upd_plan(c, std::vector<int>(idx.begin() + j0, idx.begin() + j0 + t), &up)) return e;
+        int slot = 0;
+        uint8_t *h = nullptr, *g = nullptr;
+        const size_t bytes = (size_t)(p + 2 * t) * sizeof(void *);
+        if (int e = ring_acquire(c, bytes, slot, h, g)) return e;
+        const uint8_t **rows = (const uint8_t **)h;
+        for (int i = 0; i < p; i++) rows[i] = par[i];
+        for (int j = 0; j < t; j++) {
+            rows[p + j] = old ? old[j0 + j] : nullptr;
+            rows[p + t + j] = nw[j0 + j];
+        }
+        HIP_TRY(hipMemcpyAsync(g, h, bytes, hipMemcpyHostToDevice, s));
+        UpdateArgs a{};
+        a.rows = (uint8_t *const *)g;
+        a.tw = up->tw;
+        a.S = S;
+        a.k = c->k;
+        a.p = p;
+        a.t = t;
+        a.nstripes = 1;
+        HIP_TRY(launch_update(c->bits, a, s));
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+        HIP_TRY(up->mark_used(s));
+    }
+    return RS_OK;
+}
+
+// Strided form over an rs_encode_dev_batch slab (kernels.hpp UpdateArgs).
+int update_device_batch(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, int nstripes,
+                        const std::vector<int> &idx, const uint8_t *nbase, uint64_t new_row_stride,
+                        uint64_t new_stripe_stride, uint64_t S, hipStream_t s) {
+    const int piece = upd_piece(c);
+    for (size_t j0 = 0; j0 < idx.size(); j0 += piece) {
+        const int t = (int)std::min<size_t>(piece, idx.size() - j0);
+        UpdPlan *up = nullptr;
+        if (int e = upd_plan(c, std::vector<int>(idx.begin() + j0, idx.begin() + j0 + t), &up)) return e;
+        UpdateArgs a{};
+        a.base = base;
+        a.nbase = nbase + j0 * new_row_stride;
+        a.row_stride = row_stride;
+        a.stripe_stride = stripe_stride;
+        a.new_row_stride = new_row_stride;
+        a.new_stripe_stride = new_stripe_stride;
+        a.idx = up->idx;
+        a.tw = up->tw;
+        a.S = S;
+        a.k = c->k;
+        a.p = c->p;
+        a.t = t;
+        a.nstripes = nstripes;
+        HIP_TRY(launch_update(c->bits, a, s));
+        HIP_TRY(up->mark_used(s));
+    }
     return RS_OK;
 }
 
@@ -2258,6 +2398,89 @@ int rs_host_register(void *p, size_t bytes) {
 int rs_host_unregister(void *p) {
     if (!p) return RS_ERR_INVALID_ARG;
     HIP_TRY(hipHostUnregister(p));
+    return RS_OK;
+}
+
+// ---- Incremental update for device rows (beyond the reference; rs_mi355x.h).
+// Every error is decided before the first device call.
+int rs_update_dev(rs_codec *c, uint8_t *const *d, uint8_t *const *d_new, size_t S, void *stream) {
+    if (!c || !d || !d_new) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    for (int i = c->k; i < c->total; i++)
+        if (!d[i]) return RS_ERR_INVALID_ARG;
+    std::vector<int> idx;
+    std::vector<const uint8_t *> old, nw;
+    for (int i = 0; i < c->k; i++) {
+        if (!d_new[i]) continue;
+        if (!d[i]) return RS_ERR_INVALID_ARG;
+        idx.push_back(i);
+        old.push_back(d[i]);
+        nw.push_back(d_new[i]);
+    }
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (idx.empty()) return RS_OK;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    if (int ie = ensure_device(c)) return ie;
+    hipStream_t s = pick_stream(c, stream);
+    if (int e = update_device_rows(c, d + c->k, idx, old.data(), nw.data(), S, s)) return e;
+    if (!stream) HIP_TRY(hipStreamSynchronize(s));
+    return RS_OK;
+}
+
+int rs_encode_idx_dev(rs_codec *c, const uint8_t *row, int idx, uint8_t *const *d_parity, size_t S, void *stream) {
+    if (!c || !row || !d_parity) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    for (int i = 0; i < c->p; i++)
+        if (!d_parity[i]) return RS_ERR_INVALID_ARG;
+    if (idx < 0 || idx >= c->k) return RS_ERR_INVALID_ARG;
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    if (int ie = ensure_device(c)) return ie;
+    hipStream_t s = pick_stream(c, stream);
+    if (int e = update_device_rows(c, d_parity, {idx}, nullptr, &row, S, s)) return e;
+    if (!stream) HIP_TRY(hipStreamSynchronize(s));
+    return RS_OK;
+}
+
+int rs_update_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, int nstripes,
+                        const int *idx, int nidx, const uint8_t *d_new, size_t new_row_stride,
+                        size_t new_stripe_stride, size_t S, void *stream) {
+    if (!c || !base || !idx || !d_new || nstripes <= 0) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    if (nidx < 1 || nidx > c->k) return RS_ERR_INVALID_ARG;
+    {
+        std::vector<uint8_t> seen((size_t)c->k, 0);
+        for (int j = 0; j < nidx; j++) {
+            if (idx[j] < 0 || idx[j] >= c->k || seen[idx[j]]) return RS_ERR_INVALID_ARG;
+            seen[idx[j]] = 1;
+        }
+    }
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (row_stride < S || new_row_stride < S) return RS_ERR_INVALID_ARG;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    if (int ie = ensure_device(c)) return ie;
+    hipStream_t s = pick_stream(c, stream);
+    if (int e = update_device_batch(c, base, row_stride, stripe_stride, nstripes, std::vector<int>(idx, idx + nidx),
+                                    d_new, new_row_stride, new_stripe_stride, S, s))
+        return e;
+    if (!stream) HIP_TRY(hipStreamSynchronize(s));
+    return RS_OK;
+}
+
+int rs_debug_generator(int bits, int k, int p, int idx, uint32_t *out) {
+    if ((bits != 8 && bits != 16) || !out || k <= 0 || p <= 0 || idx < 0 || idx >= k) return RS_ERR_INVALID_ARG;
+    std::vector<uint32_t> col;
+    if (!generator_column(field(bits), k, p, idx, col)) return RS_ERR_PANIC;
+    std::copy(col.begin(), col.end(), out);
     return RS_OK;
 }
 

@@ -324,6 +324,89 @@ bool encode_schedule(const Field &F, int k, int p, std::vector<uint32_t> &ifft, 
     return sv.ok;
 }
 
+namespace {
+// The reference's butterflies (galois_noasm.go:58-76) on one symbol per row.
+struct SymRows {
+    const Field &F;
+    std::vector<uint32_t> w;
+    void ifft2(int x, int y, uint32_t lg) {
+        w[y] ^= w[x];
+        if (lg != F.mod) w[x] ^= F.mul_log(w[y], lg);
+    }
+    void fft2(int x, int y, uint32_t lg) {
+        if (lg != F.mod) w[x] ^= F.mul_log(w[y], lg);
+        w[y] ^= w[x];
+    }
+};
+}  // namespace
+
+void generator_column_from(const Field &F, int k, int p, int idx, const std::vector<uint32_t> &ifft,
+                           const std::vector<uint32_t> &fft, std::vector<uint32_t> &sym) {
+    const int m = ceil_pow2(p), logm = ilog2(m);
+    const int c = idx / m, cnt = (k - c * m) < m ? (k - c * m) : m;
+    SymRows R{F, std::vector<uint32_t>((size_t)m, 0)};
+    R.w[idx - c * m] = 1;
+    // chunk c's IFFT (ifftDITEncoder leopard16.go:694-741); every other chunk is zero
+    const uint32_t *il = ifft.data() + (size_t)c * ifft_slots(logm);
+    for (const PassInfo &ps : ifft_passes(logm)) {
+        if (ps.radix == 4) {
+            for (int g = 0; g < ps.groups; g++) {
+                const int r = g * 4 * ps.dist, d = ps.dist;
+                if (r >= cnt) break;  // groups the reference skips
+                const uint32_t *s = il + ps.slot_off + 3 * g;  // (m01, m02, m23)
+                for (int i = r; i < r + d; i++) {
+                    R.ifft2(i, i + d, s[0]);
+                    R.ifft2(i + 2 * d, i + 3 * d, s[2]);
+                    R.ifft2(i, i + 2 * d, s[1]);
+                    R.ifft2(i + d, i + 3 * d, s[1]);
+                }
+            }
+        } else {
+            for (int i = 0; i < ps.dist; i++) R.ifft2(i, i + ps.dist, il[ps.slot_off]);
+        }
+    }
+    // the final FFT (fftDIT leopard16.go:618-657), truncated to the p parity rows
+    for (const PassInfo &ps : fft_passes(logm)) {
+        if (ps.radix == 4) {
+            for (int g = 0; g < ps.groups; g++) {
+                const int r = g * 4 * ps.dist, d = ps.dist;
+                if (r >= p) break;
+                const uint32_t *s = fft.data() + ps.slot_off + 3 * g;
+                for (int i = r; i < r + d; i++) {
+                    R.fft2(i, i + 2 * d, s[1]);
+                    R.fft2(i + d, i + 3 * d, s[1]);
+                    R.fft2(i, i + d, s[0]);
+                    R.fft2(i + 2 * d, i + 3 * d, s[2]);
+                }
+            }
+        } else {
+            for (int g = 0; g < ps.groups && 2 * g < p; g++) R.fft2(2 * g, 2 * g + 1, fft[ps.slot_off + g]);
+        }
+    }
+    sym.assign(R.w.begin(), R.w.begin() + p);
+}
+
+bool generator_column(const Field &F, int k, int p, int idx, std::vector<uint32_t> &sym) {
+    if (k <= 0 || p <= 0 || idx < 0 || idx >= k) return false;
+    std::vector<uint32_t> il, fl;
+    int nchunks = 0;
+    if (!encode_schedule(F, k, p, il, fl, nchunks)) return false;
+    generator_column_from(F, k, p, idx, il, fl, sym);
+    return true;
+}
+
+void make_update_tables(const Field &F, int k, int p, const int *idx, int t, const std::vector<uint32_t> &ifft,
+                        const std::vector<uint32_t> &fft, uint32_t *out) {
+    const int twd = tw_dwords(F.bits);
+    std::vector<uint32_t> col;
+    for (int j = 0; j < t; j++) {
+        generator_column_from(F, k, p, idx[j], ifft, fft, col);
+        // log[0] is not a log: a zero coefficient ships as the zero twiddle's all-zero table
+        for (int i = 0; i < p; i++)
+            make_twiddle(F, col[i] ? F.log[col[i]] : F.mod, out + ((size_t)i * t + j) * twd, true);
+    }
+}
+
 bool decode_schedule(const Field &F, int k, int p, std::vector<uint32_t> &ifft, std::vector<uint32_t> &fft) {
     const int m = ceil_pow2(p);
     if ((long)m + k > (long)F.order) return false;  // the Go code panics (see error_locators)

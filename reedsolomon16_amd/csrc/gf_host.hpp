@@ -118,6 +118,24 @@ int fft_slots(int logm);
 bool encode_schedule(const Field &F, int k, int p, std::vector<uint32_t> &ifft_logs, std::vector<uint32_t> &fft_logs,
                      int &nchunks);
 
+// Column idx of the encode's generator matrix: sym[i] = G[i][idx], i in [0, p),
+// the parity symbols the reference's encode (leopard16.go:128-224,
+// leopard8.go:153-277) produces for the unit symbol 1 in data row idx and zero
+// everywhere else.  The encode is GF-linear, so a change d in data row idx
+// changes parity row i by G[i][idx] * d.  Runs the chunk IFFT and the final FFT
+// on single symbols with encode_schedule's twiddles: only the chunk holding idx
+// is non-zero, O(m log m).  False where encode_schedule returns false, or for
+// idx outside [0, k).
+bool generator_column(const Field &F, int k, int p, int idx, std::vector<uint32_t> &sym);
+// The same from the logs encode_schedule returned for (k, p) (a codec keeps them).
+void generator_column_from(const Field &F, int k, int p, int idx, const std::vector<uint32_t> &ifft_logs,
+                           const std::vector<uint32_t> &fft_logs, std::vector<uint32_t> &sym);
+// Update tables for changed data rows idx[0..t): p x t images of "multiply by
+// G[i][idx[j]]" at out + (i * t + j) * tw_dwords (butterfly layout); a zero
+// coefficient is the all-zero table (its log is never taken).
+void make_update_tables(const Field &F, int k, int p, const int *idx, int t, const std::vector<uint32_t> &ifft_logs,
+                        const std::vector<uint32_t> &fft_logs, uint32_t *out);
+
 // Decoder schedules over n = ceilPow2(m+k) rows (leopard16.go:573-657).
 bool decode_schedule(const Field &F, int k, int p, std::vector<uint32_t> &ifft_logs, std::vector<uint32_t> &fft_logs);
 

@@ -2066,4 +2066,190 @@ hipError_t launch_encode_lds(int bits, int logm, bool verify, const EncodeArgs &
     return bits == 16 ? enc_lds_f<F16<4>>(logm, verify, a, s) : enc_lds_f<F8<4>>(logm, verify, a, s);
 }
 
+// ---------------------------------------------------------------- incremental parity update
+// parity row i ^= XOR over the changed data rows j of G[i][j] * (old_j ^ new_j)
+// (kernels.hpp UpdateArgs, gf_host.hpp generator_column).  A stream: every
+// byte is read once and written at most once, nothing is shared between lanes.
+namespace {
+
+// The nibble masks of mul_add depend only on the multiplicand.  An update
+// multiplies one difference by p constants, so the masks are prepared once per
+// difference and shared by all p rows: a product is then 12 v_perm_b32 +
+// 6 v_bitop3 per 4 symbols in GF(2^16) (3 + 2 in GF(2^8)) and no shifts.
+template <class F>
+struct UpdMasks;
+template <int W>
+struct UpdMasks<F16<W>> {
+    uint32_t a0[W], a1[W], a2[W], b0[W], b1[W], b2[W];
+    __device__ __forceinline__ void prepare(const typename F16<W>::Vec &y) {
+#pragma unroll
+        for (int i = 0; i < W; i++) {
+            const uint32_t lo = y.l[i], hi = y.h[i];
+            a0[i] = lo & 0x07070707u, a1[i] = (lo >> 3) & 0x07070707u, a2[i] = (lo >> 6) & 0x03030303u;
+            b0[i] = hi & 0x07070707u, b1[i] = (hi >> 3) & 0x07070707u, b2[i] = (hi >> 6) & 0x03030303u;
+        }
+    }
+    // x ^= y * c: t = c's table (F16::mul_add's layout), masks of y
+    __device__ __forceinline__ void mul_add(typename F16<W>::Vec &x, const uint32_t *t) const {
+#pragma unroll
+        for (int i = 0; i < W; i++) {
+            x.l[i] = xor3(xor3(xor3(x.l[i], perm(t[1], t[0], a0[i]), perm(t[5], t[4], a1[i])), perm(t[8], t[8], a2[i]),
+                               perm(t[11], t[10], b0[i])),
+                          perm(t[15], t[14], b1[i]), perm(t[18], t[18], b2[i]));
+            x.h[i] = xor3(xor3(xor3(x.h[i], perm(t[3], t[2], a0[i]), perm(t[7], t[6], a1[i])), perm(t[9], t[9], a2[i]),
+                               perm(t[13], t[12], b0[i])),
+                          perm(t[17], t[16], b1[i]), perm(t[19], t[19], b2[i]));
+        }
+    }
+};
+template <int W>
+struct UpdMasks<F8<W>> {
+    uint32_t a0[W], a1[W], a2[W];
+    __device__ __forceinline__ void prepare(const typename F8<W>::Vec &y) {
+#pragma unroll
+        for (int i = 0; i < W; i++) {
+            const uint32_t v = y.b[i];
+            a0[i] = v & 0x07070707u, a1[i] = (v >> 3) & 0x07070707u, a2[i] = (v >> 6) & 0x03030303u;
+        }
+    }
+    __device__ __forceinline__ void mul_add(typename F8<W>::Vec &x, const uint32_t *t) const {
+#pragma unroll
+        for (int i = 0; i < W; i++)
+            x.b[i] = xor3(x.b[i] ^ perm(t[1], t[0], a0[i]), perm(t[3], t[2], a1[i]), perm(t[4], t[4], a2[i]));
+    }
+};
+
+constexpr int kUpdRows = 4;  // parity rows whose loads a lane keeps in flight
+
+// Row pointers and changed indices are read-only for the whole launch: through
+// the constant address space their wave-uniform loads are scalar (as load_tab).
+typedef uint8_t *upd_rowp_t;
+typedef __attribute__((address_space(4))) const upd_rowp_t upd_crowp_t;
+typedef __attribute__((address_space(4))) const int upd_cint_t;
+__device__ __forceinline__ uint8_t *upd_row(uint8_t *const *rows, int i) { return ((upd_crowp_t *)rows)[i]; }
+
+// NT changed rows [j0, j0 + NT) of the call's t; PTR: rows through a.rows (one
+// stripe), else strided rows of stripe blockIdx.y + y0 with the new rows
+// stored over the old ones.  All addresses are 64-bit (row pointer + offset).
+template <class F, int NT, bool PTR>
+__global__ void __launch_bounds__(256, 2) k_update(UpdateArgs a, int j0, int y0) {
+    typedef typename F::Vec V;
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    UpdMasks<F> mk[NT];
+    uint8_t *pbase = nullptr;
+    if constexpr (PTR) {
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            const uint8_t *o = upd_row(a.rows, a.p + j0 + j), *n = upd_row(a.rows, a.p + a.t + j0 + j);
+            V d = F::load(n, u);
+            if (o) F::xor_into(d, F::load(o, u));  // wave-uniform; no old row: the row is the difference
+            mk[j].prepare(d);
+        }
+    } else {
+        const uint64_t z = (uint64_t)blockIdx.y + (uint64_t)y0;
+        uint8_t *sb = a.base + z * a.stripe_stride;
+        const uint8_t *nb = a.nbase + z * a.new_stripe_stride + (uint64_t)j0 * a.new_row_stride;
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            uint8_t *o = sb + (uint64_t)((upd_cint_t *)a.idx)[j0 + j] * a.row_stride;
+            const V nv = F::load(nb + (uint64_t)j * a.new_row_stride, u);
+            V d = F::load(o, u);
+            F::store(o, u, nv);
+            F::xor_into(d, nv);
+            mk[j].prepare(d);
+        }
+        pbase = sb + (uint64_t)a.k * a.row_stride;
+    }
+    const uint32_t *tw = a.tw + (uint64_t)j0 * F::TWD;  // table (i, j0 + j) at tw + (i * t + j) * TWD
+    const uint64_t trow = (uint64_t)a.t * F::TWD;
+    auto prow = [&](int i) -> uint8_t * {
+        if constexpr (PTR) return upd_row(a.rows, i);
+        else return pbase + (uint64_t)i * a.row_stride;
+    };
+    int i = 0;
+    for (; i + kUpdRows <= a.p; i += kUpdRows) {
+        uint8_t *r[kUpdRows];
+        V x[kUpdRows];
+#pragma unroll
+        for (int q = 0; q < kUpdRows; q++) {
+            r[q] = prow(i + q);
+            x[q] = F::load(r[q], u);
+        }
+#pragma unroll
+        for (int q = 0; q < kUpdRows; q++) {
+#pragma unroll
+            for (int j = 0; j < NT; j++) {
+                const Tab<F> tb = load_tab<F>(tw + (uint64_t)(i + q) * trow + (uint64_t)j * F::TWD);
+                mk[j].mul_add(x[q], tb.v);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kUpdRows; q++) F::store(r[q], u, x[q]);
+    }
+    for (; i < a.p; i++) {
+        uint8_t *r = prow(i);
+        V x = F::load(r, u);
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            const Tab<F> tb = load_tab<F>(tw + (uint64_t)i * trow + (uint64_t)j * F::TWD);
+            mk[j].mul_add(x, tb.v);
+        }
+        F::store(r, u, x);
+    }
+}
+
+template <class F, int NT>
+hipError_t update_group(const UpdateArgs &a, int j0, hipStream_t s) {
+    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
+    if (a.rows) {
+        hipLaunchKernelGGL((k_update<F, NT, true>), grid_x(units), dim3(256), 0, s, a, j0, 0);
+        return hipGetLastError();
+    }
+    return for_y(a.nstripes, [&](int y0, int ny) {
+        hipLaunchKernelGGL((k_update<F, NT, false>), dim3(grid_x(units).x, ny), dim3(256), 0, s, a, j0, y0);
+    });
+}
+
+template <class F>
+hipError_t update_f(const UpdateArgs &a, hipStream_t s) {
+    static_assert(kUpdGroup == 8, "update_f dispatches group sizes 1..8");
+    // ceil(t / kUpdGroup) launches of sizes as equal as t allows: a launch costs
+    // one pass over the parity rows plus a part that grows faster than its row
+    // count past 6 rows (registers: two waves per SIMD), so 9 rows run as 5 + 4
+    // (32 us per C3 stripe), not 8 + 1 (45 us).
+    const int nl = (a.t + kUpdGroup - 1) / kUpdGroup;
+    for (int g = 0, j0 = 0, nt = 0; g < nl; g++, j0 += nt) {
+        nt = a.t / nl + (g < a.t % nl ? 1 : 0);
+        hipError_t e;
+        switch (nt) {
+            case 1: e = update_group<F, 1>(a, j0, s); break;
+            case 2: e = update_group<F, 2>(a, j0, s); break;
+            case 3: e = update_group<F, 3>(a, j0, s); break;
+            case 4: e = update_group<F, 4>(a, j0, s); break;
+            case 5: e = update_group<F, 5>(a, j0, s); break;
+            case 6: e = update_group<F, 6>(a, j0, s); break;
+            case 7: e = update_group<F, 7>(a, j0, s); break;
+            default: e = update_group<F, 8>(a, j0, s); break;
+        }
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace
+
+// 32-byte units (16 in GF(2^8)) per lane, or 16-byte (8) ones where the wide
+// units would leave fewer than kUpdMinBlocks workgroups for the device.
+hipError_t launch_update(int bits, const UpdateArgs &a, hipStream_t s) {
+    constexpr uint64_t kUpdMinBlocks = 1024;
+    if (a.p <= 0 || a.t <= 0 || a.S == 0 || a.S % 64 || !a.tw) return hipErrorInvalidValue;
+    if (!a.rows && (!a.base || !a.nbase || !a.idx || a.nstripes <= 0)) return hipErrorInvalidValue;
+    const uint64_t ns = a.rows ? 1 : (uint64_t)a.nstripes;
+    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * ns;
+    const bool narrow = pick_narrow(wide_blocks < kUpdMinBlocks);
+    if (bits == 16) return narrow ? update_f<F16<2>>(a, s) : update_f<F16<4>>(a, s);
+    return narrow ? update_f<F8<2>>(a, s) : update_f<F8<4>>(a, s);
+}
+
 }  // namespace rs

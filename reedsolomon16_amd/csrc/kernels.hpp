@@ -197,4 +197,28 @@ bool encode_bs_fits(int k, int p, uint64_t row_stride, uint64_t S);
 hipError_t launch_encode_bs(bool verify, const BsArgs &a, int cus, hipStream_t s);
 
 
+// ---- Incremental parity update: parity row i ^= sum over changed data rows j
+// of G[i][j] * (old_j ^ new_j) (gf_host.hpp generator_column).  One lane owns
+// one unit of one column of every row it touches; grid.y = stripe.
+constexpr int kUpdGroup = 8;  // changed rows per launch (k_update's T)
+struct UpdateArgs {
+    // pointer form (rows != nullptr): a device array of p parity rows, then t
+    // old rows, then t new rows; one stripe.  An old entry is nullptr when the
+    // row itself is the difference (EncodeIdx).
+    uint8_t *const *rows;
+    // strided form: parity row i of stripe z at base + z*stripe_stride +
+    // (k+i)*row_stride, old row of changed index j at idx[j]; its new row at
+    // nbase + z*new_stripe_stride + j*new_row_stride, stored over the old one
+    uint8_t *base;
+    const uint8_t *nbase;
+    uint64_t row_stride, stripe_stride, new_row_stride, new_stripe_stride;
+    const int *idx;      // device array, t changed indices (strided form)
+    const uint32_t *tw;  // p x t tables, (i, j) at (i*t + j) * tw_dwords (make_update_tables)
+    uint64_t S;
+    int k, p, t, nstripes;
+};
+// Runs the t changed rows as ceil(t / kUpdGroup) launches on s.
+hipError_t launch_update(int bits, const UpdateArgs &a, hipStream_t s);
+
+
 }  // namespace rs

@@ -57,6 +57,30 @@ struct DevBuf {
     }
 };
 
+// Pinned host memory grown on demand, the host-side twin of DevBuf.  Neither
+// has a destructor: ~rs_codec releases them while its DeviceGuard is alive.
+struct PinnedBuf {
+    uint8_t *p = nullptr;
+    size_t n = 0;  // bytes
+    hipError_t ensure(size_t want) {
+        if (want <= n) return hipSuccess;
+        hipError_t e = p ? hipHostFree(p) : hipSuccess;
+        if (e != hipSuccess) return e;
+        p = nullptr;
+        n = 0;
+        e = hipHostMalloc((void **)&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) n = want;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+    }
+};
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 // Scoped hipSetDevice that restores the caller's device.
 struct DeviceGuard {
     int prev = -1;
@@ -76,6 +100,14 @@ struct DeviceGuard {
         hipError_t e_ = (x);                         \
         if (e_ != hipSuccess) return RS_ERR_DEVICE;  \
     } while (0)
+
+// Grow `dst` to the size of a host table and copy the table there.
+template <class T>
+int upload(DevBuf<T> &dst, const std::vector<T> &src) {
+    HIP_TRY(dst.ensure(src.size()));
+    HIP_TRY(hipMemcpy(dst.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return RS_OK;
+}
 
 // Host half of a reconstruct (leopard16.go:432-568) for one erasure pattern:
 // which shard feeds each of the n work rows, the input scalings (errLocs),
@@ -154,6 +186,27 @@ struct UpdPlan : StreamUses {
     }
 };
 
+// A small bounded LRU, most recent first.  find() moves a hit to the front;
+// put() inserts at the front and evicts past the cache's capacity, which runs
+// the evicted value's destructor (a DevPlan / UpdPlan waits there for its last
+// launch on every stream).  A pointer handed out stays valid until the next
+// put() into the same cache (calls are serialized by the codec mutex).
+template <class K, class V, size_t Cap>
+struct Lru {
+    std::list<std::pair<K, V>> items;
+    V *find(const K &key) {
+        auto it = std::find_if(items.begin(), items.end(), [&](const auto &e) { return e.first == key; });
+        if (it == items.end()) return nullptr;
+        items.splice(items.begin(), items, it);
+        return &items.front().second;
+    }
+    V *put(K key, V val) {
+        items.emplace_front(std::move(key), std::move(val));
+        if (items.size() > Cap) items.pop_back();
+        return &items.front().second;
+    }
+};
+
 }  // namespace
 
 struct rs_codec {
@@ -207,32 +260,31 @@ struct rs_codec {
     int *hflag = nullptr, *dflag = nullptr;  // verify mismatch word: device word + pinned host readback
     // per-call reconstruct inputs, packed into one blob and uploaded with one copy
     DevBuf<uint8_t> rc_blob;
-    uint8_t *rc_host = nullptr;  // pinned staging of the blob
-    size_t rc_host_n = 0;
+    PinnedBuf rc_host;  // pinned staging of the blob
     const uint8_t **rc_src = nullptr;
     uint8_t **rc_dst = nullptr;
     uint32_t *rc_tw_in = nullptr, *rc_tw_out = nullptr;
     int *rc_pos = nullptr;
 
     // reconstruct plans keyed by (erasure pattern, recover_all) (bounded LRU)
-    std::list<std::pair<std::vector<uint8_t>, RecPlan>> plan_cache;
+    Lru<std::vector<uint8_t>, RecPlan, 16> plan_cache;
     // device-resident plans of rs_reconstruct_dev (same key), and a ring of
     // per-call row-pointer slots (pinned host + HBM), each reusable once the
     // launch that read it has finished (ring_ev)
-    std::list<std::pair<std::vector<uint8_t>, std::unique_ptr<DevPlan>>> dplan_cache;
+    Lru<std::vector<uint8_t>, std::unique_ptr<DevPlan>, 16> dplan_cache;
     static constexpr int kRing = 8;
     DevBuf<uint8_t> ring_dev;
-    uint8_t *ring_host = nullptr;
+    PinnedBuf ring_host;
     size_t ring_slot = 0;  // bytes per slot
     hipEvent_t ring_ev[kRing] = {};
     bool ring_used[kRing] = {};
     int ring_next = 0;
     // incremental-update tables keyed by the ordered list of changed indices
     // (bounded LRU, as dplan_cache); their row pointers use the ring above
-    std::list<std::pair<std::vector<int>, std::unique_ptr<UpdPlan>>> uplan_cache;
+    Lru<std::vector<int>, std::unique_ptr<UpdPlan>, 16> uplan_cache;
 
     // error-locator cache keyed by erasure pattern (bounded LRU)
-    std::list<std::pair<std::vector<uint8_t>, std::vector<uint32_t>>> el_cache;
+    Lru<std::vector<uint8_t>, std::vector<uint32_t>, 64> el_cache;
     // rs_set_reference_inversion_cache: the GF(2^8) inversion cache exactly as
     // leopard8.go:508-555 keys it (raw erasure bits on lookup, bits after
     // prepare() on store), so the output is the reference's on every call
@@ -259,8 +311,7 @@ struct rs_codec {
     int *tk_hflag = nullptr, *tk_dflag = nullptr;
     uint8_t tk_kind[kTickets] = {};  // HostOp of the slot's latest ticket, + 1
     // pinned bounce slabs for outputs in pageable host memory (kHostBufs x total x seg)
-    uint8_t *bounce = nullptr;
-    size_t bounce_n = 0;
+    PinnedBuf bounce;
 
     // rs_new_multi: the per-device parts (this codec then owns no device
     // resources of its own; its caches hold the reconstruct locators)
@@ -281,20 +332,20 @@ struct rs_codec {
         if (hflag) (void)hipHostFree(hflag);
         if (dflag) (void)hipFree(dflag);
         rc_blob.release();
-        if (rc_host) (void)hipHostFree(rc_host);
-        dplan_cache.clear();  // each plan waits for its last launch
-        uplan_cache.clear();
+        rc_host.release();
+        dplan_cache.items.clear();  // each plan waits for its last launch
+        uplan_cache.items.clear();
         for (int i = 0; i < kRing; i++)
             if (ring_ev[i]) {
                 (void)hipEventSynchronize(ring_ev[i]);
                 (void)hipEventDestroy(ring_ev[i]);
             }
         ring_dev.release();
-        if (ring_host) (void)hipHostFree(ring_host);
+        ring_host.release();
         if (s_in) (void)hipStreamSynchronize(s_in);
         if (s_out) (void)hipStreamSynchronize(s_out);
         stage.release();
-        if (bounce) (void)hipHostFree(bounce);
+        bounce.release();
         for (int t = 0; t < kTickets; t++)
             if (done_ev[t]) (void)hipEventDestroy(done_ev[t]);
         if (tk_hflag) (void)hipHostFree(tk_hflag);
@@ -316,9 +367,7 @@ namespace {
 int upload_twiddles(rs_codec *c, const std::vector<uint32_t> &logs, DevBuf<uint32_t> &dst) {
     std::vector<uint32_t> host(std::max<size_t>(logs.size(), 1) * c->twd, 0);
     for (size_t i = 0; i < logs.size(); i++) make_twiddle(*c->F, logs[i], host.data() + i * c->twd, true);
-    HIP_TRY(dst.ensure(host.size()));
-    HIP_TRY(hipMemcpy(dst.p, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return RS_OK;
+    return upload(dst, host);
 }
 
 // ---- half-wave split kernel: table layout from the same compile-time schedule
@@ -361,10 +410,8 @@ int upload_split(rs_codec *c) {
     std::vector<uint32_t> hi((size_t)c->nchunks * ni), hf(std::max<size_t>(nf, 1));
     for (int ch = 0; ch < c->nchunks; ch++) split_image(*c->F, ti, c->enc_ifft_logs.data() + (size_t)ch * is, hi.data() + ch * ni);
     split_image(*c->F, tf, c->enc_fft_logs.data(), hf.data());
-    HIP_TRY(c->tws_ifft.ensure(hi.size()));
-    HIP_TRY(c->tws_fft.ensure(hf.size()));
-    HIP_TRY(hipMemcpy(c->tws_ifft.p, hi.data(), hi.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->tws_fft.p, hf.data(), hf.size() * 4, hipMemcpyHostToDevice));
+    if (int e = upload(c->tws_ifft, hi)) return e;
+    if (int e = upload(c->tws_fft, hf)) return e;
     c->split_ok = true;
     return RS_OK;
 }
@@ -433,10 +480,8 @@ int upload_ifft_sub(rs_codec *c) {
         for (int sl = passes[nff[ch]].slot_off; sl < is; sl++)
             make_sub_twiddle(*c->F, lg[sl], ts.data() + ((size_t)ch * is + sl) * kTwDwords8);
     }
-    HIP_TRY(c->tw_ifft_sub.ensure(ts.size()));
-    HIP_TRY(c->ifft_nff.ensure(nff.size()));
-    HIP_TRY(hipMemcpy(c->tw_ifft_sub.p, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->ifft_nff.p, nff.data(), nff.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (int e = upload(c->tw_ifft_sub, ts)) return e;
+    if (int e = upload(c->ifft_nff, nff)) return e;
     c->ifft_sub = true;
     return RS_OK;
 }
@@ -475,10 +520,8 @@ int ensure_device(rs_codec *c) {
             std::vector<uint32_t> hf(std::max<size_t>(c->enc_fft_logs.size(), 1) * kTwDwords8, 0), dm(kTwDwords8, 0);
             for (size_t i = 0; i < fsub_end; i++) make_sub_twiddle(*c->F, c->enc_fft_logs[i], hf.data() + i * kTwDwords8);
             make_sub_dmap(dm.data());
-            HIP_TRY(c->tw_fft_sub.ensure(hf.size()));
-            HIP_TRY(c->tw_dmap.ensure(dm.size()));
-            HIP_TRY(hipMemcpy(c->tw_fft_sub.p, hf.data(), hf.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(c->tw_dmap.p, dm.data(), dm.size() * 4, hipMemcpyHostToDevice));
+            if (int e2 = upload(c->tw_fft_sub, hf)) return e2;
+            if (int e2 = upload(c->tw_dmap, dm)) return e2;
             c->fft_sub = true;
             if (int e2 = upload_ifft_sub(c)) return e2;
         }
@@ -517,12 +560,9 @@ int upload_big_sub(rs_codec *c, const std::vector<uint32_t> &il, const std::vect
         }
     }
     make_sub_dmap(dm.data());
-    HIP_TRY(c->dtw_ifft_sub.ensure(hi.size()));
-    HIP_TRY(c->dtw_fft_sub.ensure(hf.size()));
-    HIP_TRY(c->dec_dmap.ensure(dm.size()));
-    HIP_TRY(hipMemcpy(c->dtw_ifft_sub.p, hi.data(), hi.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->dtw_fft_sub.p, hf.data(), hf.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->dec_dmap.p, dm.data(), dm.size() * 4, hipMemcpyHostToDevice));
+    if (int e = upload(c->dtw_ifft_sub, hi)) return e;
+    if (int e = upload(c->dtw_fft_sub, hf)) return e;
+    if (int e = upload(c->dec_dmap, dm)) return e;
     c->dec_big_sub = true;
     return RS_OK;
 }
@@ -543,10 +583,8 @@ int build_decode_plan(rs_codec *c) {
         std::vector<uint32_t> hi(std::max<size_t>(il.size(), 1) * kTwDwords8, 0), hf(std::max<size_t>(fl.size(), 1) * kTwDwords8, 0);
         for (size_t i = 0; i < il.size(); i++) make_sub_twiddle(*c->F, il[i], hi.data() + i * kTwDwords8);
         for (size_t i = 0; i < fl.size(); i++) make_sub_twiddle(*c->F, fl[i], hf.data() + i * kTwDwords8);
-        HIP_TRY(c->dtw_ifft.ensure(hi.size()));
-        HIP_TRY(c->dtw_fft.ensure(hf.size()));
-        HIP_TRY(hipMemcpy(c->dtw_ifft.p, hi.data(), hi.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->dtw_fft.p, hf.data(), hf.size() * 4, hipMemcpyHostToDevice));
+        if (int e = upload(c->dtw_ifft, hi)) return e;
+        if (int e = upload(c->dtw_fft, hf)) return e;
         c->dec_sub = true;
         return RS_OK;
     }
@@ -568,6 +606,24 @@ bool rec_lds_ok(const rs_codec *c) {
 hipStream_t pick_stream(rs_codec *c, void *s) {
     return s == RS_NULL_STREAM ? (hipStream_t)0 : s ? (hipStream_t)s : c->stream;
 }
+
+// What every stream-ordered entry point does once its arguments are checked:
+// take the codec mutex, select the codec's device, create the device half on
+// first use (err), pick the call's stream; and at the end, finish().
+struct DevCall {
+    std::lock_guard<std::mutex> lk;
+    DeviceGuard g;
+    const int err;
+    const hipStream_t s;
+    const bool wait;  // no caller stream: the call completes on return
+    DevCall(rs_codec *c, void *stream)
+        : lk(c->mu), g(c->device), err(ensure_device(c)), s(pick_stream(c, stream)), wait(!stream) {}
+    int finish(int e) const {
+        if (e) return e;
+        if (wait) HIP_TRY(hipStreamSynchronize(s));
+        return RS_OK;
+    }
+};
 
 // Order this call's stream behind the previous user of the codec scratch
 // (nothing to do when that was this stream: it is in order already, and an
@@ -673,22 +729,30 @@ int encode_multipass(rs_codec *c, RowSet data, RowSet par, uint64_t S, int *mism
     return RS_OK;
 }
 
+// The arguments the register, split and LDS encode kernels share (the split
+// kernel swaps in its own tables, the LDS kernel adds its subfield tables).
+EncodeArgs encode_args(const rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t stripe_stride, int nstripes,
+                       int *mismatch) {
+    EncodeArgs a{};
+    a.data = data;
+    a.parity = par;
+    a.k = c->k;
+    a.p = c->p;
+    a.nchunks = c->nchunks;
+    a.shard_size = S;
+    a.stripe_stride = stripe_stride;
+    a.nstripes = nstripes;
+    a.tw_ifft = c->tw_ifft.p;
+    a.tw_fft = c->tw_fft.p;
+    a.mismatch = mismatch;
+    return a;
+}
+
 int encode_device(rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t stripe_stride, int nstripes,
                   int *mismatch, hipStream_t s) {
     if (!c->enc_ok) return RS_ERR_PANIC;
     if (c->logm <= kMaxRegLogM) {
-        EncodeArgs a{};
-        a.data = data;
-        a.parity = par;
-        a.k = c->k;
-        a.p = c->p;
-        a.nchunks = c->nchunks;
-        a.shard_size = S;
-        a.stripe_stride = stripe_stride;
-        a.nstripes = nstripes;
-        a.tw_ifft = c->tw_ifft.p;
-        a.tw_fft = c->tw_fft.p;
-        a.mismatch = mismatch;
+        EncodeArgs a = encode_args(c, data, par, S, stripe_stride, nstripes, mismatch);
         // bit-sliced kernel: strided rows, one row stride for data and parity
         const uint64_t span = (uint64_t)(c->k - 1) * data.stride + S;
         if (c->bs_ok && !data.table && !par.table && data.stride == par.stride && data.stride >= S &&
@@ -718,17 +782,8 @@ int encode_device(rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t str
         return RS_OK;
     }
     if (enc_lds_ok(c)) {  // m rows of accumulator + chunk LDS-resident
-        EncodeArgs a{};
-        a.data = data;
-        a.parity = par;
-        a.k = c->k;
-        a.p = c->p;
-        a.nchunks = c->nchunks;
-        a.shard_size = S;
-        a.stripe_stride = (data.table || par.table) ? 0 : stripe_stride;
-        a.nstripes = (data.table || par.table) ? 1 : nstripes;
-        a.tw_ifft = c->tw_ifft.p;
-        a.tw_fft = c->tw_fft.p;
+        const bool tab = data.table || par.table;  // a row table describes one stripe
+        EncodeArgs a = encode_args(c, data, par, S, tab ? 0 : stripe_stride, tab ? 1 : nstripes, mismatch);
         if (c->fft_sub) {
             a.tw_fft_sub = c->tw_fft_sub.p;
             a.tw_dmap = c->tw_dmap.p;
@@ -737,7 +792,6 @@ int encode_device(rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t str
                 a.ifft_nff = c->ifft_nff.p;
             }
         }
-        a.mismatch = mismatch;
         HIP_TRY(launch_encode_lds(c->bits, c->logm, mismatch != nullptr, a, s));
         return RS_OK;
     }
@@ -754,19 +808,11 @@ int encode_device(rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t str
 // errLocs for an erasure pattern (cached: analog of leopard8.go:508-555, but
 // keyed by the full pattern so a hit is always exact).
 const std::vector<uint32_t> *error_locs_cached(rs_codec *c, const std::vector<uint8_t> &erased) {
-    for (auto it = c->el_cache.begin(); it != c->el_cache.end(); ++it) {
-        if (it->first == erased) {
-            c->el_cache.splice(c->el_cache.begin(), c->el_cache, it);
-            return &c->el_cache.front().second;
-        }
-    }
+    if (const std::vector<uint32_t> *hit = c->el_cache.find(erased)) return hit;
     std::vector<uint32_t> el;
     if (!error_locators(*c->F, c->k, c->p, erased.data(), el)) return nullptr;
-    c->el_cache.emplace_front(erased, std::move(el));
-    if (c->el_cache.size() > 64) c->el_cache.pop_back();
-    return &c->el_cache.front().second;
+    return c->el_cache.put(erased, std::move(el));
 }
-
 
 // The reference-keyed GF(2^8) inversion cache (rs_set_reference_inversion_cache).
 // leopard8.go:481-506 builds the error bitfield: parity erasures (and the
@@ -806,63 +852,42 @@ const std::vector<uint32_t> *ref_inv_errlocs(rs_codec *c, const std::vector<uint
     return &slot;
 }
 
-int plan_reconstruct_new(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all,
-                         const std::vector<uint32_t> *el_ref, RecPlan &pl, const std::vector<uint32_t> *el_exact);
+// The locators of one reconstruct call, and whether the reference-keyed cache
+// handed them out: those of a multi-device parent (el_ext, computed once for
+// all its parts), else this codec's reference-keyed cache, else the exact
+// ones of the pattern.  Every reconstruct comes here exactly once, so
+// ref_inv_errlocs is consulted (and stores) once per call, as
+// leopard8.go:509-554 looks up and stores once.
+int resolve_locators(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all, uint64_t S,
+                     const ElExt *el_ext, ElExt &out) {
+    out = el_ext ? *el_ext : ElExt{ref_inv_errlocs(c, present, recover_all, S), true};
+    if (out.el) return RS_OK;
+    std::vector<uint8_t> erased(c->total);
+    for (int i = 0; i < c->total; i++) erased[i] = !present[i];
+    out = ElExt{error_locs_cached(c, erased), false};
+    return out.el ? RS_OK : RS_ERR_PANIC;
+}
 
 // Plan-cache key: (erasure pattern, recover_all), plus the errLocs a
 // reference-keyed cache handed out, which can differ between calls with the
 // same pattern.
-std::vector<uint8_t> plan_key(const std::vector<uint8_t> &present, bool recover_all, const std::vector<uint32_t> *el_ref) {
+std::vector<uint8_t> plan_key(const std::vector<uint8_t> &present, bool recover_all, const ElExt &loc) {
     std::vector<uint8_t> key(present);
     key.push_back(recover_all ? 1 : 0);
-    if (el_ref) {
-        const uint8_t *b = (const uint8_t *)el_ref->data();
-        key.insert(key.end(), b, b + el_ref->size() * sizeof(uint32_t));
+    if (loc.ref) {
+        const uint8_t *b = (const uint8_t *)loc.el->data();
+        key.insert(key.end(), b, b + loc.el->size() * sizeof(uint32_t));
     }
     return key;
 }
 
-// Plans are cached per (erasure pattern, recover_all): repeated repairs of
-// the same pattern skip the table construction.  `el_ref` is the call's one
-// reference-keyed cache answer (ref_inv_errlocs), looked up by the caller
-// exactly once per reconstruct, as leopard8.go:509-554 looks up and stores once.
-int plan_reconstruct_el(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all,
-                        const std::vector<uint32_t> *el_ref, RecPlan &pl, const std::vector<uint32_t> *el_exact = nullptr) {
-    std::vector<uint8_t> key = plan_key(present, recover_all, el_ref);
-    for (auto it = c->plan_cache.begin(); it != c->plan_cache.end(); ++it) {
-        if (it->first == key) {
-            c->plan_cache.splice(c->plan_cache.begin(), c->plan_cache, it);
-            pl = c->plan_cache.front().second;
-            return RS_OK;
-        }
-    }
-    int e = plan_reconstruct_new(c, present, recover_all, el_ref, pl, el_exact);
-    if (e) return e;
-    c->plan_cache.emplace_front(std::move(key), pl);
-    if (c->plan_cache.size() > 16) c->plan_cache.pop_back();
-    return RS_OK;
-}
-// el_ext: locators handed in by a multi-device parent (computed once for all
-// its parts) instead of this codec's own caches.
-int plan_reconstruct(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all, uint64_t S, RecPlan &pl,
-                     const ElExt *el_ext = nullptr) {
-    if (el_ext)
-        return plan_reconstruct_el(c, present, recover_all, el_ext->ref ? el_ext->el : nullptr, pl,
-                                   el_ext->ref ? nullptr : el_ext->el);
-    return plan_reconstruct_el(c, present, recover_all, ref_inv_errlocs(c, present, recover_all, S), pl);
-}
-
+// The plan of one erasure pattern from its locators `el` (leopard16.go:432-568).
 int plan_reconstruct_new(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all,
-                         const std::vector<uint32_t> *el_ref, RecPlan &pl, const std::vector<uint32_t> *el_exact) {
+                         const std::vector<uint32_t> &el, RecPlan &pl) {
     int e = build_decode_plan(c);
     if (e) return e;
     if (!c->dec_ok) return RS_ERR_PANIC;
     const int k = c->k, p = c->p, m = c->m, n = c->n, total = c->total;
-    std::vector<uint8_t> erased(total);
-    for (int i = 0; i < total; i++) erased[i] = !present[i];
-    const std::vector<uint32_t> *elp = el_ref ? el_ref : el_exact ? el_exact : error_locs_cached(c, erased);
-    if (!elp) return RS_ERR_PANIC;
-    const std::vector<uint32_t> &el = *elp;
     // work rows: [recovery m][original k][zero to n] (leopard16.go:547)
     pl.src_shard.assign(n, -1);
     for (int i = 0; i < p; i++)
@@ -898,26 +923,40 @@ int plan_reconstruct_new(rs_codec *c, const std::vector<uint8_t> &present, bool 
     return RS_OK;
 }
 
+// Plans are cached per (erasure pattern, recover_all): repeated repairs of
+// the same pattern skip the table construction.
+int plan_reconstruct_el(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all, const ElExt &loc,
+                        RecPlan &pl) {
+    std::vector<uint8_t> key = plan_key(present, recover_all, loc);
+    if (const RecPlan *hit = c->plan_cache.find(key)) {
+        pl = *hit;
+        return RS_OK;
+    }
+    int e = plan_reconstruct_new(c, present, recover_all, *loc.el, pl);
+    if (e) return e;
+    c->plan_cache.put(std::move(key), pl);
+    return RS_OK;
+}
+int plan_reconstruct(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all, uint64_t S, RecPlan &pl,
+                     const ElExt *el_ext = nullptr) {
+    ElExt loc;
+    if (int e = resolve_locators(c, present, recover_all, S, el_ext, loc)) return e;
+    return plan_reconstruct_el(c, present, recover_all, loc, pl);
+}
+
 // Upload a plan for `nsets` row-pointer sets (set b: shard i at d[b][i]) as
 // one packed blob: row pointers, scale tables, rebuilt-row positions.  The
 // pinned staging buffer is reused by the next call; every caller synchronizes
 // its stream before returning (calls are serialized by the codec mutex).
 int upload_reconstruct(rs_codec *c, const RecPlan &pl, const std::vector<uint8_t *const *> &d, hipStream_t s) {
     const int n = c->n, nd = (int)pl.dst_shard.size(), ns = (int)d.size(), ndd = std::max(nd, 1);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t s_src = (size_t)ns * n * sizeof(void *), s_dst = (size_t)ns * ndd * sizeof(void *);
     const size_t s_in = pl.tw_in.size() * 4, s_out = pl.tw_out.size() * 4, s_pos = std::max<size_t>(pl.pos.size(), 1) * 4;
-    const size_t o_dst = al(s_src), o_in = o_dst + al(s_dst), o_out = o_in + al(s_in), o_pos = o_out + al(s_out);
-    const size_t total = o_pos + al(s_pos);
+    const size_t o_dst = align256(s_src), o_in = o_dst + align256(s_dst), o_out = o_in + align256(s_in);
+    const size_t o_pos = o_out + align256(s_out), total = o_pos + align256(s_pos);
     if (int e = scratch_ensure(c, c->rc_blob, total)) return e;
-    if (c->rc_host_n < total) {
-        if (c->rc_host) HIP_TRY(hipHostFree(c->rc_host));
-        c->rc_host = nullptr;
-        c->rc_host_n = 0;
-        HIP_TRY(hipHostMalloc((void **)&c->rc_host, total, hipHostMallocDefault));
-        c->rc_host_n = total;
-    }
-    uint8_t *h = c->rc_host;
+    HIP_TRY(c->rc_host.ensure(total));
+    uint8_t *h = c->rc_host.p;
     const uint8_t **src = (const uint8_t **)h;
     uint8_t **dst = (uint8_t **)(h + o_dst);
     for (int b = 0; b < ns; b++) {
@@ -937,29 +976,11 @@ int upload_reconstruct(rs_codec *c, const RecPlan &pl, const std::vector<uint8_t
     return RS_OK;
 }
 
-// Device work of one reconstruct over row-pointer set `set` of the uploaded plan.
+// Device work of one multi-pass reconstruct over row-pointer set `set` of the
+// uploaded plan.  Only codecs without an LDS-resident reconstruct come here
+// (both callers run when !rec_lds_ok, which holds for no n <= 256).
 int launch_reconstruct(rs_codec *c, const RecPlan &pl, int set, uint64_t S, hipStream_t s) {
     const int n = c->n, nd = (int)pl.dst_shard.size();
-    if (c->logn <= kMaxLdsLogN) {  // whole transform LDS-resident: one HBM read/write per row
-        if (!nd) return RS_OK;
-        RecArgs ra{};
-        ra.src = c->rc_src + (size_t)set * n;
-        ra.dst = c->rc_dst + (size_t)set * nd;
-        ra.pos = c->rc_pos;
-        ra.tw_in = c->rc_tw_in;
-        ra.tw_out = c->rc_tw_out;
-        ra.tw_ifft = c->dtw_ifft.p;
-        ra.tw_fft = c->dtw_fft.p;
-        ra.S = S;
-        ra.mtrunc = c->m + c->k;
-        ra.m = c->m;
-        ra.nd = nd;
-        ra.prune = prune_enabled() ? 1 : 0;
-    ra.lab = g_path_dec_lab.load(std::memory_order_relaxed);
-        for (int p : pl.pos) ra.need[p >> 5] |= 1u << (p & 31);
-        HIP_TRY(launch_rec_lds(c->bits, c->logn, c->dec_sub, ra, s));
-        return RS_OK;
-    }
     if (int e = scratch_ensure(c, c->work, (size_t)n * S)) return e;
     uint8_t *w = c->work.p;
     HIP_TRY(launch_scale_in(c->bits, w, S, c->rc_src + (size_t)set * n, c->rc_tw_in, n, s));
@@ -972,37 +993,25 @@ int launch_reconstruct(rs_codec *c, const RecPlan &pl, int set, uint64_t S, hipS
     return RS_OK;
 }
 
-void set_big_sub(const rs_codec *c, RecArgs &ra) {
-    if (!c->dec_big_sub) return;
-    ra.tw_ifft_sub = c->dtw_ifft_sub.p;
-    ra.tw_fft_sub = c->dtw_fft_sub.p;
-    ra.tw_dmap = c->dec_dmap.p;
-}
-
 // Device-resident plan for (present, recover_all), built and uploaded on first use.
 int dev_plan(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all, uint64_t S, DevPlan **out,
              const ElExt *el_ext = nullptr) {
-    const std::vector<uint32_t> *el_ref =
-        el_ext ? (el_ext->ref ? el_ext->el : nullptr) : ref_inv_errlocs(c, present, recover_all, S);
-    const std::vector<uint32_t> *el_exact = el_ext && !el_ext->ref ? el_ext->el : nullptr;
-    std::vector<uint8_t> key = plan_key(present, recover_all, el_ref);
-    for (auto it = c->dplan_cache.begin(); it != c->dplan_cache.end(); ++it) {
-        if (it->first == key) {
-            c->dplan_cache.splice(c->dplan_cache.begin(), c->dplan_cache, it);
-            *out = c->dplan_cache.front().second.get();
-            return RS_OK;
-        }
+    ElExt loc;
+    if (int e = resolve_locators(c, present, recover_all, S, el_ext, loc)) return e;
+    std::vector<uint8_t> key = plan_key(present, recover_all, loc);
+    if (auto *hit = c->dplan_cache.find(key)) {
+        *out = hit->get();
+        return RS_OK;
     }
     auto dp = std::make_unique<DevPlan>();
-    if (int e = plan_reconstruct_el(c, present, recover_all, el_ref, dp->pl, el_exact)) return e;
+    if (int e = plan_reconstruct_el(c, present, recover_all, loc, dp->pl)) return e;
     const RecPlan &pl = dp->pl;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t s_in = pl.tw_in.size() * 4, s_out = pl.tw_out.size() * 4, s_pos = std::max<size_t>(pl.pos.size(), 1) * 4;
     const size_t s_si = pl.src_shard.size() * 4, s_di = std::max<size_t>(pl.dst_shard.size(), 1) * 4;
     const size_t s_nw = (size_t)std::max(c->n / 32, 1) * 4, s_rev = (size_t)c->n * 4;
-    const size_t o_out = al(s_in), o_pos = o_out + al(s_out), o_si = o_pos + al(s_pos), o_di = o_si + al(s_si);
-    const size_t o_nw = o_di + al(s_di), o_rev = o_nw + al(s_nw);
-    const size_t total = o_rev + al(s_rev);
+    const size_t o_out = align256(s_in), o_pos = o_out + align256(s_out), o_si = o_pos + align256(s_pos);
+    const size_t o_di = o_si + align256(s_si), o_nw = o_di + align256(s_di), o_rev = o_nw + align256(s_nw);
+    const size_t total = o_rev + align256(s_rev);
     std::vector<uint8_t> h(total, 0);
     {
         uint32_t *nw = (uint32_t *)(h.data() + o_nw);
@@ -1018,8 +1027,7 @@ int dev_plan(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all,
     if (!pl.pos.empty()) std::memcpy(h.data() + o_pos, pl.pos.data(), pl.pos.size() * 4);
     std::memcpy(h.data() + o_si, pl.src_shard.data(), s_si);
     if (!pl.dst_shard.empty()) std::memcpy(h.data() + o_di, pl.dst_shard.data(), pl.dst_shard.size() * 4);
-    HIP_TRY(dp->blob.ensure(total));
-    HIP_TRY(hipMemcpy(dp->blob.p, h.data(), total, hipMemcpyHostToDevice));
+    if (int e = upload(dp->blob, h)) return e;
     dp->tw_in = (const uint32_t *)dp->blob.p;
     dp->tw_out = (const uint32_t *)(dp->blob.p + o_out);
     dp->pos = (const int *)(dp->blob.p + o_pos);
@@ -1029,10 +1037,35 @@ int dev_plan(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all,
     dp->rev = (const int *)(dp->blob.p + o_rev);
     for (int p : pl.pos)
         if (p < 256) dp->need[p >> 5] |= 1u << (p & 31);
-    c->dplan_cache.emplace_front(std::move(key), std::move(dp));
-    if (c->dplan_cache.size() > 16) c->dplan_cache.pop_back();  // waits for the plan's last launch
-    *out = c->dplan_cache.front().second.get();
+    *out = c->dplan_cache.put(std::move(key), std::move(dp))->get();  // an eviction waits for that plan's last launch
     return RS_OK;
+}
+
+// The arguments every LDS-resident reconstruct launch over a device plan
+// shares; the caller adds its addressing (a strided base with the plan's
+// indices, or a ring slot of row pointers).
+RecArgs rec_args(const rs_codec *c, const DevPlan *dp, uint64_t S) {
+    RecArgs ra{};
+    ra.pos = dp->pos;
+    ra.tw_in = dp->tw_in;
+    ra.tw_out = dp->tw_out;
+    ra.tw_ifft = c->dtw_ifft.p;
+    ra.tw_fft = c->dtw_fft.p;
+    ra.S = S;
+    ra.mtrunc = c->m + c->k;
+    ra.m = c->m;
+    ra.nd = (int)dp->pl.dst_shard.size();
+    ra.prune = prune_enabled() ? 1 : 0;
+    ra.lab = g_path_dec_lab.load(std::memory_order_relaxed);
+    std::memcpy(ra.need, dp->need, sizeof(ra.need));
+    ra.need_w = dp->need_w;
+    ra.rev = dp->rev;
+    if (c->dec_big_sub) {
+        ra.tw_ifft_sub = c->dtw_ifft_sub.p;
+        ra.tw_fft_sub = c->dtw_fft_sub.p;
+        ra.tw_dmap = c->dec_dmap.p;
+    }
+    return ra;
 }
 
 // One launch of the LDS-resident reconstruct (rec_lds_ok) with a cached device plan over
@@ -1041,22 +1074,7 @@ int launch_rec_plan(rs_codec *c, DevPlan *dpl, uint8_t *base, uint64_t stride, u
                     uint64_t S, hipStream_t s) {
     const int nd = (int)dpl->pl.dst_shard.size();
     if (!nd) return RS_OK;
-    RecArgs ra{};
-    ra.pos = dpl->pos;
-    ra.tw_in = dpl->tw_in;
-    ra.tw_out = dpl->tw_out;
-    ra.tw_ifft = c->dtw_ifft.p;
-    ra.tw_fft = c->dtw_fft.p;
-    ra.S = S;
-    ra.mtrunc = c->m + c->k;
-    ra.m = c->m;
-    ra.nd = nd;
-    ra.prune = prune_enabled() ? 1 : 0;
-    ra.lab = g_path_dec_lab.load(std::memory_order_relaxed);
-    std::memcpy(ra.need, dpl->need, sizeof(ra.need));
-    ra.need_w = dpl->need_w;
-    ra.rev = dpl->rev;
-    set_big_sub(c, ra);
+    RecArgs ra = rec_args(c, dpl, S);
     ra.base = base;
     ra.stride = stride;
     ra.stripe_stride = stripe_stride;
@@ -1073,15 +1091,13 @@ int launch_rec_plan(rs_codec *c, DevPlan *dpl, uint8_t *base, uint64_t stride, u
 // of the slot's previous call are done.  The caller fills h, copies it to g on
 // its stream, launches, and records ring_ev[slot] there (ring_used[slot] = true).
 int ring_acquire(rs_codec *c, size_t want, int &slot, uint8_t *&h, uint8_t *&g) {
-    const size_t bytes = (want + 255) & ~(size_t)255;
+    const size_t bytes = align256(want);
     if (c->ring_slot < bytes) {
         for (int i = 0; i < rs_codec::kRing; i++)
             if (c->ring_used[i]) HIP_TRY(hipEventSynchronize(c->ring_ev[i]));
-        if (c->ring_host) HIP_TRY(hipHostFree(c->ring_host));
-        c->ring_host = nullptr;
         c->ring_slot = 0;
+        HIP_TRY(c->ring_host.ensure(bytes * rs_codec::kRing));
         HIP_TRY(c->ring_dev.ensure(bytes * rs_codec::kRing));
-        HIP_TRY(hipHostMalloc((void **)&c->ring_host, bytes * rs_codec::kRing, hipHostMallocDefault));
         c->ring_slot = bytes;
     }
     const int i = c->ring_next;
@@ -1089,7 +1105,7 @@ int ring_acquire(rs_codec *c, size_t want, int &slot, uint8_t *&h, uint8_t *&g) 
     if (!c->ring_ev[i]) HIP_TRY(hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming));
     if (c->ring_used[i]) HIP_TRY(hipEventSynchronize(c->ring_ev[i]));  // its copy and kernel are done
     slot = i;
-    h = c->ring_host + (size_t)i * c->ring_slot;
+    h = c->ring_host.p + (size_t)i * c->ring_slot;
     g = c->ring_dev.p + (size_t)i * c->ring_slot;
     return RS_OK;
 }
@@ -1106,22 +1122,7 @@ int reconstruct_device_lds(rs_codec *c, uint8_t *const *d, const std::vector<uin
     const RecPlan &pl = dp->pl;
     const int n = c->n, nd = (int)pl.dst_shard.size();
     if (!nd) return RS_OK;
-    RecArgs ra{};
-    ra.pos = dp->pos;
-    ra.tw_in = dp->tw_in;
-    ra.tw_out = dp->tw_out;
-    ra.tw_ifft = c->dtw_ifft.p;
-    ra.tw_fft = c->dtw_fft.p;
-    ra.S = S;
-    ra.mtrunc = c->m + c->k;
-    ra.m = c->m;
-    ra.nd = nd;
-    ra.prune = prune_enabled() ? 1 : 0;
-    ra.lab = g_path_dec_lab.load(std::memory_order_relaxed);
-    std::memcpy(ra.need, dp->need, sizeof(ra.need));
-    ra.need_w = dp->need_w;
-    ra.rev = dp->rev;
-    set_big_sub(c, ra);
+    RecArgs ra = rec_args(c, dp, S);
     {
         // strided: every shard the launch touches at d[0] + i * stride
         int i0 = -1, i1 = -1;
@@ -1167,27 +1168,21 @@ int reconstruct_device_lds(rs_codec *c, uint8_t *const *d, const std::vector<uin
 // ---- Incremental update (rs_update_dev / rs_encode_idx_dev / rs_update_dev_batch)
 // Cached device tables for the ordered index list `idx`, built and uploaded on first use.
 int upd_plan(rs_codec *c, const std::vector<int> &idx, UpdPlan **out) {
-    for (auto it = c->uplan_cache.begin(); it != c->uplan_cache.end(); ++it) {
-        if (it->first == idx) {
-            c->uplan_cache.splice(c->uplan_cache.begin(), c->uplan_cache, it);
-            *out = c->uplan_cache.front().second.get();
-            return RS_OK;
-        }
+    if (auto *hit = c->uplan_cache.find(idx)) {
+        *out = hit->get();
+        return RS_OK;
     }
     const int t = (int)idx.size();
     const size_t s_tw = (size_t)c->p * t * c->twd * 4;
-    const size_t o_idx = (s_tw + 255) & ~(size_t)255, total = o_idx + (((size_t)t * 4 + 255) & ~(size_t)255);
+    const size_t o_idx = align256(s_tw), total = o_idx + align256((size_t)t * 4);
     std::vector<uint8_t> h(total, 0);
     make_update_tables(*c->F, c->k, c->p, idx.data(), t, c->enc_ifft_logs, c->enc_fft_logs, (uint32_t *)h.data());
     std::memcpy(h.data() + o_idx, idx.data(), (size_t)t * 4);
     auto up = std::make_unique<UpdPlan>();
-    HIP_TRY(up->blob.ensure(total));
-    HIP_TRY(hipMemcpy(up->blob.p, h.data(), total, hipMemcpyHostToDevice));
+    if (int e = upload(up->blob, h)) return e;
     up->tw = (const uint32_t *)up->blob.p;
     up->idx = (const int *)(up->blob.p + o_idx);
-    c->uplan_cache.emplace_front(idx, std::move(up));
-    if (c->uplan_cache.size() > 16) c->uplan_cache.pop_back();  // waits for the plan's last launch
-    *out = c->uplan_cache.front().second.get();
+    *out = c->uplan_cache.put(idx, std::move(up))->get();  // an eviction waits for that plan's last launch
     return RS_OK;
 }
 
@@ -1498,7 +1493,7 @@ int host_pipeline(rs_codec *c, uint8_t *const *shards, uint64_t S, HostOp op, co
     }
     const uint64_t seg = host_segment(c, S, in_rows.size());
     const uint64_t slab = (uint64_t)total * seg;
-    const uint64_t slab_al = (slab + 255) / 256 * 256;
+    const uint64_t slab_al = align256(slab);
     if (c->stage.n / kHostBufs < slab_al) {  // a reallocation waits for queued segments
         HIP_TRY(hipStreamSynchronize(c->s_in));
         HIP_TRY(hipStreamSynchronize(sc));
@@ -1532,16 +1527,9 @@ int host_pipeline(rs_codec *c, uint8_t *const *shards, uint64_t S, HostOp op, co
     const bool zc_out = (zm & 2) && zc_rows(shards, out_rows, S, zout);
     std::vector<std::vector<uint8_t *>> btab(kHostBufs, std::vector<uint8_t *>(total));
     if (use_bounce) {
-        const size_t need = (size_t)kHostBufs * slab;
-        if (c->bounce_n < need) {
-            if (c->bounce) HIP_TRY(hipHostFree(c->bounce));
-            c->bounce = nullptr;
-            c->bounce_n = 0;
-            HIP_TRY(hipHostMalloc((void **)&c->bounce, need, hipHostMallocDefault));
-            c->bounce_n = need;
-        }
+        HIP_TRY(c->bounce.ensure((size_t)kHostBufs * slab));
         for (int b = 0; b < kHostBufs; b++)
-            for (int i = 0; i < total; i++) btab[b][i] = c->bounce + b * slab + (uint64_t)i * seg;
+            for (int i = 0; i < total; i++) btab[b][i] = c->bounce.p + b * slab + (uint64_t)i * seg;
     }
     const uint64_t seq0 = c->pipe_seq;
     auto drain = [&](uint64_t j) -> int {  // host copy of segment j's outputs out of its bounce slab
@@ -1653,15 +1641,118 @@ int host_pipeline(rs_codec *c, uint8_t *const *shards, uint64_t S, HostOp op, co
     return RS_OK;
 }
 
+// ---------------------------------------------------------------- workers of the entry points
+// Each public function keeps its own argument checks, in its own order, and
+// hands the validated call to the worker of its family.
+
+// A host-resident call under the codec mutex: on the parts of a multi-device
+// codec, else through this codec's own pipeline.
+int host_run(rs_codec *c, HostOp op, uint8_t *const *shards, uint64_t S, const std::vector<uint8_t> &present,
+             bool recover_all, int *ok, uint64_t *ticket, const ElExt *el = nullptr) {
+    if (c->multi) return multi_host(c->multi, c, op, shards, S, present, recover_all, ok, ticket);
+    DeviceGuard g(c->device);
+    if (int ie = ensure_device(c)) return ie;
+    return host_pipeline(c, shards, S, op, present, recover_all, ok, ticket, el);
+}
+
+// rs_encode / rs_encode_async / rs_verify / rs_verify_async after their NULL
+// checks (Encode leopard16.go:116-135, Verify :361-387).
+int host_call(rs_codec *c, HostOp op, uint8_t *const *shards, const size_t *lens, int nshards, int *ok,
+              uint64_t *ticket) {
+    if (nshards != c->total) return RS_ERR_TOO_FEW_SHARDS;
+    if (int e = check_shards(lens, nshards, false)) return e;
+    const uint64_t S = shard_size_of(lens, nshards);
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    for (int i = 0; i < nshards; i++)
+        if (!shards[i]) return RS_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return host_run(c, op, shards, S, {}, true, ok, ticket);
+}
+
+// rs_encode_dev / rs_verify_dev (rows d[0..total)) and rs_encode_dev_batch /
+// rs_verify_dev_batch (d == nullptr: the slab at `base`) after their argument
+// checks.  ok != nullptr: verify, which always takes the scratch (the mismatch
+// word) and always completes before it returns (it reads the pinned word); an
+// encode takes the scratch only when its launch uses it, and completes on
+// return only without a caller stream.
+int encode_dev_call(rs_codec *c, uint8_t *const *d, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride,
+                    int nstripes, uint64_t S, int *ok, void *stream) {
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    RowSet data, par;
+    if (d) {
+        if (int e = make_rowsets(c, d, s, data, par)) return e;
+    } else {
+        data = RowSet{nullptr, base, row_stride};
+        par = RowSet{nullptr, base + (size_t)c->k * row_stride, row_stride};
+    }
+    const bool scr = ok || encode_uses_scratch(c, data, par);
+    if (scr)
+        if (int e = scratch_acquire(c, s)) return e;
+    if (ok) HIP_TRY(hipMemsetAsync(c->dflag, 0, sizeof(int), s));
+    if (int e = encode_device(c, data, par, S, stripe_stride, nstripes, ok ? c->dflag : nullptr, s)) return e;
+    if (scr)
+        if (int e = scratch_release(c, s)) return e;
+    if (!ok) return dc.finish(RS_OK);
+    HIP_TRY(hipMemcpyAsync(c->hflag, c->dflag, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *ok = *(volatile int *)c->hflag == 0;
+    return RS_OK;
+}
+
+// The rules rs_reconstruct_dev, rs_reconstruct_dev_batch and the host
+// reconstructs share (leopard16.go:390-430), on the shards marked present.
+// done: `return` is the call's result (an error, or RS_OK with nothing to rebuild).
+int reconstruct_checks(const rs_codec *c, const std::vector<uint8_t> &present, uint64_t S, bool recover_all, bool &done) {
+    int np = 0, dp = 0;
+    for (int i = 0; i < c->total; i++)
+        if (present[i]) {
+            np++;
+            if (i < c->k) dp++;
+        }
+    done = true;
+    if (np == 0 || S == 0) return RS_ERR_SHARD_NO_DATA;
+    if (np == c->total || (!recover_all && dp == c->k)) return RS_OK;
+    if (np < c->k) return RS_ERR_TOO_FEW_SHARDS;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    done = false;
+    return RS_OK;
+}
+
+
+// rs_reconstruct / rs_reconstruct_async.  Nothing to rebuild: RS_OK with no
+// ticket issued (*ticket stays 0, which rs_ticket_wait / query report as done).
+int reconstruct_host(rs_codec *c, uint8_t *const *shards, size_t *lens, int nshards, int recover_all, uint64_t *ticket) {
+    if (!c || !shards || !lens) return RS_ERR_INVALID_ARG;
+    if (nshards != c->total) return RS_ERR_TOO_FEW_SHARDS;
+    int e = check_shards(lens, nshards, true);
+    if (e) return e;
+    std::vector<uint8_t> pr(c->total);
+    for (int i = 0; i < c->total; i++) pr[i] = lens[i] != 0;
+    const uint64_t S = shard_size_of(lens, nshards);  // > 0, and a shard is present (check_shards)
+    bool done;
+    e = reconstruct_checks(c, pr, S, recover_all != 0, done);
+    if (done) return e;
+    const int end = recover_all ? c->total : c->k;
+    for (int i = 0; i < c->total; i++)
+        if ((pr[i] || i < end) && !shards[i]) return RS_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    e = host_run(c, HostOp::Reconstruct, shards, S, pr, recover_all != 0, nullptr, ticket);
+    if (e) return e;
+    for (int i = 0; i < end; i++)
+        if (!pr[i]) lens[i] = S;
+    return RS_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- multi-device parts (multi.hpp)
 int rs::part_host_call(rs_codec *c, HostOp op, uint8_t *const *shards, uint64_t S, const std::vector<uint8_t> &present,
                        bool recover_all, int *ok, uint64_t *ticket, const ElExt *el) {
     std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    return host_pipeline(c, shards, S, op, present, recover_all, ok, ticket, el);
+    return host_run(c, op, shards, S, present, recover_all, ok, ticket, el);  // a part has no parts of its own
 }
 
 // The locators a single-device codec would use for this call (its reference-
@@ -1670,16 +1761,7 @@ int rs::part_host_call(rs_codec *c, HostOp op, uint8_t *const *shards, uint64_t 
 // valid while the parent's mutex is held, i.e. for the whole multi call.
 int rs::parent_error_locators(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all, uint64_t S,
                               ElExt &out) {
-    out = ElExt{};
-    if (const std::vector<uint32_t> *r = ref_inv_errlocs(c, present, recover_all, S)) {
-        out.el = r;
-        out.ref = true;
-        return RS_OK;
-    }
-    std::vector<uint8_t> erased(c->total);
-    for (int i = 0; i < c->total; i++) erased[i] = !present[i];
-    out.el = error_locs_cached(c, erased);
-    return out.el ? RS_OK : RS_ERR_PANIC;
+    return resolve_locators(c, present, recover_all, S, nullptr, out);
 }
 
 // Host simulation of the split schedules against the plain op lists on random
@@ -1929,20 +2011,7 @@ int rs_encode_dev(rs_codec *c, uint8_t *const *d, size_t S, void *stream) {
         if (!d[i]) return RS_ERR_INVALID_ARG;
     if (S == 0) return RS_ERR_SHARD_NO_DATA;
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    hipStream_t s = pick_stream(c, stream);
-    RowSet data, par;
-    int e = make_rowsets(c, d, s, data, par);
-    if (e) return e;
-    const bool scr = encode_uses_scratch(c, data, par);
-    if (scr && (e = scratch_acquire(c, s))) return e;
-    e = encode_device(c, data, par, S, 0, 1, nullptr, s);
-    if (e) return e;
-    if (scr && (e = scratch_release(c, s))) return e;
-    if (!stream) HIP_TRY(hipStreamSynchronize(s));
-    return RS_OK;
+    return encode_dev_call(c, d, nullptr, 0, 0, 1, S, nullptr, stream);
 }
 
 int rs_encode_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, int nstripes, size_t S,
@@ -1952,19 +2021,7 @@ int rs_encode_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t st
     if (S == 0) return RS_ERR_SHARD_NO_DATA;
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
     if (row_stride < S) return RS_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    hipStream_t s = pick_stream(c, stream);
-    RowSet data{nullptr, base, row_stride}, par{nullptr, base + (size_t)c->k * row_stride, row_stride};
-    const bool scr = encode_uses_scratch(c, data, par);
-    int e = scr ? scratch_acquire(c, s) : RS_OK;
-    if (e) return e;
-    e = encode_device(c, data, par, S, stripe_stride, nstripes, nullptr, s);
-    if (e) return e;
-    if (scr && (e = scratch_release(c, s))) return e;
-    if (!stream) HIP_TRY(hipStreamSynchronize(s));
-    return RS_OK;
+    return encode_dev_call(c, nullptr, base, row_stride, stripe_stride, nstripes, S, nullptr, stream);
 }
 
 int rs_verify_dev(rs_codec *c, uint8_t *const *d, size_t S, int *ok, void *stream) {
@@ -1975,24 +2032,7 @@ int rs_verify_dev(rs_codec *c, uint8_t *const *d, size_t S, int *ok, void *strea
         if (!d[i]) return RS_ERR_INVALID_ARG;
     if (S == 0) return RS_ERR_SHARD_NO_DATA;
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    hipStream_t s = pick_stream(c, stream);
-    RowSet data, par;
-    int e = make_rowsets(c, d, s, data, par);
-    if (e) return e;
-    e = scratch_acquire(c, s);
-    if (e) return e;
-    HIP_TRY(hipMemsetAsync(c->dflag, 0, sizeof(int), s));
-    e = encode_device(c, data, par, S, 0, 1, c->dflag, s);
-    if (e) return e;
-    e = scratch_release(c, s);
-    if (e) return e;
-    HIP_TRY(hipMemcpyAsync(c->hflag, c->dflag, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *ok = *(volatile int *)c->hflag == 0;
-    return RS_OK;
+    return encode_dev_call(c, d, nullptr, 0, 0, 1, S, ok, stream);
 }
 
 int rs_verify_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, int nstripes, size_t S,
@@ -2003,22 +2043,7 @@ int rs_verify_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t st
     if (S == 0) return RS_ERR_SHARD_NO_DATA;
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
     if (row_stride < S) return RS_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    hipStream_t s = pick_stream(c, stream);
-    RowSet data{nullptr, base, row_stride}, par{nullptr, base + (size_t)c->k * row_stride, row_stride};
-    int e = scratch_acquire(c, s);
-    if (e) return e;
-    HIP_TRY(hipMemsetAsync(c->dflag, 0, sizeof(int), s));
-    e = encode_device(c, data, par, S, stripe_stride, nstripes, c->dflag, s);
-    if (e) return e;
-    e = scratch_release(c, s);
-    if (e) return e;
-    HIP_TRY(hipMemcpyAsync(c->hflag, c->dflag, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *ok = *(volatile int *)c->hflag == 0;
-    return RS_OK;
+    return encode_dev_call(c, nullptr, base, row_stride, stripe_stride, nstripes, S, ok, stream);
 }
 
 int rs_reconstruct_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
@@ -2026,29 +2051,19 @@ int rs_reconstruct_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size
     if (!c || !base || !present || nstripes == 0 || nstripes > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
     if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
     std::vector<uint8_t> pr(present, present + c->total);
-    int np = 0, dp = 0;
-    for (int i = 0; i < c->total; i++)
-        if (pr[i]) {
-            np++;
-            if (i < c->k) dp++;
-        }
-    if (np == 0 || S == 0) return RS_ERR_SHARD_NO_DATA;
-    if (np == c->total || (!recover_all && dp == c->k)) return RS_OK;
-    if (np < c->k) return RS_ERR_TOO_FEW_SHARDS;
-    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    bool done;
+    const int ce = reconstruct_checks(c, pr, S, recover_all != 0, done);
+    if (done) return ce;
     if (row_stride < S || (nstripes > 1 && stripe_stride < (size_t)c->total * row_stride)) return RS_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    const hipStream_t s = pick_stream(c, stream);
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
     if (int e = build_decode_plan(c)) return e;
     if (c->dec_ok && rec_lds_ok(c)) {
         // one launch: grid.y = stripe, the pattern's tables shared (dev_plan cache)
         DevPlan *dpl = nullptr;
         if (int e = dev_plan(c, pr, recover_all != 0, S, &dpl)) return e;
-        if (int e = launch_rec_plan(c, dpl, base, row_stride, stripe_stride, (int)nstripes, S, s)) return e;
-        if (!stream) HIP_TRY(hipStreamSynchronize(s));  // no caller stream: complete on return
-        return RS_OK;
+        return dc.finish(launch_rec_plan(c, dpl, base, row_stride, stripe_stride, (int)nstripes, S, s));
     }
     // multi-pass codecs (n > 256): stripe by stripe
     std::vector<uint8_t *> rows(c->total);
@@ -2064,64 +2079,28 @@ int rs_reconstruct_dev(rs_codec *c, uint8_t *const *d, const uint8_t *present, s
     if (!c || !d || !present) return RS_ERR_INVALID_ARG;
     if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
     std::vector<uint8_t> pr(present, present + c->total);
-    int np = 0, dp = 0;
-    for (int i = 0; i < c->total; i++)
-        if (pr[i]) {
-            np++;
-            if (i < c->k) dp++;
-        }
-    if (np == 0 || S == 0) return RS_ERR_SHARD_NO_DATA;
-    if (np == c->total || (!recover_all && dp == c->k)) return RS_OK;
-    if (np < c->k) return RS_ERR_TOO_FEW_SHARDS;
-    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    bool done;
+    const int ce = reconstruct_checks(c, pr, S, recover_all != 0, done);
+    if (done) return ce;
     const int end = recover_all ? c->total : c->k;
     for (int i = 0; i < c->total; i++)
         if ((pr[i] || i < end) && !d[i]) return RS_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    const hipStream_t s = pick_stream(c, stream);
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
     if (int e = build_decode_plan(c)) return e;
-    if (c->dec_ok && rec_lds_ok(c)) {
-        if (int e = reconstruct_device_lds(c, d, pr, S, recover_all != 0, s)) return e;
-        if (!stream) HIP_TRY(hipStreamSynchronize(s));  // no caller stream: complete on return
-        return RS_OK;
-    }
+    if (c->dec_ok && rec_lds_ok(c)) return dc.finish(reconstruct_device_lds(c, d, pr, S, recover_all != 0, s));
     return reconstruct_device(c, d, pr, S, recover_all != 0, s);
 }
 
 int rs_encode(rs_codec *c, uint8_t *const *shards, const size_t *lens, int nshards) {
     if (!c || !shards || !lens) return RS_ERR_INVALID_ARG;
-    if (nshards != c->total) return RS_ERR_TOO_FEW_SHARDS;
-    int e = check_shards(lens, nshards, false);
-    if (e) return e;
-    const uint64_t S = shard_size_of(lens, nshards);
-    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
-    if (!c->enc_ok) return RS_ERR_PANIC;
-    for (int i = 0; i < nshards; i++)
-        if (!shards[i]) return RS_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (c->multi) return multi_host(c->multi, c, HostOp::Encode, shards, S, {}, true, nullptr, nullptr);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    return host_pipeline(c, shards, S, HostOp::Encode, {}, true, nullptr);
+    return host_call(c, HostOp::Encode, shards, lens, nshards, nullptr, nullptr);
 }
 
 int rs_encode_async(rs_codec *c, uint8_t *const *shards, const size_t *lens, int nshards, uint64_t *ticket) {
     if (!c || !shards || !lens || !ticket) return RS_ERR_INVALID_ARG;
-    if (nshards != c->total) return RS_ERR_TOO_FEW_SHARDS;
-    int e = check_shards(lens, nshards, false);
-    if (e) return e;
-    const uint64_t S = shard_size_of(lens, nshards);
-    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
-    if (!c->enc_ok) return RS_ERR_PANIC;
-    for (int i = 0; i < nshards; i++)
-        if (!shards[i]) return RS_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (c->multi) return multi_host(c->multi, c, HostOp::Encode, shards, S, {}, true, nullptr, ticket);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    return host_pipeline(c, shards, S, HostOp::Encode, {}, true, nullptr, ticket);
+    return host_call(c, HostOp::Encode, shards, lens, nshards, nullptr, ticket);
 }
 
 int rs_encode_query(rs_codec *c, uint64_t ticket, int *done) {
@@ -2170,19 +2149,7 @@ int rs_ticket_wait(rs_codec *c, uint64_t ticket) { return rs_encode_wait(c, tick
 
 int rs_verify_async(rs_codec *c, uint8_t *const *shards, const size_t *lens, int nshards, uint64_t *ticket) {
     if (!c || !shards || !lens || !ticket) return RS_ERR_INVALID_ARG;
-    if (nshards != c->total) return RS_ERR_TOO_FEW_SHARDS;
-    int e = check_shards(lens, nshards, false);
-    if (e) return e;
-    const uint64_t S = lens[0];
-    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
-    if (!c->enc_ok) return RS_ERR_PANIC;
-    for (int i = 0; i < nshards; i++)
-        if (!shards[i]) return RS_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (c->multi) return multi_host(c->multi, c, HostOp::Verify, shards, S, {}, true, nullptr, ticket);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    return host_pipeline(c, shards, S, HostOp::Verify, {}, true, nullptr, ticket);
+    return host_call(c, HostOp::Verify, shards, lens, nshards, nullptr, ticket);
 }
 
 int rs_verify_result(rs_codec *c, uint64_t ticket, int *ok) {
@@ -2211,62 +2178,8 @@ int rs_verify_result(rs_codec *c, uint64_t ticket, int *ok) {
 int rs_verify(rs_codec *c, uint8_t *const *shards, const size_t *lens, int nshards, int *ok) {
     if (!c || !shards || !lens || !ok) return RS_ERR_INVALID_ARG;
     *ok = 0;
-    if (nshards != c->total) return RS_ERR_TOO_FEW_SHARDS;
-    int e = check_shards(lens, nshards, false);
-    if (e) return e;
-    const uint64_t S = lens[0];
-    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
-    if (!c->enc_ok) return RS_ERR_PANIC;
-    for (int i = 0; i < nshards; i++)
-        if (!shards[i]) return RS_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (c->multi) return multi_host(c->multi, c, HostOp::Verify, shards, S, {}, true, ok, nullptr);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    return host_pipeline(c, shards, S, HostOp::Verify, {}, true, ok);
+    return host_call(c, HostOp::Verify, shards, lens, nshards, ok, nullptr);
 }
-
-}  // extern "C"
-
-namespace {
-// rs_reconstruct / rs_reconstruct_async.  Nothing to rebuild: RS_OK with no
-// ticket issued (*ticket stays 0, which rs_ticket_wait / query report as done).
-int reconstruct_host(rs_codec *c, uint8_t *const *shards, size_t *lens, int nshards, int recover_all, uint64_t *ticket) {
-    if (!c || !shards || !lens) return RS_ERR_INVALID_ARG;
-    if (nshards != c->total) return RS_ERR_TOO_FEW_SHARDS;
-    int e = check_shards(lens, nshards, true);
-    if (e) return e;
-    int np = 0, dp = 0;
-    for (int i = 0; i < c->total; i++)
-        if (lens[i]) {
-            np++;
-            if (i < c->k) dp++;
-        }
-    if (np == c->total || (!recover_all && dp == c->k)) return RS_OK;
-    if (np < c->k) return RS_ERR_TOO_FEW_SHARDS;
-    const uint64_t S = shard_size_of(lens, nshards);
-    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
-    const int end = recover_all ? c->total : c->k;
-    for (int i = 0; i < c->total; i++)
-        if ((lens[i] || i < end) && !shards[i]) return RS_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    std::vector<uint8_t> pr(c->total);
-    for (int i = 0; i < c->total; i++) pr[i] = lens[i] != 0;
-    if (c->multi) {
-        e = multi_host(c->multi, c, HostOp::Reconstruct, shards, S, pr, recover_all != 0, nullptr, ticket);
-    } else {
-        DeviceGuard g(c->device);
-        if (int ie = ensure_device(c)) return ie;
-        e = host_pipeline(c, shards, S, HostOp::Reconstruct, pr, recover_all != 0, nullptr, ticket);
-    }
-    if (e) return e;
-    for (int i = 0; i < end; i++)
-        if (!pr[i]) lens[i] = S;
-    return RS_OK;
-}
-}  // namespace
-
-extern "C" {
 
 int rs_reconstruct(rs_codec *c, uint8_t *const *shards, size_t *lens, int nshards, int recover_all) {
     return reconstruct_host(c, shards, lens, nshards, recover_all, nullptr);
@@ -2304,10 +2217,9 @@ int rs_split(rs_codec *c, const uint8_t *data, size_t len, uint8_t *dst, size_t 
         }
         return RS_OK;
     }
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    hipStream_t s = pick_stream(c, stream);
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
     if (nfull) HIP_TRY(hipMemcpy2DAsync(dst, dst_stride, data, per, per, nfull, hipMemcpyDefault, s));
     if (rem) HIP_TRY(hipMemcpyAsync(dst + nfull * dst_stride, data + nfull * per, rem, hipMemcpyDefault, s));
     const size_t zrow = nfull + (rem ? 1 : 0);
@@ -2319,8 +2231,7 @@ int rs_split(rs_codec *c, const uint8_t *data, size_t len, uint8_t *dst, size_t 
         if (rem) std::memset(dst + nfull * dst_stride + rem, 0, per - rem);
         for (size_t i = zrow; i < (size_t)total; i++) std::memset(dst + i * dst_stride, 0, per);
     }
-    if (!stream) HIP_TRY(hipStreamSynchronize(s));
-    return RS_OK;
+    return dc.finish(RS_OK);
 }
 
 int rs_join(rs_codec *c, uint8_t *const *shards, const size_t *lens, int nshards, uint8_t *dst, size_t out_size,
@@ -2348,17 +2259,15 @@ int rs_join(rs_codec *c, uint8_t *const *shards, const size_t *lens, int nshards
         }
         return RS_OK;
     }
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    hipStream_t s = pick_stream(c, stream);
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
     for (int i = 0; i < use && written < out_size; i++) {
         const size_t n = std::min(lens[i], out_size - written);
         if (n) HIP_TRY(hipMemcpyAsync(dst + written, shards[i], n, hipMemcpyDefault, s));
         written += n;
     }
-    if (!stream) HIP_TRY(hipStreamSynchronize(s));
-    return RS_OK;
+    return dc.finish(RS_OK);
 }
 
 int rs_set_host_segment(rs_codec *c, size_t bytes) {
@@ -2421,13 +2330,9 @@ int rs_update_dev(rs_codec *c, uint8_t *const *d, uint8_t *const *d_new, size_t 
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
     if (idx.empty()) return RS_OK;
     if (!c->enc_ok) return RS_ERR_PANIC;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    hipStream_t s = pick_stream(c, stream);
-    if (int e = update_device_rows(c, d + c->k, idx, old.data(), nw.data(), S, s)) return e;
-    if (!stream) HIP_TRY(hipStreamSynchronize(s));
-    return RS_OK;
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    return dc.finish(update_device_rows(c, d + c->k, idx, old.data(), nw.data(), S, dc.s));
 }
 
 int rs_encode_idx_dev(rs_codec *c, const uint8_t *row, int idx, uint8_t *const *d_parity, size_t S, void *stream) {
@@ -2439,13 +2344,9 @@ int rs_encode_idx_dev(rs_codec *c, const uint8_t *row, int idx, uint8_t *const *
     if (S == 0) return RS_ERR_SHARD_NO_DATA;
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
     if (!c->enc_ok) return RS_ERR_PANIC;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    hipStream_t s = pick_stream(c, stream);
-    if (int e = update_device_rows(c, d_parity, {idx}, nullptr, &row, S, s)) return e;
-    if (!stream) HIP_TRY(hipStreamSynchronize(s));
-    return RS_OK;
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    return dc.finish(update_device_rows(c, d_parity, {idx}, nullptr, &row, S, dc.s));
 }
 
 int rs_update_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, int nstripes,
@@ -2465,15 +2366,10 @@ int rs_update_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t st
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
     if (row_stride < S || new_row_stride < S) return RS_ERR_INVALID_ARG;
     if (!c->enc_ok) return RS_ERR_PANIC;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    if (int ie = ensure_device(c)) return ie;
-    hipStream_t s = pick_stream(c, stream);
-    if (int e = update_device_batch(c, base, row_stride, stripe_stride, nstripes, std::vector<int>(idx, idx + nidx),
-                                    d_new, new_row_stride, new_stripe_stride, S, s))
-        return e;
-    if (!stream) HIP_TRY(hipStreamSynchronize(s));
-    return RS_OK;
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    return dc.finish(update_device_batch(c, base, row_stride, stripe_stride, nstripes, std::vector<int>(idx, idx + nidx),
+                                         d_new, new_row_stride, new_stripe_stride, S, dc.s));
 }
 
 int rs_debug_generator(int bits, int k, int p, int idx, uint32_t *out) {

@@ -237,6 +237,67 @@ int rs_reconstruct_dev(rs_codec *codec, uint8_t *const *d_shards, const uint8_t 
 int rs_reconstruct_dev_batch(rs_codec *codec, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
                              const uint8_t *present, size_t shard_size, int recover_all, void *stream);
 
+/* ---------------- Selective reconstruct (beyond the reference) ----------------
+ * The reference's ReconstructSome reads only len(required) (leopard16.go:343-348)
+ * and rebuilds all missing shards or all missing data shards.  The three calls
+ * below rebuild exactly the rows with !present[i] && required[i] (data or
+ * parity, any mix; required has k+p flags like present) and write no other
+ * byte: the degraded read of a storage system ("shard 17 is gone and I need
+ * only that one").  Each rebuilt row is, bit for bit, what the reference's
+ * Reconstruct (leopard16.go:390-570, leopard8.go:439-695) puts into that row
+ * for the same `present`, for every input, stripes whose present rows are not
+ * consistent with each other included: the map uses every row marked present,
+ * with the locators of that pattern.  A caller who wants the minimum read
+ * marks only k rows present.  A required flag on a present row is ignored;
+ * nothing to rebuild returns RS_OK with nothing launched.  Errors: the rules
+ * and order of rs_reconstruct_dev / rs_reconstruct_dev_batch / rs_reconstruct
+ * (NULL arguments, a multi-device codec for the device forms, no row present or
+ * shard_size == 0, nothing to do, too few present, shard_size % 64, row
+ * pointers and strides), all decided before any device call.  These calls
+ * always use the exact locators of the pattern: they neither read nor store the
+ * reference-keyed GF(2^8) inversion cache (rs_set_reference_inversion_cache),
+ * so existing call sequences replay the reference as before.
+ *
+ * Two tiers serve the device forms.  For decode transforms of n <= 2048 rows
+ * and few wanted rows, one streaming kernel applies the pattern's decode matrix
+ * directly (wanted row = XOR over the present rows of a constant times the
+ * row: each present row read once, each wanted row written once; tables cached
+ * per (present, required), 16 pairs per codec, least recently used).
+ * Otherwise, and for the host form, the reconstruct kernels run with their
+ * output set and pruning mask narrowed to the wanted rows. */
+
+/* Pointer form.  d_shards[i] may be NULL for rows that are neither present nor
+ * rebuilt; a missing-and-required entry points at the output buffer (a degraded
+ * read is "the present rows where they lie, plus one fresh buffer").  Stream
+ * semantics of rs_reconstruct_dev: stream-ordered, nothing waits for the kernel
+ * where the codec has an LDS-resident reconstruct or the direct tier serves. */
+int rs_reconstruct_rows_dev(rs_codec *codec, uint8_t *const *d_shards, const uint8_t *present,
+                            const uint8_t *required, size_t shard_size, void *stream);
+/* Strided form over an rs_reconstruct_dev_batch slab, one (present, required)
+ * pair for every stripe.
+ * Tier choice, measured on one MI355X at 128+32 x 1 MiB, 32 erasures, 16
+ * stripes per launch (profiles/rows_c4.txt), us per stripe,
+ * direct kernel / restricted transform / full rs_reconstruct_dev_batch (the
+ * profile's run 1; its other runs agree to 2 %):
+ * t = 1 wanted row 23.9 / 83.3 / 97.3, t = 2 27.0 / 81.6, t = 4 46.0 / 84.0,
+ * t = 6 68.4 / 83.0, t = 7 92.2 / 84.2, t = 8 104.7 / 83.5, t = 32 418 / 97.7.
+ * The automatic threshold is therefore t <= 6: the direct kernel up to six
+ * wanted rows, the restricted transform from seven on.  At 1024+256 x 256 KiB,
+ * 256 erasures, 8 stripes (n = 2048): t = 1 55.1 / 475.9 / 639.2 and t = 8
+ * 416 / 482; there the threshold is t <= 8, the largest t measured.  One
+ * data row missing and every other row present (t = 1): 29.2 / 91.2 / 85.6. */
+int rs_reconstruct_rows_dev_batch(rs_codec *codec, uint8_t *base, size_t row_stride, size_t stripe_stride,
+                                  size_t nstripes, const uint8_t *present, const uint8_t *required,
+                                  size_t shard_size, void *stream);
+/* Host memory, through the host pipeline of rs_reconstruct (pinned, pageable
+ * and zero-copy rows; single- and multi-device codecs, where the locators are
+ * computed once and every part gets the same `required`).  lens[i] == 0 marks
+ * shard i missing; shards[i] must point at >= S writable bytes for each row
+ * that is rebuilt and may be NULL for the other missing rows; lens[i] is set to
+ * S for the rebuilt rows only. */
+int rs_reconstruct_rows(rs_codec *codec, uint8_t *const *shards, size_t *lens, int nshards,
+                        const uint8_t *required);
+
 /* Batched device encode of `nstripes` independent stripes laid out as one slab
  * per stripe: stripe j, shard i at d_base + j*stripe_stride + i*row_stride.
  * Asynchronous on `stream`. */
@@ -323,6 +384,13 @@ int rs_debug_error_locators(int field_bits, int data_shards, int parity_shards, 
  * row idx (the constants of the incremental update).  RS_ERR_INVALID_ARG for bad
  * arguments, RS_ERR_PANIC where the reference's encode panics. */
 int rs_debug_generator(int field_bits, int data_shards, int parity_shards, int idx, uint32_t *out /* p symbols */);
+/* Row `row` of the decode map of an erasure pattern: out[i] is the constant by
+ * which present shard i enters the shard the reference's Reconstruct puts into
+ * `row` (0 at the missing shards), the constants of rs_reconstruct_rows_dev's
+ * direct tier.  RS_ERR_INVALID_ARG for bad arguments, RS_ERR_PANIC where the
+ * reference's reconstruct panics. */
+int rs_debug_decode_coefficients(int field_bits, int data_shards, int parity_shards, const uint8_t *present, int row,
+                                 uint32_t *out /* k+p symbols */);
 
 /* Checks the half-wave split schedules of the GF(2^16) encode kernel
  * (logm 2..5) against the plain butterfly order on random symbols and
@@ -369,7 +437,9 @@ int rs_debug_encode_bs_fits(int data_shards, int parity_shards, size_t row_strid
  *                     LDS-resident launch (1, default) or the multi-pass kernels (0),
  *   "zc"      0..3    host reconstruct over pinned mapped rows: zero-copy kernels move the
  *                     present rows in (bit 0) and the rebuilt rows out (bit 1) (default 3);
- *                     a cleared bit keeps that direction's per-run hipMemcpy copies.
+ *                     a cleared bit keeps that direction's per-run hipMemcpy copies,
+ *   "rows_direct" -1/0/1  rs_reconstruct_rows_dev*: the direct decode kernel by the measured
+ *                     threshold (-1, default), never (0), or always where n <= 2048 admits it (1).
  * Returns RS_ERR_INVALID_ARG for an unknown knob or value.  Host only. */
 int rs_debug_set_path(const char *knob, int value);
 

@@ -50,6 +50,10 @@ def lib() -> C.CDLL:
     L.rs_verify_dev.argtypes = [vp, P(vp), sz, P(i32), vp]
     L.rs_reconstruct_dev.argtypes = [vp, P(vp), P(C.c_uint8), sz, i32, vp]
     L.rs_reconstruct_dev_batch.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint8), sz, i32, vp]
+    L.rs_reconstruct_rows_dev.argtypes = [vp, P(vp), P(C.c_uint8), P(C.c_uint8), sz, vp]
+    L.rs_reconstruct_rows_dev_batch.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint8), P(C.c_uint8), sz, vp]
+    L.rs_reconstruct_rows.argtypes = [vp, P(vp), P(sz), i32, P(C.c_uint8)]
+    L.rs_debug_decode_coefficients.argtypes = [i32, i32, i32, P(C.c_uint8), i32, vp]
     L.rs_verify_dev_batch.argtypes = [vp, vp, sz, sz, i32, sz, P(i32), vp]
     L.rs_encode_dev_batch.argtypes = [vp, vp, sz, sz, i32, sz, vp]
     L.rs_update_dev.argtypes = [vp, P(vp), P(vp), sz, vp]
@@ -88,7 +92,7 @@ def lib() -> C.CDLL:
     return L
 
 
-_PATH_DEFAULTS = {"bs": 1, "sub": 1, "prune": 1, "unit_width": -1, "hp_tiles": 0, "hp_step": 0, "zc": 3, "hp_tune": 1, "rec_half": 0, "dec_lab": 0, "lds_big": 1}
+_PATH_DEFAULTS = {"bs": 1, "sub": 1, "prune": 1, "unit_width": -1, "hp_tiles": 0, "hp_step": 0, "zc": 3, "hp_tune": 1, "rec_half": 0, "dec_lab": 0, "lds_big": 1, "rows_direct": -1}
 
 
 def set_path(knob: str, value: int) -> None:

@@ -472,6 +472,42 @@ class ReedSolomon:
         """ReconstructSome (leopard16.go:343-348): only len(required) matters."""
         return self._reconstruct(shards, len(required) == self.total_shards())
 
+    def reconstruct_rows(self, shards: list, required: Sequence[bool]) -> list:
+        """Rebuild only the missing shards whose `required` flag is set
+        (rs_reconstruct_rows; k+p flags, data or parity): each is what
+        reconstruct() would put there.  The other missing entries stay as they
+        are; a rebuilt one lands in its EmptyShard's buffer when that holds the
+        shard size, else in a new array."""
+        total = len(shards)
+        if len(required) != total:
+            raise ErrTooFewShards("need %d required flags, got %d" % (total, len(required)))
+        S = next((len(s) for s in shards if s is not None and len(s)), 0)
+        bufs = list(shards)
+        ptrs = (C.c_void_p * total)()
+        lens = (C.c_size_t * total)()
+        for i, s in enumerate(shards):
+            present = s is not None and len(s) > 0
+            if not present:
+                bufs[i] = None
+                if required[i]:
+                    bufs[i] = _capacity_view(s, S)
+                    if bufs[i] is None:
+                        bufs[i] = np.empty(S, dtype=np.uint8)
+            b = bufs[i]
+            if b is not None and len(b):
+                b = np.asarray(b)
+                if b.dtype != np.uint8 or not b.flags["C_CONTIGUOUS"]:
+                    raise TypeError("host shards must be C-contiguous numpy uint8 arrays")
+                bufs[i] = b
+                ptrs[i] = b.ctypes.data
+            lens[i] = len(s) if present else 0
+        req = (C.c_uint8 * total)(*[1 if x else 0 for x in required])
+        _check(self._L.rs_reconstruct_rows(self._h, ptrs, lens, total, req))
+        for i in range(total):
+            if lens[i] and (shards[i] is None or len(shards[i]) == 0):
+                shards[i] = bufs[i]
+        return shards
+
     def encode_idx(self, data_shard, idx: int, parity: list) -> None:
         """EncodeIdx (leopard16.go:227-229): not supported."""
         _check(self._L.rs_encode_idx(self._h, None, 0, idx, None, None, 0))
@@ -706,6 +742,37 @@ class ReedSolomon:
         pr = (C.c_uint8 * len(present))(*[1 if x else 0 for x in present])
         _check(self._L.rs_reconstruct_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, pr, S,
                                                 int(recover_all), _stream_handle(stream)))
+
+    def _flags(self, flags: Sequence[bool], what: str):
+        if len(flags) != self.total_shards():
+            raise ErrTooFewShards("need %d %s flags, got %d" % (self.total_shards(), what, len(flags)))
+        return (C.c_uint8 * len(flags))(*[1 if x else 0 for x in flags])
+
+    def reconstruct_rows_dev(self, rows, present: Sequence[bool], required: Sequence[bool], stream=None) -> None:
+        """Rebuild only the rows that are missing and required, in HBM
+        (rs_reconstruct_rows_dev).  rows: a [k+p, S] tensor, or k+p tensors with
+        None allowed for rows that are neither present nor rebuilt; a missing
+        and required entry is the output buffer.  No other row is written."""
+        if hasattr(rows, "dim") and rows.dim() == 2:
+            ptrs, S = _dev_rows(rows, self.total_shards())
+        else:
+            ptrs, S = _dev_rows_opt(rows, self.total_shards())
+        _check(self._L.rs_reconstruct_rows_dev(self._h, ptrs, self._flags(present, "present"),
+                                               self._flags(required, "required"), S or 0, _stream_handle(stream)))
+
+    def reconstruct_rows_dev_batch(self, slab, present: Sequence[bool], required: Sequence[bool], stream=None) -> None:
+        """Rebuild the missing and required shards of every stripe of a
+        [nstripes, k+p, S] uint8 CUDA tensor in place, one (present, required)
+        pair for all stripes (rs_reconstruct_rows_dev_batch).  Any view with
+        contiguous rows works; stripe and row strides come from the tensor."""
+        if slab.dim() != 3 or slab.shape[1] != self.total_shards():
+            raise TypeError("slab must be a [nstripes, k+p, S] uint8 CUDA tensor")
+        if not slab.is_cuda or slab.dtype.itemsize != 1 or slab.stride(2) != 1:
+            raise TypeError("slab rows must be contiguous uint8 on a CUDA device")
+        n, _, S = slab.shape
+        _check(self._L.rs_reconstruct_rows_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n,
+                                                     self._flags(present, "present"), self._flags(required, "required"),
+                                                     S, _stream_handle(stream)))
 
     def encode_dev_batch(self, slab, stream=None) -> None:
         """Encode a [nstripes, k+p, S] uint8 CUDA tensor in one launch.  Any

@@ -186,6 +186,20 @@ struct UpdPlan : StreamUses {
     }
 };
 
+// The device tables of a direct decode (rs_reconstruct_rows_dev*) for one
+// (present, rows rebuilt) pair: t x np multiply-by-D[j][i] images
+// (make_decode_tables) and the present / rebuilt shard indices.
+struct RowsPlan : StreamUses {
+    DevBuf<uint8_t> blob;
+    const uint32_t *tw = nullptr;
+    const int *src_idx = nullptr, *dst_idx = nullptr;  // device copies of src / dst (strided launches)
+    std::vector<int> src, dst;                         // present shards, rebuilt shards, ascending
+    ~RowsPlan() {
+        drain();
+        blob.release();
+    }
+};
+
 // A small bounded LRU, most recent first.  find() moves a hit to the front;
 // put() inserts at the front and evicts past the cache's capacity, which runs
 // the evicted value's destructor (a DevPlan / UpdPlan waits there for its last
@@ -239,6 +253,7 @@ struct rs_codec {
     bool dec_built = false, dec_ok = false;
     bool dec_sub = false;  // LDS reconstruct runs its transforms in subfield coordinates
     int n = 0, logn = 0;
+    std::vector<uint32_t> dec_ifft_logs, dec_fft_logs;  // decode_schedule's logs (the direct decode's coefficients)
     DevBuf<uint32_t> dtw_ifft, dtw_fft;
     // n = 512..2048: subfield tables of the passes that run in subfield
     // coordinates (RecArgs::tw_ifft_sub / tw_fft_sub, kernels.hip BigSub)
@@ -282,6 +297,8 @@ struct rs_codec {
     // incremental-update tables keyed by the ordered list of changed indices
     // (bounded LRU, as dplan_cache); their row pointers use the ring above
     Lru<std::vector<int>, std::unique_ptr<UpdPlan>, 16> uplan_cache;
+    // direct-decode tables keyed by (erasure pattern, rows rebuilt), likewise
+    Lru<std::vector<uint8_t>, std::unique_ptr<RowsPlan>, 16> rowsplan_cache;
 
     // error-locator cache keyed by erasure pattern (bounded LRU)
     Lru<std::vector<uint8_t>, std::vector<uint32_t>, 64> el_cache;
@@ -335,6 +352,7 @@ struct rs_codec {
         rc_host.release();
         dplan_cache.items.clear();  // each plan waits for its last launch
         uplan_cache.items.clear();
+        rowsplan_cache.items.clear();
         for (int i = 0; i < kRing; i++)
             if (ring_ev[i]) {
                 (void)hipEventSynchronize(ring_ev[i]);
@@ -422,7 +440,7 @@ int upload_split(rs_codec *c) {
 // the reconstruct FFT unpruned, the narrow / wide LDS units) on the same small
 // inputs.  Process-wide; read when a codec is created (bs) or at each launch.
 std::atomic<int> g_path_bs{1}, g_path_sub{1}, g_path_prune{1}, g_path_unit_width{-1}, g_path_hp_tiles{0}, g_path_hp_step{0},
-    g_path_zc{3}, g_path_hp_tune{1}, g_path_rec_half{0}, g_path_dec_lab{0}, g_path_lds_big{1};
+    g_path_zc{3}, g_path_hp_tune{1}, g_path_rec_half{0}, g_path_dec_lab{0}, g_path_lds_big{1}, g_path_rows_direct{-1};
 bool bs_enabled() { return g_path_bs.load(std::memory_order_relaxed) != 0; }
 bool sub_enabled() { return g_path_sub.load(std::memory_order_relaxed) != 0; }
 bool prune_enabled() { return g_path_prune.load(std::memory_order_relaxed) != 0; }
@@ -569,7 +587,7 @@ int upload_big_sub(rs_codec *c, const std::vector<uint32_t> &il, const std::vect
 
 int build_decode_plan(rs_codec *c) {
     if (c->dec_built) return RS_OK;
-    std::vector<uint32_t> il, fl;
+    std::vector<uint32_t> &il = c->dec_ifft_logs, &fl = c->dec_fft_logs;
     c->dec_ok = decode_schedule(*c->F, c->k, c->p, il, fl);
     c->dec_built = true;
     if (!c->dec_ok) return RS_OK;
@@ -858,9 +876,10 @@ const std::vector<uint32_t> *ref_inv_errlocs(rs_codec *c, const std::vector<uint
 // ones of the pattern.  Every reconstruct comes here exactly once, so
 // ref_inv_errlocs is consulted (and stores) once per call, as
 // leopard8.go:509-554 looks up and stores once.
-int resolve_locators(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all, uint64_t S,
+int resolve_locators(rs_codec *c, const std::vector<uint8_t> &present, Want want, uint64_t S,
                      const ElExt *el_ext, ElExt &out) {
-    out = el_ext ? *el_ext : ElExt{ref_inv_errlocs(c, present, recover_all, S), true};
+    // a row selection (rs_reconstruct_rows*) neither reads nor stores the reference-keyed cache
+    out = el_ext ? *el_ext : ElExt{want.rows ? nullptr : ref_inv_errlocs(c, present, want.all, S), true};
     if (out.el) return RS_OK;
     std::vector<uint8_t> erased(c->total);
     for (int i = 0; i < c->total; i++) erased[i] = !present[i];
@@ -870,10 +889,12 @@ int resolve_locators(rs_codec *c, const std::vector<uint8_t> &present, bool reco
 
 // Plan-cache key: (erasure pattern, recover_all), plus the errLocs a
 // reference-keyed cache handed out, which can differ between calls with the
-// same pattern.
-std::vector<uint8_t> plan_key(const std::vector<uint8_t> &present, bool recover_all, const ElExt &loc) {
+// same pattern.  A row selection's key is (pattern, 2, the rows it rebuilds).
+std::vector<uint8_t> plan_key(const std::vector<uint8_t> &present, Want want, const ElExt &loc) {
     std::vector<uint8_t> key(present);
-    key.push_back(recover_all ? 1 : 0);
+    key.push_back(want.rows ? 2 : want.all ? 1 : 0);
+    if (want.rows)
+        for (size_t i = 0; i < present.size(); i++) key.push_back(!present[i] && (*want.rows)[i]);
     if (loc.ref) {
         const uint8_t *b = (const uint8_t *)loc.el->data();
         key.insert(key.end(), b, b + loc.el->size() * sizeof(uint32_t));
@@ -882,7 +903,7 @@ std::vector<uint8_t> plan_key(const std::vector<uint8_t> &present, bool recover_
 }
 
 // The plan of one erasure pattern from its locators `el` (leopard16.go:432-568).
-int plan_reconstruct_new(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all,
+int plan_reconstruct_new(rs_codec *c, const std::vector<uint8_t> &present, Want want,
                          const std::vector<uint32_t> &el, RecPlan &pl) {
     int e = build_decode_plan(c);
     if (e) return e;
@@ -906,9 +927,8 @@ int plan_reconstruct_new(rs_codec *c, const std::vector<uint8_t> &present, bool 
     }
     pl.dst_shard.clear();
     pl.pos.clear();
-    const int end = recover_all ? total : k;
-    for (int i = 0; i < end; i++) {
-        if (present[i]) continue;
+    for (int i = 0; i < total; i++) {
+        if (present[i] || !want.has(i, k)) continue;
         pl.dst_shard.push_back(i);
         pl.pos.push_back(i >= k ? i - k : i + m);
     }
@@ -925,23 +945,23 @@ int plan_reconstruct_new(rs_codec *c, const std::vector<uint8_t> &present, bool 
 
 // Plans are cached per (erasure pattern, recover_all): repeated repairs of
 // the same pattern skip the table construction.
-int plan_reconstruct_el(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all, const ElExt &loc,
+int plan_reconstruct_el(rs_codec *c, const std::vector<uint8_t> &present, Want want, const ElExt &loc,
                         RecPlan &pl) {
-    std::vector<uint8_t> key = plan_key(present, recover_all, loc);
+    std::vector<uint8_t> key = plan_key(present, want, loc);
     if (const RecPlan *hit = c->plan_cache.find(key)) {
         pl = *hit;
         return RS_OK;
     }
-    int e = plan_reconstruct_new(c, present, recover_all, *loc.el, pl);
+    int e = plan_reconstruct_new(c, present, want, *loc.el, pl);
     if (e) return e;
     c->plan_cache.put(std::move(key), pl);
     return RS_OK;
 }
-int plan_reconstruct(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all, uint64_t S, RecPlan &pl,
+int plan_reconstruct(rs_codec *c, const std::vector<uint8_t> &present, Want want, uint64_t S, RecPlan &pl,
                      const ElExt *el_ext = nullptr) {
     ElExt loc;
-    if (int e = resolve_locators(c, present, recover_all, S, el_ext, loc)) return e;
-    return plan_reconstruct_el(c, present, recover_all, loc, pl);
+    if (int e = resolve_locators(c, present, want, S, el_ext, loc)) return e;
+    return plan_reconstruct_el(c, present, want, loc, pl);
 }
 
 // Upload a plan for `nsets` row-pointer sets (set b: shard i at d[b][i]) as
@@ -994,17 +1014,17 @@ int launch_reconstruct(rs_codec *c, const RecPlan &pl, int set, uint64_t S, hipS
 }
 
 // Device-resident plan for (present, recover_all), built and uploaded on first use.
-int dev_plan(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all, uint64_t S, DevPlan **out,
+int dev_plan(rs_codec *c, const std::vector<uint8_t> &present, Want want, uint64_t S, DevPlan **out,
              const ElExt *el_ext = nullptr) {
     ElExt loc;
-    if (int e = resolve_locators(c, present, recover_all, S, el_ext, loc)) return e;
-    std::vector<uint8_t> key = plan_key(present, recover_all, loc);
+    if (int e = resolve_locators(c, present, want, S, el_ext, loc)) return e;
+    std::vector<uint8_t> key = plan_key(present, want, loc);
     if (auto *hit = c->dplan_cache.find(key)) {
         *out = hit->get();
         return RS_OK;
     }
     auto dp = std::make_unique<DevPlan>();
-    if (int e = plan_reconstruct_el(c, present, recover_all, loc, dp->pl)) return e;
+    if (int e = plan_reconstruct_el(c, present, want, loc, dp->pl)) return e;
     const RecPlan &pl = dp->pl;
     const size_t s_in = pl.tw_in.size() * 4, s_out = pl.tw_out.size() * 4, s_pos = std::max<size_t>(pl.pos.size(), 1) * 4;
     const size_t s_si = pl.src_shard.size() * 4, s_di = std::max<size_t>(pl.dst_shard.size(), 1) * 4;
@@ -1116,9 +1136,9 @@ int ring_acquire(rs_codec *c, size_t want, int &slot, uint8_t *&h, uint8_t *&g) 
 // through a ring slot; nothing waits for the kernel -- the call is
 // stream-ordered like the device encodes.
 int reconstruct_device_lds(rs_codec *c, uint8_t *const *d, const std::vector<uint8_t> &present, uint64_t S,
-                           bool recover_all, hipStream_t s) {
+                           Want want, hipStream_t s) {
     DevPlan *dp = nullptr;
-    if (int e = dev_plan(c, present, recover_all, S, &dp)) return e;
+    if (int e = dev_plan(c, present, want, S, &dp)) return e;
     const RecPlan &pl = dp->pl;
     const int n = c->n, nd = (int)pl.dst_shard.size();
     if (!nd) return RS_OK;
@@ -1261,11 +1281,106 @@ int update_device_batch(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_
     return RS_OK;
 }
 
+// ---- Direct decode of a few rows (rs_reconstruct_rows_dev / _batch, kernels.hip k_decode_rows)
+// The direct tier serves decode transforms of n <= 2048 (every BASELINE repair
+// shape): a plan costs t transposed transforms of n rows and t * np tables.
+constexpr int kRowsDirectMaxN = 2048;
+// Largest number of wanted rows the automatic choice hands to the direct tier:
+// the largest t at which it measured faster than the restricted transform
+// (profiles/rows_c4.txt).  At C4 (128+32, n = 256, 32
+// erasures) t = 6: 68.4 us per stripe against 83.0, and t = 7 loses, 92.2
+// against 84.2.  At 1024+256 (n = 2048, 256 erasures) t = 8, the largest
+// measured: 416 us against 482.  n = 512 and 1024 are unmeasured and take
+// the smaller value.
+constexpr int kRowsDirectAuto = 6, kRowsDirectAuto2048 = 8;
+
+bool rows_direct(const rs_codec *c, int t) {
+    if (!c->dec_ok || c->n > kRowsDirectMaxN) return false;
+    const int knob = g_path_rows_direct.load(std::memory_order_relaxed);
+    return knob == 1 || (knob < 0 && t <= (c->n == 2048 ? kRowsDirectAuto2048 : kRowsDirectAuto));
+}
+
+// Cached device tables for (present, required), built and uploaded on first
+// use, always from the exact locators of the pattern.
+int rows_plan(rs_codec *c, const std::vector<uint8_t> &present, const std::vector<uint8_t> &required, RowsPlan **out) {
+    const int total = c->total;
+    std::vector<uint8_t> key(present), erased(total);
+    for (int i = 0; i < total; i++) {
+        key.push_back(!present[i] && required[i]);
+        erased[i] = !present[i];
+    }
+    if (auto *hit = c->rowsplan_cache.find(key)) {
+        *out = hit->get();
+        return RS_OK;
+    }
+    const std::vector<uint32_t> *el = error_locs_cached(c, erased);
+    if (!el) return RS_ERR_PANIC;
+    auto dp = std::make_unique<RowsPlan>();
+    for (int i = 0; i < total; i++) {
+        if (present[i]) dp->src.push_back(i);
+        else if (required[i]) dp->dst.push_back(i);
+    }
+    const size_t np = dp->src.size(), t = dp->dst.size();
+    const size_t s_tw = t * np * c->twd * 4;
+    const size_t o_si = align256(s_tw), o_di = o_si + align256(np * 4), bytes = o_di + align256(t * 4);
+    std::vector<uint8_t> h(bytes, 0);
+    make_decode_tables(*c->F, c->k, c->p, erased.data(), *el, c->dec_ifft_logs, c->dec_fft_logs, dp->dst.data(), (int)t,
+                       (uint32_t *)h.data());
+    std::memcpy(h.data() + o_si, dp->src.data(), np * 4);
+    std::memcpy(h.data() + o_di, dp->dst.data(), t * 4);
+    if (int e = upload(dp->blob, h)) return e;
+    dp->tw = (const uint32_t *)dp->blob.p;
+    dp->src_idx = (const int *)(dp->blob.p + o_si);
+    dp->dst_idx = (const int *)(dp->blob.p + o_di);
+    *out = c->rowsplan_cache.put(std::move(key), std::move(dp))->get();  // an eviction waits for that plan's last launch
+    return RS_OK;
+}
+
+// d != nullptr: the pointer form (row pointers through a ring slot); else the
+// strided form over `base`.  Stream-ordered: nothing waits for the kernel.
+int decode_rows_device(rs_codec *c, uint8_t *const *d, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride,
+                       int nstripes, const std::vector<uint8_t> &present, const std::vector<uint8_t> &required,
+                       uint64_t S, hipStream_t s) {
+    RowsPlan *dp = nullptr;
+    if (int e = rows_plan(c, present, required, &dp)) return e;
+    const int np = (int)dp->src.size(), t = (int)dp->dst.size();
+    DecodeRowsArgs a{};
+    a.tw = dp->tw;
+    a.S = S;
+    a.np = np;
+    a.t = t;
+    a.nstripes = nstripes;
+    int slot = -1;
+    if (d) {
+        uint8_t *h = nullptr, *g = nullptr;
+        const size_t bytes = (size_t)(np + t) * sizeof(void *);
+        if (int e = ring_acquire(c, bytes, slot, h, g)) return e;
+        uint8_t **rows = (uint8_t **)h;
+        for (int i = 0; i < np; i++) rows[i] = d[dp->src[i]];
+        for (int j = 0; j < t; j++) rows[np + j] = d[dp->dst[j]];
+        HIP_TRY(hipMemcpyAsync(g, h, bytes, hipMemcpyHostToDevice, s));
+        a.rows = (uint8_t *const *)g;
+    } else {
+        a.base = base;
+        a.row_stride = row_stride;
+        a.stripe_stride = stripe_stride;
+        a.src_idx = dp->src_idx;
+        a.dst_idx = dp->dst_idx;
+    }
+    HIP_TRY(launch_decode_rows(c->bits, a, s));
+    if (slot >= 0) {
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+    }
+    HIP_TRY(dp->mark_used(s));
+    return RS_OK;
+}
+
 // Device reconstruct (leopard16.go:432-568) for already-validated input.
 int reconstruct_device(rs_codec *c, uint8_t *const *d, const std::vector<uint8_t> &present, uint64_t S,
-                       bool recover_all, hipStream_t s) {
+                       Want want, hipStream_t s) {
     RecPlan pl;
-    int e = plan_reconstruct(c, present, recover_all, S, pl);
+    int e = plan_reconstruct(c, present, want, S, pl);
     if (e) return e;
     e = scratch_acquire(c, s);
     if (e) return e;
@@ -1459,7 +1574,7 @@ struct PipeDrainIf {
 // returns after queueing every segment; *ticket completes when the parity is
 // in the caller's rows (rs_encode_wait).
 int host_pipeline(rs_codec *c, uint8_t *const *shards, uint64_t S, HostOp op, const std::vector<uint8_t> &present,
-                  bool recover_all, int *ok, uint64_t *ticket = nullptr, const ElExt *el_ext = nullptr) {
+                  Want want, int *ok, uint64_t *ticket = nullptr, const ElExt *el_ext = nullptr) {
     int e = ensure_host_pipe(c);
     if (e) return e;
     PipeDrainIf drain_guard{c};
@@ -1476,11 +1591,11 @@ int host_pipeline(rs_codec *c, uint8_t *const *shards, uint64_t S, HostOp op, co
     if (op == HostOp::Reconstruct) {
         if (int be = build_decode_plan(c)) return be;
         if (c->dec_ok && rec_lds_ok(c)) {
-            e = dev_plan(c, present, recover_all, S, &dpl, el_ext);
+            e = dev_plan(c, present, want, S, &dpl, el_ext);
             if (e) return e;
             pl = dpl->pl;
         } else {
-            e = plan_reconstruct(c, present, recover_all, S, pl, el_ext);
+            e = plan_reconstruct(c, present, want, S, pl, el_ext);
             if (e) return e;
         }
         for (int i = 0; i < total; i++)
@@ -1648,11 +1763,11 @@ int host_pipeline(rs_codec *c, uint8_t *const *shards, uint64_t S, HostOp op, co
 // A host-resident call under the codec mutex: on the parts of a multi-device
 // codec, else through this codec's own pipeline.
 int host_run(rs_codec *c, HostOp op, uint8_t *const *shards, uint64_t S, const std::vector<uint8_t> &present,
-             bool recover_all, int *ok, uint64_t *ticket, const ElExt *el = nullptr) {
-    if (c->multi) return multi_host(c->multi, c, op, shards, S, present, recover_all, ok, ticket);
+             Want want, int *ok, uint64_t *ticket, const ElExt *el = nullptr) {
+    if (c->multi) return multi_host(c->multi, c, op, shards, S, present, want, ok, ticket);
     DeviceGuard g(c->device);
     if (int ie = ensure_device(c)) return ie;
-    return host_pipeline(c, shards, S, op, present, recover_all, ok, ticket, el);
+    return host_pipeline(c, shards, S, op, present, want, ok, ticket, el);
 }
 
 // rs_encode / rs_encode_async / rs_verify / rs_verify_async after their NULL
@@ -1705,16 +1820,15 @@ int encode_dev_call(rs_codec *c, uint8_t *const *d, uint8_t *base, uint64_t row_
 // The rules rs_reconstruct_dev, rs_reconstruct_dev_batch and the host
 // reconstructs share (leopard16.go:390-430), on the shards marked present.
 // done: `return` is the call's result (an error, or RS_OK with nothing to rebuild).
-int reconstruct_checks(const rs_codec *c, const std::vector<uint8_t> &present, uint64_t S, bool recover_all, bool &done) {
-    int np = 0, dp = 0;
-    for (int i = 0; i < c->total; i++)
-        if (present[i]) {
-            np++;
-            if (i < c->k) dp++;
-        }
+int reconstruct_checks(const rs_codec *c, const std::vector<uint8_t> &present, uint64_t S, Want want, bool &done) {
+    int np = 0, todo = 0;  // present rows; missing rows the call rebuilds
+    for (int i = 0; i < c->total; i++) {
+        if (present[i]) np++;
+        else if (want.has(i, c->k)) todo++;
+    }
     done = true;
     if (np == 0 || S == 0) return RS_ERR_SHARD_NO_DATA;
-    if (np == c->total || (!recover_all && dp == c->k)) return RS_OK;
+    if (todo == 0) return RS_OK;
     if (np < c->k) return RS_ERR_TOO_FEW_SHARDS;
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
     done = false;
@@ -1724,44 +1838,100 @@ int reconstruct_checks(const rs_codec *c, const std::vector<uint8_t> &present, u
 
 // rs_reconstruct / rs_reconstruct_async.  Nothing to rebuild: RS_OK with no
 // ticket issued (*ticket stays 0, which rs_ticket_wait / query report as done).
-int reconstruct_host(rs_codec *c, uint8_t *const *shards, size_t *lens, int nshards, int recover_all, uint64_t *ticket) {
+// required != nullptr: rs_reconstruct_rows (k+p flags; recover_all is not read).
+int reconstruct_host(rs_codec *c, uint8_t *const *shards, size_t *lens, int nshards, int recover_all,
+                     const uint8_t *required, uint64_t *ticket) {
     if (!c || !shards || !lens) return RS_ERR_INVALID_ARG;
-    if (nshards != c->total) return RS_ERR_TOO_FEW_SHARDS;
+    if (nshards != c->total) return RS_ERR_TOO_FEW_SHARDS;  // required has nshards flags: read only past this check
+    const std::vector<uint8_t> req(required, required ? required + c->total : required);
+    const Want want = required ? Want(req) : Want(recover_all != 0);
     int e = check_shards(lens, nshards, true);
     if (e) return e;
     std::vector<uint8_t> pr(c->total);
     for (int i = 0; i < c->total; i++) pr[i] = lens[i] != 0;
     const uint64_t S = shard_size_of(lens, nshards);  // > 0, and a shard is present (check_shards)
     bool done;
-    e = reconstruct_checks(c, pr, S, recover_all != 0, done);
+    e = reconstruct_checks(c, pr, S, want, done);
     if (done) return e;
-    const int end = recover_all ? c->total : c->k;
     for (int i = 0; i < c->total; i++)
-        if ((pr[i] || i < end) && !shards[i]) return RS_ERR_INVALID_ARG;
+        if ((pr[i] || want.has(i, c->k)) && !shards[i]) return RS_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
-    e = host_run(c, HostOp::Reconstruct, shards, S, pr, recover_all != 0, nullptr, ticket);
+    e = host_run(c, HostOp::Reconstruct, shards, S, pr, want, nullptr, ticket);
     if (e) return e;
-    for (int i = 0; i < end; i++)
-        if (!pr[i]) lens[i] = S;
+    for (int i = 0; i < c->total; i++)
+        if (!pr[i] && want.has(i, c->k)) lens[i] = S;
     return RS_OK;
+}
+
+// Missing rows a row selection rebuilds.
+int rows_wanted(const rs_codec *c, const std::vector<uint8_t> &pr, Want want) {
+    int t = 0;
+    for (int i = 0; i < c->total; i++) t += !pr[i] && want.has(i, c->k);
+    return t;
+}
+
+// rs_reconstruct_dev_batch / rs_reconstruct_rows_dev_batch after their NULL checks.
+int reconstruct_dev_batch_call(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
+                               const std::vector<uint8_t> &pr, Want want, size_t S, void *stream) {
+    bool done;
+    const int ce = reconstruct_checks(c, pr, S, want, done);
+    if (done) return ce;
+    if (row_stride < S || (nstripes > 1 && stripe_stride < (size_t)c->total * row_stride)) return RS_ERR_INVALID_ARG;
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    if (int e = build_decode_plan(c)) return e;
+    if (want.rows && rows_direct(c, rows_wanted(c, pr, want)))
+        return dc.finish(decode_rows_device(c, nullptr, base, row_stride, stripe_stride, (int)nstripes, pr, *want.rows, S, s));
+    if (c->dec_ok && rec_lds_ok(c)) {
+        // one launch: grid.y = stripe, the pattern's tables shared (dev_plan cache)
+        DevPlan *dpl = nullptr;
+        if (int e = dev_plan(c, pr, want, S, &dpl)) return e;
+        return dc.finish(launch_rec_plan(c, dpl, base, row_stride, stripe_stride, (int)nstripes, S, s));
+    }
+    // multi-pass codecs (n > 256): stripe by stripe
+    std::vector<uint8_t *> rows(c->total);
+    for (size_t z = 0; z < nstripes; z++) {
+        for (int i = 0; i < c->total; i++) rows[i] = base + z * stripe_stride + (uint64_t)i * row_stride;
+        if (int e = reconstruct_device(c, rows.data(), pr, S, want, s)) return e;
+    }
+    return RS_OK;
+}
+
+// rs_reconstruct_dev / rs_reconstruct_rows_dev after their NULL checks.
+int reconstruct_dev_call(rs_codec *c, uint8_t *const *d, const std::vector<uint8_t> &pr, Want want, size_t S,
+                         void *stream) {
+    bool done;
+    const int ce = reconstruct_checks(c, pr, S, want, done);
+    if (done) return ce;
+    for (int i = 0; i < c->total; i++)
+        if ((pr[i] || want.has(i, c->k)) && !d[i]) return RS_ERR_INVALID_ARG;
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    if (int e = build_decode_plan(c)) return e;
+    if (want.rows && rows_direct(c, rows_wanted(c, pr, want)))
+        return dc.finish(decode_rows_device(c, d, nullptr, 0, 0, 1, pr, *want.rows, S, s));
+    if (c->dec_ok && rec_lds_ok(c)) return dc.finish(reconstruct_device_lds(c, d, pr, S, want, s));
+    return reconstruct_device(c, d, pr, S, want, s);
 }
 
 }  // namespace
 
 // ---------------------------------------------------------------- multi-device parts (multi.hpp)
 int rs::part_host_call(rs_codec *c, HostOp op, uint8_t *const *shards, uint64_t S, const std::vector<uint8_t> &present,
-                       bool recover_all, int *ok, uint64_t *ticket, const ElExt *el) {
+                       Want want, int *ok, uint64_t *ticket, const ElExt *el) {
     std::lock_guard<std::mutex> lk(c->mu);
-    return host_run(c, op, shards, S, present, recover_all, ok, ticket, el);  // a part has no parts of its own
+    return host_run(c, op, shards, S, present, want, ok, ticket, el);  // a part has no parts of its own
 }
 
 // The locators a single-device codec would use for this call (its reference-
 // keyed GF(2^8) cache, whose useBits key depends on the full S, else the exact
 // ones), looked up once per call like leopard8.go:509-554.  The pointer stays
 // valid while the parent's mutex is held, i.e. for the whole multi call.
-int rs::parent_error_locators(rs_codec *c, const std::vector<uint8_t> &present, bool recover_all, uint64_t S,
+int rs::parent_error_locators(rs_codec *c, const std::vector<uint8_t> &present, Want want, uint64_t S,
                               ElExt &out) {
-    return resolve_locators(c, present, recover_all, S, nullptr, out);
+    return resolve_locators(c, present, want, S, nullptr, out);
 }
 
 // Host simulation of the split schedules against the plain op lists on random
@@ -2050,47 +2220,37 @@ int rs_reconstruct_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size
                              const uint8_t *present, size_t S, int recover_all, void *stream) {
     if (!c || !base || !present || nstripes == 0 || nstripes > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
     if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
-    std::vector<uint8_t> pr(present, present + c->total);
-    bool done;
-    const int ce = reconstruct_checks(c, pr, S, recover_all != 0, done);
-    if (done) return ce;
-    if (row_stride < S || (nstripes > 1 && stripe_stride < (size_t)c->total * row_stride)) return RS_ERR_INVALID_ARG;
-    DevCall dc(c, stream);
-    if (dc.err) return dc.err;
-    const hipStream_t s = dc.s;
-    if (int e = build_decode_plan(c)) return e;
-    if (c->dec_ok && rec_lds_ok(c)) {
-        // one launch: grid.y = stripe, the pattern's tables shared (dev_plan cache)
-        DevPlan *dpl = nullptr;
-        if (int e = dev_plan(c, pr, recover_all != 0, S, &dpl)) return e;
-        return dc.finish(launch_rec_plan(c, dpl, base, row_stride, stripe_stride, (int)nstripes, S, s));
-    }
-    // multi-pass codecs (n > 256): stripe by stripe
-    std::vector<uint8_t *> rows(c->total);
-    for (size_t z = 0; z < nstripes; z++) {
-        for (int i = 0; i < c->total; i++) rows[i] = base + z * stripe_stride + (uint64_t)i * row_stride;
-        if (int e = reconstruct_device(c, rows.data(), pr, S, recover_all != 0, s)) return e;
-    }
-    return RS_OK;
+    const std::vector<uint8_t> pr(present, present + c->total);
+    return reconstruct_dev_batch_call(c, base, row_stride, stripe_stride, nstripes, pr, recover_all != 0, S, stream);
+}
+
+int rs_reconstruct_rows_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
+                                  const uint8_t *present, const uint8_t *required, size_t S, void *stream) {
+    if (!c || !base || !present || !required || nstripes == 0 || nstripes > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    const std::vector<uint8_t> pr(present, present + c->total), req(required, required + c->total);
+    return reconstruct_dev_batch_call(c, base, row_stride, stripe_stride, nstripes, pr, Want(req), S, stream);
 }
 
 int rs_reconstruct_dev(rs_codec *c, uint8_t *const *d, const uint8_t *present, size_t S, int recover_all,
                        void *stream) {
     if (!c || !d || !present) return RS_ERR_INVALID_ARG;
     if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
-    std::vector<uint8_t> pr(present, present + c->total);
-    bool done;
-    const int ce = reconstruct_checks(c, pr, S, recover_all != 0, done);
-    if (done) return ce;
-    const int end = recover_all ? c->total : c->k;
-    for (int i = 0; i < c->total; i++)
-        if ((pr[i] || i < end) && !d[i]) return RS_ERR_INVALID_ARG;
-    DevCall dc(c, stream);
-    if (dc.err) return dc.err;
-    const hipStream_t s = dc.s;
-    if (int e = build_decode_plan(c)) return e;
-    if (c->dec_ok && rec_lds_ok(c)) return dc.finish(reconstruct_device_lds(c, d, pr, S, recover_all != 0, s));
-    return reconstruct_device(c, d, pr, S, recover_all != 0, s);
+    const std::vector<uint8_t> pr(present, present + c->total);
+    return reconstruct_dev_call(c, d, pr, recover_all != 0, S, stream);
+}
+
+int rs_reconstruct_rows_dev(rs_codec *c, uint8_t *const *d, const uint8_t *present, const uint8_t *required, size_t S,
+                            void *stream) {
+    if (!c || !d || !present || !required) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    const std::vector<uint8_t> pr(present, present + c->total), req(required, required + c->total);
+    return reconstruct_dev_call(c, d, pr, Want(req), S, stream);
+}
+
+int rs_reconstruct_rows(rs_codec *c, uint8_t *const *shards, size_t *lens, int nshards, const uint8_t *required) {
+    if (!required) return RS_ERR_INVALID_ARG;
+    return reconstruct_host(c, shards, lens, nshards, 1, required, nullptr);
 }
 
 int rs_encode(rs_codec *c, uint8_t *const *shards, const size_t *lens, int nshards) {
@@ -2182,14 +2342,14 @@ int rs_verify(rs_codec *c, uint8_t *const *shards, const size_t *lens, int nshar
 }
 
 int rs_reconstruct(rs_codec *c, uint8_t *const *shards, size_t *lens, int nshards, int recover_all) {
-    return reconstruct_host(c, shards, lens, nshards, recover_all, nullptr);
+    return reconstruct_host(c, shards, lens, nshards, recover_all, nullptr, nullptr);
 }
 
 int rs_reconstruct_async(rs_codec *c, uint8_t *const *shards, size_t *lens, int nshards, int recover_all,
                          uint64_t *ticket) {
     if (!ticket) return RS_ERR_INVALID_ARG;
     *ticket = 0;
-    return reconstruct_host(c, shards, lens, nshards, recover_all, ticket);
+    return reconstruct_host(c, shards, lens, nshards, recover_all, nullptr, ticket);
 }
 
 int rs_split_shard_size(const rs_codec *c, size_t len, size_t *per_shard) {
@@ -2380,6 +2540,15 @@ int rs_debug_generator(int bits, int k, int p, int idx, uint32_t *out) {
     return RS_OK;
 }
 
+int rs_debug_decode_coefficients(int bits, int k, int p, const uint8_t *present, int row, uint32_t *out) {
+    if ((bits != 8 && bits != 16) || !present || !out || k <= 0 || p <= 0 || row < 0 || row >= k + p) return RS_ERR_INVALID_ARG;
+    std::vector<uint8_t> erased((size_t)k + p);
+    for (int i = 0; i < k + p; i++) erased[i] = !present[i];
+    std::vector<uint32_t> el;
+    if (!error_locators(field(bits), k, p, erased.data(), el)) return RS_ERR_PANIC;
+    return decode_coefficients(field(bits), k, p, erased.data(), el, row, out) ? RS_OK : RS_ERR_PANIC;
+}
+
 int rs_encode_idx(rs_codec *c, const uint8_t *, size_t, int, uint8_t *const *, const size_t *, int) {
     return c ? RS_ERR_NOT_SUPPORTED : RS_ERR_INVALID_ARG;
 }
@@ -2475,6 +2644,7 @@ int rs_debug_set_path(const char *knob, int value) {
     else if (k == "dec_lab" && value >= 0 && value <= 255) g_path_dec_lab = value;
     else if (k == "lds_big" && value >= 0 && value <= 1) g_path_lds_big = value;
     else if (k == "zc" && value >= 0 && value <= 3) g_path_zc = value;
+    else if (k == "rows_direct" && value >= -1 && value <= 1) g_path_rows_direct = value;
     else return RS_ERR_INVALID_ARG;
     return RS_OK;
 }

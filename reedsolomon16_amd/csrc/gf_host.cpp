@@ -437,4 +437,97 @@ bool error_locators(const Field &F, int k, int p, const uint8_t *erased, std::ve
     return true;
 }
 
+void decode_coefficients_from(const Field &F, int k, int p, const uint8_t *erased, const std::vector<uint32_t> &el,
+                              const std::vector<uint32_t> &ifft, const std::vector<uint32_t> &fft, int row,
+                              uint32_t *out) {
+    const int m = ceil_pow2(p), n = ceil_pow2(m + k), logn = ilog2(n);
+    const int q = row >= k ? row - k : row + m;  // the work row the shard is revealed from
+    SymRows R{F, std::vector<uint32_t>((size_t)n, 0)};
+    R.w[q] = 1;
+    // The decode is reveal . FFT . derivative . IFFT . scale-in; row q of its
+    // matrix is e_q pushed through the transposes in reverse order.  A
+    // butterfly's transpose is the other butterfly with its rows swapped:
+    // fft2(x, y)^T = ifft2(y, x), ifft2(x, y)^T = fft2(y, x).  Groups the
+    // reference skips (twiddle == mod past m + k) only touch columns no
+    // present row feeds, so running them XOR-only changes nothing that is read.
+    const std::vector<PassInfo> fp = fft_passes(logn), ip = ifft_passes(logn);
+    for (auto it = fp.rbegin(); it != fp.rend(); ++it) {
+        const PassInfo &ps = *it;
+        if (ps.radix == 4) {
+            for (int g = 0; g < ps.groups; g++) {
+                const int r = g * 4 * ps.dist, d = ps.dist;
+                const uint32_t *s = fft.data() + ps.slot_off + 3 * g;  // (m01, m02, m23)
+                for (int i = r; i < r + d; i++) {
+                    R.ifft2(i + 3 * d, i + 2 * d, s[2]);
+                    R.ifft2(i + d, i, s[0]);
+                    R.ifft2(i + 3 * d, i + d, s[1]);
+                    R.ifft2(i + 2 * d, i, s[1]);
+                }
+            }
+        } else {
+            for (int g = 0; g < ps.groups; g++) R.ifft2(2 * g + 1, 2 * g, fft[ps.slot_off + g]);
+        }
+    }
+    // formal derivative (leopard16.go:527-530): row r takes row r | 1 << b for
+    // every clear bit b of r; transposed, row r feeds every such r | 1 << b
+    {
+        std::vector<uint32_t> v(R.w);
+        for (int r = 0; r < n; r++)
+            if (v[r])
+                for (int b = 0; b < logn; b++)
+                    if (!((r >> b) & 1)) R.w[r | (1 << b)] ^= v[r];
+    }
+    for (auto it = ip.rbegin(); it != ip.rend(); ++it) {
+        const PassInfo &ps = *it;
+        if (ps.radix == 4) {
+            for (int g = 0; g < ps.groups; g++) {
+                const int r = g * 4 * ps.dist, d = ps.dist;
+                const uint32_t *s = ifft.data() + ps.slot_off + 3 * g;
+                for (int i = r; i < r + d; i++) {
+                    R.fft2(i + 3 * d, i + d, s[1]);
+                    R.fft2(i + 2 * d, i, s[1]);
+                    R.fft2(i + 3 * d, i + 2 * d, s[2]);
+                    R.fft2(i + d, i, s[0]);
+                }
+            }
+        } else {
+            for (int i = 0; i < ps.dist; i++) R.fft2(i + ps.dist, i, ifft[ps.slot_off]);
+        }
+    }
+    // scale-in by errLocs[r] and reveal by mod - errLocs[q] (leopard16.go:494, 507, 563, 566)
+    const uint32_t lq = (F.mod - el[q]) & F.mod;
+    for (int i = 0; i < k + p; i++) {
+        const int r = i >= k ? i - k : i + m;
+        out[i] = erased[i] ? 0 : F.mul_log(F.mul_log(R.w[r], el[r]), lq);
+    }
+}
+
+bool decode_coefficients(const Field &F, int k, int p, const uint8_t *erased, const std::vector<uint32_t> &el, int row,
+                         uint32_t *out) {
+    if (k <= 0 || p <= 0 || row < 0 || row >= k + p || el.size() < F.order) return false;
+    std::vector<uint32_t> il, fl;
+    if (!decode_schedule(F, k, p, il, fl)) return false;
+    decode_coefficients_from(F, k, p, erased, el, il, fl, row, out);
+    return true;
+}
+
+void make_decode_tables(const Field &F, int k, int p, const uint8_t *erased, const std::vector<uint32_t> &el,
+                        const std::vector<uint32_t> &ifft, const std::vector<uint32_t> &fft, const int *rows, int t,
+                        uint32_t *out) {
+    const int twd = tw_dwords(F.bits);
+    int np = 0;
+    for (int i = 0; i < k + p; i++) np += erased[i] ? 0 : 1;
+    std::vector<uint32_t> co((size_t)k + p);
+    for (int j = 0; j < t; j++) {
+        decode_coefficients_from(F, k, p, erased, el, ifft, fft, rows[j], co.data());
+        uint32_t *o = out + (size_t)j * np * twd;
+        // log[0] is not a log: a zero coefficient ships as the zero twiddle's all-zero table
+        for (int i = 0; i < k + p; i++)
+            if (!erased[i]) {
+                make_twiddle(F, co[i] ? F.log[co[i]] : F.mod, o, true);
+                o += twd;
+            }
+    }
+}
+
 }  // namespace rs

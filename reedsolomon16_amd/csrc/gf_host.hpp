@@ -144,4 +144,27 @@ bool decode_schedule(const Field &F, int k, int p, std::vector<uint32_t> &ifft_l
 // Returns false when the reference would panic (GF(2^8) with m+k > 256).
 bool error_locators(const Field &F, int k, int p, const uint8_t *erased, std::vector<uint32_t> &err_locs);
 
+// Row `row` (a shard index in [0, k+p), usually an erased one) of the decode
+// map of an erasure pattern: the reference's reconstruct (leopard16.go:390-570,
+// leopard8.go:439-695) is GF-linear in the present rows, so the shard it puts
+// into `row` is the XOR over the present shards i of out[i] * shard i, symbol
+// by symbol; out has k+p entries, 0 at the erased shards.  Computed with the
+// reference's own schedule (decode_schedule; scale-in by el, the formal
+// derivative, reveal by mod - el) on single symbols through the transposed
+// transforms: O(n log n) per row.  el: the pattern's error_locators.  False
+// where decode_schedule returns false or for a row outside [0, k+p).
+bool decode_coefficients(const Field &F, int k, int p, const uint8_t *erased, const std::vector<uint32_t> &el, int row,
+                         uint32_t *out);
+// The same from the logs decode_schedule returned for (k, p) (a codec keeps them).
+void decode_coefficients_from(const Field &F, int k, int p, const uint8_t *erased, const std::vector<uint32_t> &el,
+                              const std::vector<uint32_t> &ifft_logs, const std::vector<uint32_t> &fft_logs, int row,
+                              uint32_t *out);
+// Decode tables for the wanted rows rows[0..t): t x (number present) images of
+// "multiply by the coefficient" at out + (j * npresent + i) * tw_dwords, i
+// counting the present shards in ascending order (butterfly layout); a zero
+// coefficient is the all-zero table (its log is never taken).
+void make_decode_tables(const Field &F, int k, int p, const uint8_t *erased, const std::vector<uint32_t> &el,
+                        const std::vector<uint32_t> &ifft_logs, const std::vector<uint32_t> &fft_logs, const int *rows,
+                        int t, uint32_t *out);
+
 }  // namespace rs

@@ -2252,4 +2252,116 @@ hipError_t launch_update(int bits, const UpdateArgs &a, hipStream_t s) {
     return narrow ? update_f<F8<2>>(a, s) : update_f<F8<4>>(a, s);
 }
 
+// ---------------------------------------------------------------- direct decode of a few rows
+// wanted row j = XOR over the present rows i of D[j][i] * row i (kernels.hpp
+// DecodeRowsArgs, gf_host.hpp decode_coefficients): k_update's shape
+// transposed.  A stream: every present byte is read once, every wanted byte
+// written once, nothing is shared between lanes.
+namespace {
+
+constexpr int kDecRows = 4;  // present rows whose loads a lane keeps in flight
+
+// NT wanted rows [j0, j0 + NT) of the call's t; PTR: rows through a.rows (one
+// stripe), else strided rows of stripe blockIdx.y + y0.  The masks of a present
+// unit are prepared once and shared by the NT products; the tables are
+// wave-uniform scalar loads.  All addresses are 64-bit (row pointer + offset).
+template <class F, int NT, bool PTR>
+__global__ void __launch_bounds__(256, 2) k_decode_rows(DecodeRowsArgs a, int j0, int y0) {
+    typedef typename F::Vec V;
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    uint8_t *sb = nullptr;
+    if constexpr (!PTR) sb = a.base + ((uint64_t)blockIdx.y + (uint64_t)y0) * a.stripe_stride;
+    auto srow = [&](int i) -> const uint8_t * {
+        if constexpr (PTR) return upd_row(a.rows, i);
+        else return sb + (uint64_t)((upd_cint_t *)a.src_idx)[i] * a.row_stride;
+    };
+    auto drow = [&](int j) -> uint8_t * {
+        if constexpr (PTR) return upd_row(a.rows, a.np + j);
+        else return sb + (uint64_t)((upd_cint_t *)a.dst_idx)[j] * a.row_stride;
+    };
+    V acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; j++) acc[j] = F::zero();
+    const uint64_t trow = (uint64_t)a.np * F::TWD;  // table (j0 + j, i) at tw + (j * np + i) * TWD
+    const uint32_t *tw = a.tw + (uint64_t)j0 * trow;
+    int i = 0;
+    for (; i + kDecRows <= a.np; i += kDecRows) {
+        V x[kDecRows];
+#pragma unroll
+        for (int q = 0; q < kDecRows; q++) x[q] = F::load(srow(i + q), u);
+#pragma unroll
+        for (int q = 0; q < kDecRows; q++) {
+            UpdMasks<F> mk;
+            mk.prepare(x[q]);
+#pragma unroll
+            for (int j = 0; j < NT; j++) {
+                const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)(i + q) * F::TWD);
+                mk.mul_add(acc[j], tb.v);
+            }
+        }
+    }
+    for (; i < a.np; i++) {
+        UpdMasks<F> mk;
+        mk.prepare(F::load(srow(i), u));
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)i * F::TWD);
+            mk.mul_add(acc[j], tb.v);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NT; j++) F::store(drow(j0 + j), u, acc[j]);
+}
+
+template <class F, int NT>
+hipError_t decode_group(const DecodeRowsArgs &a, int j0, hipStream_t s) {
+    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
+    if (a.rows) {
+        hipLaunchKernelGGL((k_decode_rows<F, NT, true>), grid_x(units), dim3(256), 0, s, a, j0, 0);
+        return hipGetLastError();
+    }
+    return for_y(a.nstripes, [&](int y0, int ny) {
+        hipLaunchKernelGGL((k_decode_rows<F, NT, false>), dim3(grid_x(units).x, ny), dim3(256), 0, s, a, j0, y0);
+    });
+}
+
+template <class F>
+hipError_t decode_rows_f(const DecodeRowsArgs &a, hipStream_t s) {
+    static_assert(kDecGroup == 8, "decode_rows_f dispatches group sizes 1..8");
+    // ceil(t / kDecGroup) launches of sizes as equal as t allows (as update_f):
+    // every launch reads all present rows, so none should carry a lone row
+    const int nl = (a.t + kDecGroup - 1) / kDecGroup;
+    for (int g = 0, j0 = 0, nt = 0; g < nl; g++, j0 += nt) {
+        nt = a.t / nl + (g < a.t % nl ? 1 : 0);
+        hipError_t e;
+        switch (nt) {
+            case 1: e = decode_group<F, 1>(a, j0, s); break;
+            case 2: e = decode_group<F, 2>(a, j0, s); break;
+            case 3: e = decode_group<F, 3>(a, j0, s); break;
+            case 4: e = decode_group<F, 4>(a, j0, s); break;
+            case 5: e = decode_group<F, 5>(a, j0, s); break;
+            case 6: e = decode_group<F, 6>(a, j0, s); break;
+            case 7: e = decode_group<F, 7>(a, j0, s); break;
+            default: e = decode_group<F, 8>(a, j0, s); break;
+        }
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace
+
+// Unit widths by launch_update's grid rule.
+hipError_t launch_decode_rows(int bits, const DecodeRowsArgs &a, hipStream_t s) {
+    constexpr uint64_t kDecMinBlocks = 1024;
+    if (a.np <= 0 || a.t <= 0 || a.S == 0 || a.S % 64 || !a.tw) return hipErrorInvalidValue;
+    if (!a.rows && (!a.base || !a.src_idx || !a.dst_idx || a.nstripes <= 0)) return hipErrorInvalidValue;
+    const uint64_t ns = a.rows ? 1 : (uint64_t)a.nstripes;
+    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * ns;
+    const bool narrow = pick_narrow(wide_blocks < kDecMinBlocks);
+    if (bits == 16) return narrow ? decode_rows_f<F16<2>>(a, s) : decode_rows_f<F16<4>>(a, s);
+    return narrow ? decode_rows_f<F8<2>>(a, s) : decode_rows_f<F8<4>>(a, s);
+}
+
 }  // namespace rs

@@ -221,4 +221,27 @@ struct UpdateArgs {
 hipError_t launch_update(int bits, const UpdateArgs &a, hipStream_t s);
 
 
+// ---- Direct decode of a few rows: wanted row j = sum over the present rows i
+// of D[j][i] * row i (gf_host.hpp decode_coefficients), the transpose of the
+// update's shape: every present row is read once, the outputs of a launch stay
+// in registers and are stored once.  One lane owns one unit of one column of
+// every row; grid.y = stripe.
+constexpr int kDecGroup = 8;  // wanted rows per launch (k_decode_rows's NT)
+struct DecodeRowsArgs {
+    // pointer form (rows != nullptr): a device array of np present rows
+    // (ascending shard index), then t output rows; one stripe
+    uint8_t *const *rows;
+    // strided form: shard i of stripe z at base + z*stripe_stride + i*row_stride;
+    // src_idx: np present shard indices, dst_idx: t wanted ones (device arrays)
+    uint8_t *base;
+    uint64_t row_stride, stripe_stride;
+    const int *src_idx, *dst_idx;
+    const uint32_t *tw;  // t x np tables, (j, i) at (j*np + i) * tw_dwords (make_decode_tables)
+    uint64_t S;
+    int np, t, nstripes;
+};
+// Runs the t wanted rows as ceil(t / kDecGroup) launches on s.
+hipError_t launch_decode_rows(int bits, const DecodeRowsArgs &a, hipStream_t s);
+
+
 }  // namespace rs

@@ -127,11 +127,11 @@ rs_codec *multi_part(Multi *m, int g, int *device) {
 }
 
 int multi_host(Multi *m, rs_codec *parent, HostOp op, uint8_t *const *shards, uint64_t S,
-               const std::vector<uint8_t> &present, bool recover_all, int *ok, uint64_t *ticket) {
+               const std::vector<uint8_t> &present, Want want, int *ok, uint64_t *ticket) {
     const int n = (int)m->parts.size(), total = rs_total_shards(parent);
     ElExt el;
     if (op == HostOp::Reconstruct)  // once for every part, keyed on the full shard size
-        if (int e = parent_error_locators(parent, present, recover_all, S, el)) return e;
+        if (int e = parent_error_locators(parent, present, want, S, el)) return e;
     std::vector<std::vector<uint8_t *>> rows(n);
     std::vector<uint64_t> sub(n, 0);
     std::vector<int> oks(n, 1), active;
@@ -145,7 +145,7 @@ int multi_host(Multi *m, rs_codec *parent, HostOp op, uint8_t *const *shards, ui
         const uint64_t w = hi - lo;
         active.push_back(g);
         fut.push_back(m->workers[g]->submit([&, g, w] {
-            return part_host_call(m->parts[g], op, rows[g].data(), w, present, recover_all,
+            return part_host_call(m->parts[g], op, rows[g].data(), w, present, want,
                                   op == HostOp::Verify ? &oks[g] : nullptr, ticket ? &sub[g] : nullptr,
                                   op == HostOp::Reconstruct ? &el : nullptr);
         }));

@@ -27,13 +27,24 @@ struct ElExt {
     bool ref = false;
 };
 
+// Which missing rows a reconstruct rebuilds: all of them (Reconstruct, true),
+// the data rows (ReconstructData, false), or those flagged in `rows` (k+p
+// flags, rs_reconstruct_rows*: always with the pattern's exact locators).
+struct Want {
+    bool all = true;
+    const std::vector<uint8_t> *rows = nullptr;
+    Want(bool recover_all) : all(recover_all) {}
+    explicit Want(const std::vector<uint8_t> &required) : rows(&required) {}
+    bool has(int i, int k) const { return rows ? (*rows)[i] != 0 : all || i < k; }
+};
+
 // codec.cpp: one part's share of a host-resident call.  The parent has
 // validated the call; `shards` point at the part's byte range of every row.
 int part_host_call(rs_codec *part, HostOp op, uint8_t *const *shards, uint64_t S, const std::vector<uint8_t> &present,
-                   bool recover_all, int *ok, uint64_t *ticket, const ElExt *el);
+                   Want want, int *ok, uint64_t *ticket, const ElExt *el);
 // codec.cpp: the parent's locators for a reconstruct of the FULL shard size S
 // (the reference's useBits depends on it, leopard8.go:475), from its caches.
-int parent_error_locators(rs_codec *parent, const std::vector<uint8_t> &present, bool recover_all, uint64_t S,
+int parent_error_locators(rs_codec *parent, const std::vector<uint8_t> &present, Want want, uint64_t S,
                           ElExt &out);
 
 // [lo, hi) of shard bytes owned by part g of n: 64-byte blocks dealt as evenly
@@ -48,7 +59,7 @@ rs_codec *multi_part(Multi *m, int g, int *device);
 // Host-resident encode / verify / reconstruct over the parts (the parent's
 // mutex is held by the caller).  ticket != nullptr: asynchronous.
 int multi_host(Multi *m, rs_codec *parent, HostOp op, uint8_t *const *shards, uint64_t S,
-               const std::vector<uint8_t> &present, bool recover_all, int *ok, uint64_t *ticket);
+               const std::vector<uint8_t> &present, Want want, int *ok, uint64_t *ticket);
 int multi_ticket_wait(Multi *m, uint64_t ticket);
 int multi_ticket_query(Multi *m, uint64_t ticket, int *done);
 int multi_verify_result(Multi *m, uint64_t ticket, int *ok);

@@ -361,6 +361,66 @@ int rs_update_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, siz
                         const int *idx, int nidx, const uint8_t *d_new, size_t new_row_stride,
                         size_t new_stripe_stride, size_t shard_size, void *stream);
 
+/* ---------------- Scrub (beyond the reference) ----------------
+ * The reference's Verify returns one bool per stripe (leopard16.go:361-387) and
+ * nothing says which shard of a bad stripe is wrong.  The code is linear, so
+ * the answer is cheap.  With G the p x k generator (rs_debug_generator), P the
+ * stored parity and P' the parity recomputed from the stored data rows, the
+ * syndrome rows are e_i = P_i ^ P'_i.  If only data shard j is wrong, by a
+ * difference D, then e_i = G[i][j] * D for every i: every parity row differs
+ * wherever D != 0, at any such symbol e_1 / e_0 = G[1][j] / G[0][j] names j (the
+ * k ratios of an MDS code's generator are distinct), and D = e_0 / G[0][j].  If
+ * only parity shard k+i is wrong, exactly syndrome row i is non-zero.
+ *
+ * What a verdict means: RS_SCRUB_CLEAN: the parity matches.  s >= 0: replacing
+ * shard s alone, by the content the call computed, makes the stripe verify;
+ * the code has distance p + 1, so s is the true culprit whenever fewer than p
+ * shards are corrupt.  RS_SCRUB_UNLOCATED: corrupt, and no single shard
+ * explains it (always the case when p == 1).  A data verdict is never taken
+ * from the ratio alone: the candidate's repaired row is built and the stripe
+ * verified with it in place, so a wrong guess can only become "not located",
+ * never a wrong shard.
+ *
+ * The three calls are for device rows on a single-device codec and return
+ * after their work is complete (their results are read back), ordered on the
+ * caller's stream (NULL: the codec's; RS_NULL_STREAM: the null stream).
+ * Errors follow rs_verify_dev / rs_verify_dev_batch, in this order, all decided
+ * before any device call: NULL codec or arguments (nbad may be NULL), a
+ * multi-device codec, NULL rows -> RS_ERR_INVALID_ARG; shard_size == 0 ->
+ * RS_ERR_SHARD_NO_DATA; shard_size % 64 -> RS_ERR_INVALID_SHARD_SIZE;
+ * row_stride < shard_size -> RS_ERR_INVALID_ARG; RS_ERR_PANIC where the
+ * reference's encode of the geometry panics.  No existing call changes. */
+#define RS_SCRUB_CLEAN     (-1)  /* parity matches */
+#define RS_SCRUB_UNLOCATED (-2)  /* corrupt, and no single shard explains it (always the case when p == 1) */
+
+/* Verify of rs_verify_dev_batch, one verdict per stripe, in the same launches
+ * (each stripe sets a word of its own; one memset before, one copy after):
+ * bad[z] = 1 iff stripe z's parity does not match its data, else 0.  bad: host,
+ * nstripes bytes; *nbad: the number of bad stripes. */
+int rs_verify_dev_batch_map(rs_codec *codec, uint8_t *d_base, size_t row_stride, size_t stripe_stride, int nstripes,
+                            size_t shard_size, uint8_t *bad, int *nbad, void *stream);
+
+/* One stripe, row pointers (rs_verify_dev's arguments): *verdict = RS_SCRUB_CLEAN,
+ * the index in [0, k+p) of the one shard whose replacement makes the stripe a
+ * codeword, or RS_SCRUB_UNLOCATED.  repair != 0: that shard is overwritten with
+ * its right content; no other byte is written.  Work: one encode into scratch
+ * rows, one streaming scan of the 2 p parity rows; for a data shard also a
+ * three-row streaming kernel that builds the repaired row and one verify. */
+int rs_locate_dev(rs_codec *codec, uint8_t *const *d_shards, size_t shard_size, int repair, int *verdict, void *stream);
+
+/* The map, then the locate (and repair) of every bad stripe, one stripe at a
+ * time.  verdict: host, nstripes int32; *nbad: the number of bad stripes,
+ * located or not.
+ * Measured on one MI355X at 128+32 x 1 MiB, 256 stripes (profiles/scrub_c3.txt,
+ * DESIGN.md 4.12), ms per call: rs_verify_dev_batch 7.27 (the parent commit's
+ * 7.27; the two differ by less than their 0.4 % pass-to-pass spread),
+ * rs_verify_dev_batch_map 7.31-7.32 (+0.5 % in every run); this call on a clean slab is the
+ * map; with one corrupt data shard among the 256 stripes 7.58 (locate) and 7.60
+ * (locate and repair), where finding the stripe alone by re-verifying
+ * sub-ranges costs 8 further rs_verify_dev_batch calls, 7.69 ms. */
+int rs_scrub_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, size_t stripe_stride, int nstripes,
+                       size_t shard_size, int repair, int32_t *verdict, int *nbad, void *stream);
+
 /* ---------------- Host-only diagnostics (no device calls; used by CPU tests) ---------------- */
 /* Field tables as built by the engine (initLUTs/initFFTSkew, leopard16.go:940-1031). */
 int rs_debug_field_tables(int field_bits, uint16_t *log_out, uint16_t *exp_out, uint16_t *skew_out,
@@ -391,6 +451,15 @@ int rs_debug_generator(int field_bits, int data_shards, int parity_shards, int i
  * reference's reconstruct panics. */
 int rs_debug_decode_coefficients(int field_bits, int data_shards, int parity_shards, const uint8_t *present, int row,
                                  uint32_t *out /* k+p symbols */);
+/* The scrub's ratio lookup: *shard = the data shard j with G[1][j] / G[0][j] == e1 / e0
+ * (e0, e1: the syndrome symbols of parity rows 0 and 1 at one position), or -1
+ * when no column has that ratio, a symbol is zero, or p < 2; *scale = 1 / G[0][j]
+ * (scale * e0 is the shard's difference at that position), 0 with -1.  The map
+ * takes rows 0 and 1 of G from the decode map of "every parity shard erased",
+ * O(n log n).  RS_ERR_INVALID_ARG for bad arguments, RS_ERR_PANIC where the
+ * reference's encode panics. */
+int rs_debug_locate(int field_bits, int data_shards, int parity_shards, uint32_t e0, uint32_t e1, int *shard,
+                    uint32_t *scale);
 
 /* Checks the half-wave split schedules of the GF(2^16) encode kernel
  * (logm 2..5) against the plain butterfly order on random symbols and

@@ -25,6 +25,8 @@ from .codec import (  # noqa: F401
     ErrDevice,
     alloc_pinned,
     EmptyShard,
+    SCRUB_CLEAN,
+    SCRUB_UNLOCATED,
 )
 from ._capi import LIB_PATH, lib  # noqa: F401
 
@@ -32,5 +34,5 @@ __all__ = [
     "New", "New8", "New16", "ReedSolomon", "RSError", "ErrInvShardNum", "ErrMaxShardNum", "ErrTooFewShards",
     "ErrShardNoData", "ErrShardSize", "ErrInvalidShardSize", "ErrNotSupported", "ErrShortData",
     "ErrReconstructRequired", "ErrNilWriter", "ErrSize", "ErrPanic", "ErrDevice", "LIB_PATH", "lib", "alloc_pinned",
-    "EmptyShard",
+    "EmptyShard", "SCRUB_CLEAN", "SCRUB_UNLOCATED",
 ]

@@ -223,6 +223,7 @@ def _dev_rows_opt(rows, count: int):
 
 
 RS_NULL_STREAM = C.c_void_p(-1).value  # include/rs_mi355x.h: HIP's null stream, asynchronous
+SCRUB_CLEAN, SCRUB_UNLOCATED = -1, -2  # include/rs_mi355x.h RS_SCRUB_*: verdicts of locate_dev / scrub_dev_batch
 
 
 def _stream_handle(stream):
@@ -830,6 +831,48 @@ class ReedSolomon:
         arr = (C.c_int * max(len(idx), 1))(*idx)
         _check(self._L.rs_update_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, arr, len(idx),
                                            new.data_ptr(), new.stride(1), new.stride(0), S, _stream_handle(stream)))
+
+    # ---------------- scrub (beyond the reference: its Verify returns one bool;
+    # the encode is GF-linear, so the syndrome names a single corrupt shard)
+    def _slab(self, slab):
+        if slab.dim() != 3 or slab.shape[1] != self.total_shards():
+            raise TypeError("slab must be a [nstripes, k+p, S] uint8 CUDA tensor")
+        if not slab.is_cuda or slab.dtype.itemsize != 1 or slab.stride(2) != 1:
+            raise TypeError("slab rows must be contiguous uint8 on a CUDA device")
+        n, _, S = slab.shape
+        return n, S
+
+    def verify_dev_batch_map(self, slab, stream=None) -> np.ndarray:
+        """verify_dev_batch with one verdict per stripe, in the same launches
+        (rs_verify_dev_batch_map): a bool array, True where a stripe's parity
+        does not match its data."""
+        n, S = self._slab(slab)
+        bad = np.zeros(max(n, 1), np.uint8)
+        nbad = C.c_int(0)
+        _check(self._L.rs_verify_dev_batch_map(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, S,
+                                               bad.ctypes.data, C.byref(nbad), _stream_handle(stream)))
+        return bad[:n].astype(bool)
+
+    def locate_dev(self, rows, repair: bool = False, stream=None) -> int:
+        """Which shard of one stripe is corrupt (rs_locate_dev): SCRUB_CLEAN (-1),
+        the index of the one shard whose replacement makes the stripe verify,
+        or SCRUB_UNLOCATED (-2).  repair: that shard is overwritten with its
+        right content; no other byte is written."""
+        ptrs, S = _dev_rows(rows, self.total_shards())
+        v = C.c_int(SCRUB_UNLOCATED)
+        _check(self._L.rs_locate_dev(self._h, ptrs, S, int(bool(repair)), C.byref(v), _stream_handle(stream)))
+        return int(v.value)
+
+    def scrub_dev_batch(self, slab, repair: bool = False, stream=None) -> np.ndarray:
+        """The per-stripe verify of a [nstripes, k+p, S] slab, then locate_dev
+        (and the repair) of every bad stripe (rs_scrub_dev_batch): an int32
+        array of verdicts, one per stripe."""
+        n, S = self._slab(slab)
+        verdict = np.full(max(n, 1), SCRUB_UNLOCATED, np.int32)
+        nbad = C.c_int(0)
+        _check(self._L.rs_scrub_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, S,
+                                          int(bool(repair)), verdict.ctypes.data, C.byref(nbad), _stream_handle(stream)))
+        return verdict[:n]
 
 
 class EncodeTicket:

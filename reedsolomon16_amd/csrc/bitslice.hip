@@ -152,7 +152,11 @@ __device__ __forceinline__ void hp_get(uint32_t lbase, int row, Half &v) {
 // (vmcnt(0)) and so would drain the next chunk's prefetch at the first
 // barrier of every chunk; this waits for LDS traffic alone.
 
-template <int LOGM, bool VERIFY>
+// MAP (verify only): one mismatch word per stripe (BsArgs::mismatch_stride).  An
+// instantiation of its own: with the stride in the one verify kernel,
+// rs_verify_dev_batch measured 0.5 % slower at C3 than the kernel without it
+// (profiles/scrub_c3.txt), outside that session's 0.37 % pass-to-pass spread.
+template <int LOGM, bool VERIFY, bool MAP = false>
 struct HpEncoder {
     using TW = HpTab<LOGM>;
     static constexpr int M = 1 << LOGM;
@@ -382,9 +386,12 @@ struct HpEncoder {
                 const uint64_t m = __ballot(bad != 0);
                 // a set flag stays set: skip the store (a failing verify would
                 // otherwise store once per wave per tile into one contended word)
+                int *flag = a.mismatch;
+                // (cur.stripe changes between the tiles of one workgroup)
+                if constexpr (MAP) flag += (uint64_t)cur.stripe * a.mismatch_stride;
                 if (m && lane == __ffsll((unsigned long long)m) - 1 &&
-                    __hip_atomic_load(a.mismatch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-                    __hip_atomic_store(a.mismatch, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
+                    __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             cur = nxt;
         }
@@ -394,10 +401,10 @@ struct HpEncoder {
 // Workgroups per CU: LDS m x 2 KB and the register budget above.
 template <int LOGM> constexpr int kHpWgPerCu = LOGM == 5 ? 2 : 4;
 
-template <int LOGM, bool VERIFY>
+template <int LOGM, bool VERIFY, bool MAP = false>
 __global__ void __launch_bounds__(256, kHpWgPerCu<LOGM>) k_encode_hp(BsArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[(1 << LOGM) * 512];  // m rows x 2 KB
-    HpEncoder<LOGM, VERIFY> e{a};
+    HpEncoder<LOGM, VERIFY, MAP> e{a};
     e.lane = threadIdx.x & 63;
     e.w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     e.h = e.lane >> 5;
@@ -501,7 +508,7 @@ hipError_t launch_hp_t(bool verify, BsArgs a, int cus, hipStream_t s) {
         tpw = (a.ntiles >= 224 * slots || (a.tiles_per_stripe <= 256 && a.ntiles >= 32 * slots)) ? HpTuner::kMany : 1;
         int dev = 0;
         if (tpw > 1 && hp_tune_enabled() && hipGetDevice(&dev) == hipSuccess)
-            tpw = g_hp_tuner.choose({dev, LOGM, verify ? 1 : 0, a.ntiles, a.tiles_per_stripe, (int64_t)a.row_stride,
+            tpw = g_hp_tuner.choose({dev, LOGM, verify ? (a.mismatch_stride ? 2 : 1) : 0, a.ntiles, a.tiles_per_stripe, (int64_t)a.row_stride,
                                      a.nstripes > 1 ? (int64_t)a.stripe_stride : 0, (int64_t)a.S},
                                     &e0, &e1);
     }
@@ -514,7 +521,8 @@ hipError_t launch_hp_t(bool verify, BsArgs a, int cus, hipStream_t s) {
     a.tpw = tpw;
     a.tile_step = step;
     if (e0) (void)hipEventRecord(e0, s);
-    if (verify) hipLaunchKernelGGL((k_encode_hp<LOGM, true>), dim3(grid), dim3(256), 0, s, a);
+    if (verify && a.mismatch_stride) hipLaunchKernelGGL((k_encode_hp<LOGM, true, true>), dim3(grid), dim3(256), 0, s, a);
+    else if (verify) hipLaunchKernelGGL((k_encode_hp<LOGM, true>), dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_encode_hp<LOGM, false>), dim3(grid), dim3(256), 0, s, a);
     const hipError_t le = hipGetLastError();
     if (e1) (void)hipEventRecord(e1, s);

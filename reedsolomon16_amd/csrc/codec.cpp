@@ -299,6 +299,17 @@ struct rs_codec {
     Lru<std::vector<int>, std::unique_ptr<UpdPlan>, 16> uplan_cache;
     // direct-decode tables keyed by (erasure pattern, rows rebuilt), likewise
     Lru<std::vector<uint8_t>, std::unique_ptr<RowsPlan>, 16> rowsplan_cache;
+    // scrub (rs_verify_dev_batch_map / rs_locate_dev / rs_scrub_dev_batch): the
+    // ratio map of the data shards (built on the first locate), the device
+    // tables of a repaired row keyed by its data shard (UpdPlan::tw: the three
+    // make_repair_tables images), p + 1 scratch rows (the recomputed parity and
+    // the repaired row), and the per-stripe flags / scan results with their
+    // pinned readback.  The buffers are codec scratch (scratch_acquire / _release).
+    bool locate_built = false;
+    LocateMap locate_map;
+    Lru<int, std::unique_ptr<UpdPlan>, 16> fixplan_cache;
+    DevBuf<uint8_t> scrub_rows, scrub_dev;
+    PinnedBuf scrub_host;
 
     // error-locator cache keyed by erasure pattern (bounded LRU)
     Lru<std::vector<uint8_t>, std::vector<uint32_t>, 64> el_cache;
@@ -353,6 +364,9 @@ struct rs_codec {
         dplan_cache.items.clear();  // each plan waits for its last launch
         uplan_cache.items.clear();
         rowsplan_cache.items.clear();
+        fixplan_cache.items.clear();
+        scrub_rows.release(); scrub_dev.release();
+        scrub_host.release();
         for (int i = 0; i < kRing; i++)
             if (ring_ev[i]) {
                 (void)hipEventSynchronize(ring_ev[i]);
@@ -750,7 +764,7 @@ int encode_multipass(rs_codec *c, RowSet data, RowSet par, uint64_t S, int *mism
 // The arguments the register, split and LDS encode kernels share (the split
 // kernel swaps in its own tables, the LDS kernel adds its subfield tables).
 EncodeArgs encode_args(const rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t stripe_stride, int nstripes,
-                       int *mismatch) {
+                       int *mismatch, int mismatch_stride) {
     EncodeArgs a{};
     a.data = data;
     a.parity = par;
@@ -763,14 +777,17 @@ EncodeArgs encode_args(const rs_codec *c, RowSet data, RowSet par, uint64_t S, u
     a.tw_ifft = c->tw_ifft.p;
     a.tw_fft = c->tw_fft.p;
     a.mismatch = mismatch;
+    a.mismatch_stride = mismatch_stride;
     return a;
 }
 
+// mismatch != nullptr: verify.  mismatch_stride: ints per stripe between the
+// stripes' mismatch words (kernels.hpp EncodeArgs), 0: one word for all.
 int encode_device(rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t stripe_stride, int nstripes,
-                  int *mismatch, hipStream_t s) {
+                  int *mismatch, hipStream_t s, int mismatch_stride = 0) {
     if (!c->enc_ok) return RS_ERR_PANIC;
     if (c->logm <= kMaxRegLogM) {
-        EncodeArgs a = encode_args(c, data, par, S, stripe_stride, nstripes, mismatch);
+        EncodeArgs a = encode_args(c, data, par, S, stripe_stride, nstripes, mismatch, mismatch_stride);
         // bit-sliced kernel: strided rows, one row stride for data and parity
         const uint64_t span = (uint64_t)(c->k - 1) * data.stride + S;
         if (c->bs_ok && !data.table && !par.table && data.stride == par.stride && data.stride >= S &&
@@ -785,6 +802,7 @@ int encode_device(rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t str
             b.p = c->p;
             b.nstripes = nstripes;
             b.mismatch = mismatch;
+            b.mismatch_stride = mismatch_stride;
             if (!c->cus) HIP_TRY(hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, c->device));
             HIP_TRY(launch_encode_bs(mismatch != nullptr, b, c->cus, s));
             return RS_OK;
@@ -801,7 +819,7 @@ int encode_device(rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t str
     }
     if (enc_lds_ok(c)) {  // m rows of accumulator + chunk LDS-resident
         const bool tab = data.table || par.table;  // a row table describes one stripe
-        EncodeArgs a = encode_args(c, data, par, S, tab ? 0 : stripe_stride, tab ? 1 : nstripes, mismatch);
+        EncodeArgs a = encode_args(c, data, par, S, tab ? 0 : stripe_stride, tab ? 1 : nstripes, mismatch, mismatch_stride);
         if (c->fft_sub) {
             a.tw_fft_sub = c->tw_fft_sub.p;
             a.tw_dmap = c->tw_dmap.p;
@@ -817,7 +835,8 @@ int encode_device(rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t str
         RowSet d = data, p = par;
         if (!d.table) d.base += (size_t)j * stripe_stride;
         if (!p.table) p.base += (size_t)j * stripe_stride;
-        int e = encode_multipass(c, d, p, S, mismatch, s);
+        // the host loop over stripes moves the mismatch word
+        int e = encode_multipass(c, d, p, S, mismatch ? mismatch + (size_t)j * mismatch_stride : nullptr, s);
         if (e) return e;
     }
     return RS_OK;
@@ -1817,6 +1836,236 @@ int encode_dev_call(rs_codec *c, uint8_t *const *d, uint8_t *base, uint64_t row_
     return RS_OK;
 }
 
+// ---- Scrub (rs_verify_dev_batch_map / rs_locate_dev / rs_scrub_dev_batch; rs_mi355x.h)
+// scrub_dev: [first position, 8 bytes][rowbad, p ints] then, 256-aligned, one
+// mismatch int per stripe; scrub_host mirrors the head, then four 64-byte
+// blocks (the syndrome symbols), then the stripes' ints.
+size_t scrub_head(const rs_codec *c) { return align256(8 + 4 * (size_t)c->p); }
+int scrub_buffers(rs_codec *c, int nstripes) {
+    const size_t head = scrub_head(c), flags = 4 * (size_t)nstripes;
+    if (int e = scratch_ensure(c, c->scrub_dev, head + flags)) return e;
+    if (head + 256 + flags > c->scrub_host.n) {
+        if (int e = scratch_host_wait(c)) return e;
+        HIP_TRY(c->scrub_host.ensure(head + 256 + flags));
+    }
+    return RS_OK;
+}
+
+// The verify of rs_verify_dev_batch with one mismatch word per stripe: the same
+// launches, the words cleared by one memset and read back by one copy.  Returns
+// with the stream drained; *flags: nstripes ints in pinned memory, non-zero = bad.
+int verify_map_device(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, int nstripes, uint64_t S,
+                      hipStream_t s, const int **flags) {
+    if (int e = scrub_buffers(c, nstripes)) return e;
+    int *dflags = (int *)(c->scrub_dev.p + scrub_head(c));
+    int *hflags = (int *)(c->scrub_host.p + scrub_head(c) + 256);
+    HIP_TRY(hipMemsetAsync(dflags, 0, 4 * (size_t)nstripes, s));
+    const RowSet data{nullptr, base, row_stride}, par{nullptr, base + (size_t)c->k * row_stride, row_stride};
+    if (int e = encode_device(c, data, par, S, stripe_stride, nstripes, dflags, s, 1)) return e;
+    HIP_TRY(hipMemcpyAsync(hflags, dflags, 4 * (size_t)nstripes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *flags = hflags;
+    return RS_OK;
+}
+
+// The common distance of rows[0..n) when they are equally spaced upwards, else 0.
+uint64_t common_stride(uint8_t *const *rows, int n) {
+    if (n < 2 || rows[1] <= rows[0]) return 0;
+    const uint64_t st = (uint64_t)(rows[1] - rows[0]);
+    for (int i = 2; i < n; i++)
+        if (rows[i] <= rows[i - 1] || (uint64_t)(rows[i] - rows[i - 1]) != st) return 0;
+    return st;
+}
+
+// Device tables of the repaired row of data shard j (make_repair_tables), cached.
+int fix_plan(rs_codec *c, int j, uint32_t scale, UpdPlan **out) {
+    if (auto *hit = c->fixplan_cache.find(j)) {
+        *out = hit->get();
+        return RS_OK;
+    }
+    std::vector<uint8_t> h((size_t)3 * c->twd * 4, 0);
+    make_repair_tables(*c->F, scale, (uint32_t *)h.data());
+    auto up = std::make_unique<UpdPlan>();
+    if (int e = upload(up->blob, h)) return e;
+    up->tw = (const uint32_t *)up->blob.p;
+    *out = c->fixplan_cache.put(j, std::move(up))->get();  // an eviction waits for that plan's last launch
+    return RS_OK;
+}
+
+// Locate (and repair) of one stripe whose rows are d[0..total), all on the
+// caller's stream s inside the caller's scratch_acquire / scratch_release:
+// recompute the parity into scratch rows, scan it against the stored parity,
+// classify; for a data candidate build the repaired row, confirm it with the
+// pointer-form verify, and only then name (and overwrite) the shard.  Returns
+// with every readback done; a repair copy may still be queued on s.
+int locate_stripe(rs_codec *c, uint8_t *const *d, uint64_t S, bool repair, hipStream_t s, int *verdict) {
+    const int k = c->k, p = c->p;
+    *verdict = RS_SCRUB_UNLOCATED;
+    if (int e = scrub_buffers(c, 0)) return e;
+    // scratch rows at the data rows' own stride where that keeps the bit-sliced
+    // kernel eligible (one stride for data and parity), else packed
+    uint64_t qs = S;
+    const uint64_t ds = common_stride(d, k);
+    if (c->bs_ok && ds >= S && ds <= 2 * S && encode_bs_fits(k, p, ds, S)) qs = ds;
+    if (int e = scratch_ensure(c, c->scrub_rows, (size_t)p * qs + S)) return e;
+    uint8_t *q = c->scrub_rows.p, *fix = q + (size_t)p * qs;
+    std::vector<uint8_t *> rows(d, d + c->total);
+    for (int i = 0; i < p; i++) rows[k + i] = q + (size_t)i * qs;
+    {
+        RowSet data, par;
+        if (int e = make_rowsets(c, rows.data(), s, data, par)) return e;
+        if (int e = encode_device(c, data, par, S, 0, 1, nullptr, s)) return e;
+    }
+    uint8_t *dev = c->scrub_dev.p, *host = c->scrub_host.p;
+    HIP_TRY(hipMemsetAsync(dev, 0xff, 8, s));
+    HIP_TRY(hipMemsetAsync(dev + 8, 0, 4 * (size_t)p, s));
+    ScanArgs sa{};
+    sa.S = S;
+    sa.p = p;
+    sa.first = (unsigned long long *)dev;
+    sa.rowbad = (int *)(dev + 8);
+    const uint64_t ps = common_stride(d + k, p);
+    int slot = -1;
+    if (p == 1 || ps) {
+        sa.stored = d[k];
+        sa.stored_stride = ps;
+        sa.fresh = q;
+        sa.fresh_stride = qs;
+    } else {
+        uint8_t *h = nullptr, *g = nullptr;
+        const size_t bytes = (size_t)2 * p * sizeof(void *);
+        if (int e = ring_acquire(c, bytes, slot, h, g)) return e;
+        uint8_t **rp = (uint8_t **)h;
+        for (int i = 0; i < p; i++) rp[i] = d[k + i], rp[p + i] = q + (size_t)i * qs;
+        HIP_TRY(hipMemcpyAsync(g, h, bytes, hipMemcpyHostToDevice, s));
+        sa.rows = (uint8_t *const *)g;
+    }
+    HIP_TRY(launch_syndrome_scan(c->bits, sa, s));
+    if (slot >= 0) {
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+    }
+    HIP_TRY(hipMemcpyAsync(host, dev, 8 + 4 * (size_t)p, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const volatile int *rowbad = (const volatile int *)(host + 8);
+    const uint64_t first = *(const volatile uint64_t *)host;
+    int nb = 0, bi = -1;
+    for (int i = 0; i < p; i++)
+        if (rowbad[i]) nb++, bi = i;
+    if (!nb) {
+        *verdict = RS_SCRUB_CLEAN;
+        return RS_OK;
+    }
+    if (p == 1) return RS_OK;  // one syndrome row cannot tell the shards apart
+    if (nb == 1) {
+        // data and the other parity rows form a codeword by construction
+        *verdict = k + bi;
+        if (repair) HIP_TRY(hipMemcpyAsync(d[k + bi], q + (size_t)bi * qs, S, hipMemcpyDeviceToDevice, s));
+        return RS_OK;
+    }
+    if (nb < p || first >= S) return RS_OK;  // a data shard's difference shows in every parity row
+    // the two syndrome symbols at the first differing position
+    const uint64_t blk = first & ~(uint64_t)63;
+    uint8_t *sym = host + scrub_head(c);
+    const uint8_t *from[4] = {d[k], q, d[k + 1], q + qs};
+    for (int i = 0; i < 4; i++) HIP_TRY(hipMemcpyAsync(sym + 64 * i, from[i] + blk, 64, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    auto symbol = [&](int i) -> uint32_t {
+        const volatile uint8_t *b = sym + 64 * i;
+        const int o = (int)(first & 63);
+        // GF(2^16): low bytes in [0, 32) of the block, high bytes in [32, 64)
+        return c->bits == 16 ? (uint32_t)b[o & 31] | (uint32_t)b[(o & 31) + 32] << 8 : b[o];
+    };
+    const uint32_t e0 = symbol(0) ^ symbol(1), e1 = symbol(2) ^ symbol(3);
+    if (!c->locate_built) {
+        make_locate_map(*c->F, k, p, c->locate_map);
+        c->locate_built = true;
+    }
+    uint32_t scale = 0;
+    const int j = locate_shard(*c->F, c->locate_map, e0, e1, &scale);
+    if (j < 0) return RS_OK;
+    // R = row_j ^ scale * (P_0 ^ P'_0) into the spare scratch row
+    UpdPlan *fp = nullptr;
+    if (int e = fix_plan(c, j, scale, &fp)) return e;
+    {
+        uint8_t *h = nullptr, *g = nullptr;
+        const size_t bytes = 4 * sizeof(void *);
+        if (int e = ring_acquire(c, bytes, slot, h, g)) return e;
+        uint8_t **rp = (uint8_t **)h;
+        rp[0] = d[j], rp[1] = d[k], rp[2] = q, rp[3] = fix;
+        HIP_TRY(hipMemcpyAsync(g, h, bytes, hipMemcpyHostToDevice, s));
+        DecodeRowsArgs a{};
+        a.rows = (uint8_t *const *)g;
+        a.tw = fp->tw;
+        a.S = S;
+        a.np = 3;
+        a.t = 1;
+        a.nstripes = 1;
+        HIP_TRY(launch_decode_rows(c->bits, a, s));
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+        HIP_TRY(fp->mark_used(s));
+    }
+    // never from the ratio alone: the stripe with R in place of row j must verify
+    std::copy(d, d + c->total, rows.begin());
+    rows[j] = fix;
+    {
+        RowSet data, par;
+        if (int e = make_rowsets(c, rows.data(), s, data, par)) return e;
+        HIP_TRY(hipMemsetAsync(c->dflag, 0, sizeof(int), s));
+        if (int e = encode_device(c, data, par, S, 0, 1, c->dflag, s)) return e;
+        HIP_TRY(hipMemcpyAsync(c->hflag, c->dflag, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (*(volatile int *)c->hflag != 0) return RS_OK;
+    *verdict = j;
+    if (repair) HIP_TRY(hipMemcpyAsync(d[j], fix, S, hipMemcpyDeviceToDevice, s));
+    return RS_OK;
+}
+
+// The three scrub calls after their argument checks.  d != nullptr: one stripe
+// by row pointers (verdict[0]); else the slab at `base`: the map (bad != nullptr:
+// one byte per stripe), then, with verdict != nullptr, the locate of each bad
+// stripe, one at a time.  Complete on return (the results are read back).
+int scrub_call(rs_codec *c, uint8_t *const *d, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, int nstripes,
+               uint64_t S, int repair, uint8_t *bad, int32_t *verdict, int *nbad, void *stream) {
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    if (int e = scratch_acquire(c, s)) return e;
+    int count = 0, err = RS_OK;
+    if (d) {
+        int v = RS_SCRUB_UNLOCATED;
+        err = locate_stripe(c, d, S, repair != 0, s, &v);
+        verdict[0] = v;
+    } else {
+        const int *flags = nullptr;
+        err = verify_map_device(c, base, row_stride, stripe_stride, nstripes, S, s, &flags);
+        std::vector<int> todo;
+        for (int z = 0; z < nstripes && !err; z++) {
+            const bool b = ((const volatile int *)flags)[z] != 0;
+            count += b;
+            if (bad) bad[z] = b;
+            if (verdict) verdict[z] = b ? RS_SCRUB_UNLOCATED : RS_SCRUB_CLEAN;
+            if (b && verdict) todo.push_back(z);
+        }
+        std::vector<uint8_t *> rows((size_t)c->total);
+        for (size_t t = 0; t < todo.size() && !err; t++) {
+            uint8_t *sb = base + (size_t)todo[t] * stripe_stride;
+            for (int i = 0; i < c->total; i++) rows[i] = sb + (size_t)i * row_stride;
+            int v = RS_SCRUB_UNLOCATED;
+            err = locate_stripe(c, rows.data(), S, repair != 0, s, &v);
+            // (the map said bad; a clean scan cannot follow on unchanged rows)
+            verdict[todo[t]] = v == RS_SCRUB_CLEAN ? RS_SCRUB_UNLOCATED : v;
+        }
+    }
+    if (int e = scratch_release(c, s)) return err ? err : e;
+    if (err) return err;
+    HIP_TRY(hipStreamSynchronize(s));  // a queued repair copy
+    if (nbad) *nbad = count;
+    return RS_OK;
+}
+
 // The rules rs_reconstruct_dev, rs_reconstruct_dev_batch and the host
 // reconstructs share (leopard16.go:390-430), on the shards marked present.
 // done: `return` is the call's result (an error, or RS_OK with nothing to rebuild).
@@ -2214,6 +2463,66 @@ int rs_verify_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t st
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
     if (row_stride < S) return RS_ERR_INVALID_ARG;
     return encode_dev_call(c, nullptr, base, row_stride, stripe_stride, nstripes, S, ok, stream);
+}
+
+// ---- Scrub (beyond the reference; rs_mi355x.h).  Every error is decided
+// before the first device call, by rs_verify_dev's / rs_verify_dev_batch's rules.
+int rs_verify_dev_batch_map(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, int nstripes, size_t S,
+                            uint8_t *bad, int *nbad, void *stream) {
+    if (!c || !base || !bad || nstripes <= 0) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    if (nbad) *nbad = 0;
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (row_stride < S) return RS_ERR_INVALID_ARG;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    return scrub_call(c, nullptr, base, row_stride, stripe_stride, nstripes, S, 0, bad, nullptr, nbad, stream);
+}
+
+int rs_locate_dev(rs_codec *c, uint8_t *const *d, size_t S, int repair, int *verdict, void *stream) {
+    if (!c || !d || !verdict) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    *verdict = RS_SCRUB_UNLOCATED;
+    for (int i = 0; i < c->total; i++)
+        if (!d[i]) return RS_ERR_INVALID_ARG;
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    int32_t v = RS_SCRUB_UNLOCATED;
+    const int e = scrub_call(c, d, nullptr, 0, 0, 1, S, repair, nullptr, &v, nullptr, stream);
+    if (!e) *verdict = v;
+    return e;
+}
+
+int rs_scrub_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, int nstripes, size_t S,
+                       int repair, int32_t *verdict, int *nbad, void *stream) {
+    if (!c || !base || !verdict || nstripes <= 0) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    if (nbad) *nbad = 0;
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (row_stride < S) return RS_ERR_INVALID_ARG;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    return scrub_call(c, nullptr, base, row_stride, stripe_stride, nstripes, S, repair, nullptr, verdict, nbad, stream);
+}
+
+int rs_debug_locate(int bits, int k, int p, uint32_t e0, uint32_t e1, int *shard, uint32_t *scale) {
+    if ((bits != 8 && bits != 16) || !shard || !scale || k <= 0 || p <= 0) return RS_ERR_INVALID_ARG;
+    *shard = -1;
+    *scale = 0;
+    // the last geometry's map is kept: a test asks many syndromes of one geometry
+    static std::mutex mu;
+    static int kb = 0, kk = 0, kp = 0;
+    static bool ok = false;
+    static LocateMap map;
+    std::lock_guard<std::mutex> lk(mu);
+    if (kb != bits || kk != k || kp != p) {
+        ok = make_locate_map(field(bits), k, p, map);
+        kb = bits, kk = k, kp = p;
+    }
+    if (!ok) return RS_ERR_PANIC;
+    *shard = locate_shard(field(bits), map, e0, e1, scale);
+    return RS_OK;
 }
 
 int rs_reconstruct_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,

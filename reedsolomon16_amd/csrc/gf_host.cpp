@@ -530,4 +530,69 @@ void make_decode_tables(const Field &F, int k, int p, const uint8_t *erased, con
     }
 }
 
+bool generator_rows(const Field &F, int k, int p, int nrows, std::vector<uint32_t> &rows) {
+    if (k <= 0 || p <= 0 || nrows < 0 || nrows > p) return false;
+    std::vector<uint32_t> il, fl, el;
+    if (!decode_schedule(F, k, p, il, fl)) return false;
+    std::vector<uint8_t> erased((size_t)k + p, 0);
+    std::fill(erased.begin() + k, erased.end(), (uint8_t)1);
+    if (!error_locators(F, k, p, erased.data(), el)) return false;
+    std::vector<uint32_t> co((size_t)k + p);
+    rows.assign((size_t)nrows * k, 0);
+    for (int i = 0; i < nrows; i++) {
+        decode_coefficients_from(F, k, p, erased.data(), el, il, fl, k + i, co.data());
+        std::copy(co.begin(), co.begin() + k, rows.begin() + (size_t)i * k);
+    }
+    return true;
+}
+
+bool make_locate_map(const Field &F, int k, int p, LocateMap &map) {
+    map.g0.clear();
+    map.by_ratio.clear();
+    if (k <= 0 || p <= 0) return false;
+    std::vector<uint32_t> il, fl;
+    int nchunks = 0;
+    if (!encode_schedule(F, k, p, il, fl, nchunks)) return false;
+    if (p < 2) return true;
+    std::vector<uint32_t> g;  // rows 0 and 1 of G
+    if (!generator_rows(F, k, p, 2, g)) return true;  // no decode schedule: nothing is located
+    map.g0.assign(g.begin(), g.begin() + k);
+    map.by_ratio.assign(F.order, -1);
+    for (int j = 0; j < k; j++) {
+        const uint32_t a = g[j], b = g[(size_t)k + j];
+        if (!a || !b) {
+            map.g0[j] = 0;
+            continue;
+        }
+        const uint32_t r = F.mul_log(b, F.sub_mod(0, F.log[a]));
+        int32_t &slot = map.by_ratio[r];
+        if (slot == -1) {
+            slot = j;
+        } else {  // a shared ratio names no shard: both columns leave the map
+            if (slot >= 0) map.g0[slot] = 0;
+            map.g0[j] = 0;
+            slot = -2;
+        }
+    }
+    for (int32_t &s : map.by_ratio)
+        if (s < 0) s = -1;
+    return true;
+}
+
+int locate_shard(const Field &F, const LocateMap &map, uint32_t e0, uint32_t e1, uint32_t *scale) {
+    if (scale) *scale = 0;
+    if (!e0 || !e1 || e0 >= F.order || e1 >= F.order || map.by_ratio.empty()) return -1;
+    const int j = map.by_ratio[F.mul_log(e1, F.sub_mod(0, F.log[e0]))];
+    if (j < 0 || !map.g0[j]) return -1;
+    if (scale) *scale = F.exp[F.sub_mod(0, F.log[map.g0[j]])];
+    return j;
+}
+
+void make_repair_tables(const Field &F, uint32_t scale, uint32_t *out) {
+    const int twd = tw_dwords(F.bits);
+    make_twiddle(F, 0, out, true);  // exp(0) = 1
+    make_twiddle(F, scale ? F.log[scale] : F.mod, out + twd, true);
+    make_twiddle(F, scale ? F.log[scale] : F.mod, out + 2 * twd, true);
+}
+
 }  // namespace rs

@@ -167,4 +167,34 @@ void make_decode_tables(const Field &F, int k, int p, const uint8_t *erased, con
                         const std::vector<uint32_t> &ifft_logs, const std::vector<uint32_t> &fft_logs, const int *rows,
                         int t, uint32_t *out);
 
+// ---- Scrub: which single data shard explains a syndrome.
+// Rows [0, nrows) of the encode's generator matrix: rows[i * k + j] = G[i][j].
+// With every data shard present and every parity shard erased, the decode map
+// of parity row i IS the encode's row i (both give the one codeword of the k
+// data symbols), so each row costs one decode_coefficients: O(n log n), where k
+// generator columns would cost O(k m log m).  False where the decode schedule
+// does not exist (m + k > field order) or nrows > p.
+bool generator_rows(const Field &F, int k, int p, int nrows, std::vector<uint32_t> &rows);
+// A corrupt data shard j (difference D) gives the syndrome rows e_i = G[i][j] * D,
+// so at a symbol with D != 0 the ratio e_1 / e_0 = G[1][j] / G[0][j] names j when
+// the k ratios are distinct.  g0[j] = G[0][j], or 0 for a column left out of the
+// map: one with a zero entry, or whose ratio another column shares (both are
+// left out: such shards come out "not located", never as the wrong shard).
+// by_ratio: `order` entries, the shard of each ratio or -1.  Empty when p < 2.
+struct LocateMap {
+    std::vector<uint32_t> g0;
+    std::vector<int32_t> by_ratio;
+};
+// False where the encode's schedule does not exist (encode_schedule).  Uses
+// generator_rows; where that fails (m + k > field order) the map stays empty
+// and nothing is located.
+bool make_locate_map(const Field &F, int k, int p, LocateMap &map);
+// The data shard whose ratio is e1 / e0, or -1; *scale = 1 / G[0][shard] (the
+// shard's difference at that symbol is *scale * e0), 0 with -1.
+int locate_shard(const Field &F, const LocateMap &map, uint32_t e0, uint32_t e1, uint32_t *scale);
+// The three tables (butterfly layout, tw_dwords each) of the repaired row
+// R = 1 * row_j ^ scale * P_0 ^ scale * P'_0, for k_decode_rows over those
+// three rows in that order.
+void make_repair_tables(const Field &F, uint32_t scale, uint32_t *out);
+
 }  // namespace rs

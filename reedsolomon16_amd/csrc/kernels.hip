@@ -660,7 +660,7 @@ __global__ void __launch_bounds__(256, 2) k_encode_reg(EncodeArgs a) {
 #pragma unroll
         for (int r = 0; r < M; r++)
             if (r < a.p) bad |= F::diff(acc[r], F::load(rowp<ROWTAB>(a.parity, r, soff), u));
-        flag_mismatch(a.mismatch, bad != 0);
+        flag_mismatch(a.mismatch + (uint64_t)blockIdx.y * a.mismatch_stride, bad != 0);
     } else {
 #pragma unroll
         for (int r = 0; r < M; r++)
@@ -872,7 +872,7 @@ __global__ void __launch_bounds__(256, 4) k_encode_split(EncodeArgs a) {
         }
     }
     if constexpr (VERIFY) {
-        flag_mismatch(a.mismatch, bad != 0);
+        flag_mismatch(a.mismatch + (uint64_t)blockIdx.y * a.mismatch_stride, bad != 0);
     }
 }
 
@@ -1726,7 +1726,7 @@ __global__ void __launch_bounds__((enc_threads<LOGM>()), (LOGM >= 9 ? 1 : 4)) k_
             lds_transform<FT, false, LOGM, LdsIO<FT, PK>, ParityOut, NoNeed, 1, 32, NT, false, PK>(cur, a.p, twf, NoNeed{}, LdsIO<FT, PK>{cur},
                                                                              ParityOut{a, soff, tile, uo, &bad});
         }
-        if constexpr (VERIFY) flag_mismatch(a.mismatch, bad != 0);
+        if constexpr (VERIFY) flag_mismatch(a.mismatch + (uint64_t)blockIdx.y * a.mismatch_stride, bad != 0);
         return;
     }
     for (int c = 0; c < a.nchunks; c++) {
@@ -1740,7 +1740,8 @@ __global__ void __launch_bounds__((enc_threads<LOGM>()), (LOGM >= 9 ? 1 : 4)) k_
     lds_transform<F, false, LOGM, LdsIO<F, PK>, ParityOut, NoNeed, 0, 32, NT, false, PK>(acc, a.p, a.tw_fft, NoNeed{}, LdsIO<F, PK>{acc},
                                                                     ParityOut{a, soff, tile, uo, &bad});
     if constexpr (VERIFY) {
-        flag_mismatch(a.mismatch, bad != 0);
+        // (the launch has no grid.y slices: blockIdx.y is the stripe)
+        flag_mismatch(a.mismatch + (uint64_t)blockIdx.y * a.mismatch_stride, bad != 0);
     }
 }
 
@@ -2362,6 +2363,104 @@ hipError_t launch_decode_rows(int bits, const DecodeRowsArgs &a, hipStream_t s) 
     const bool narrow = pick_narrow(wide_blocks < kDecMinBlocks);
     if (bits == 16) return narrow ? decode_rows_f<F16<2>>(a, s) : decode_rows_f<F16<4>>(a, s);
     return narrow ? decode_rows_f<F8<2>>(a, s) : decode_rows_f<F8<4>>(a, s);
+}
+
+// ---------------------------------------------------------------- syndrome scan (scrub)
+// Stored parity rows against freshly encoded ones (kernels.hpp ScanArgs):
+// k_update's shape without a product.  A stream: every byte of the 2 p rows is
+// read once, nothing is written into either set; per wave at most one flag
+// store per differing row and one 64-bit atomic minimum.
+namespace {
+
+constexpr int kScanRows = 4;  // parity rows whose two loads a lane keeps in flight (8 loads)
+
+template <class F>
+__device__ __forceinline__ void or_into(typename F::Vec &a, const typename F::Vec &b) {
+    if constexpr (F::SYM16) {
+#pragma unroll
+        for (int i = 0; i < F::W; i++) a.l[i] |= b.l[i], a.h[i] |= b.h[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < F::W; i++) a.b[i] |= b.b[i];
+    }
+}
+// Byte index, within the unit's 4 W (low) bytes, of the first symbol with a set
+// bit in m; 4 W when there is none.
+template <class F>
+__device__ __forceinline__ uint32_t first_symbol(const typename F::Vec &m) {
+    uint32_t r = 4 * F::W;
+#pragma unroll
+    for (int i = F::W - 1; i >= 0; i--) {
+        uint32_t w;
+        if constexpr (F::SYM16) w = m.l[i] | m.h[i];
+        else w = m.b[i];
+        if (w) r = 4 * i + ((uint32_t)__builtin_ctz(w) >> 3);
+    }
+    return r;
+}
+
+// PTR: rows through a.rows, else strided.  All addresses are 64-bit (row pointer + offset).
+template <class F, bool PTR>
+__global__ void __launch_bounds__(256) k_syndrome_scan(ScanArgs a) {
+    typedef typename F::Vec V;
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    auto srow = [&](int i) -> const uint8_t * {
+        if constexpr (PTR) return upd_row(a.rows, i);
+        else return a.stored + (uint64_t)i * a.stored_stride;
+    };
+    auto frow = [&](int i) -> const uint8_t * {
+        if constexpr (PTR) return upd_row(a.rows, a.p + i);
+        else return a.fresh + (uint64_t)i * a.fresh_stride;
+    };
+    V any = F::zero();
+    int i = 0;
+    for (; i + kScanRows <= a.p; i += kScanRows) {
+        V x[kScanRows], y[kScanRows];
+#pragma unroll
+        for (int q = 0; q < kScanRows; q++) {
+            x[q] = F::load(srow(i + q), u);
+            y[q] = F::load(frow(i + q), u);
+        }
+#pragma unroll
+        for (int q = 0; q < kScanRows; q++) {
+            F::xor_into(x[q], y[q]);
+            or_into<F>(any, x[q]);
+            flag_mismatch(a.rowbad + i + q, F::diff(x[q], F::zero()) != 0);
+        }
+    }
+    for (; i < a.p; i++) {
+        V x = F::load(srow(i), u);
+        F::xor_into(x, F::load(frow(i), u));
+        or_into<F>(any, x);
+        flag_mismatch(a.rowbad + i, F::diff(x, F::zero()) != 0);
+    }
+    // lanes own ascending units: the first lane that saw a difference holds the wave's minimum
+    const uint64_t m = __ballot(F::diff(any, F::zero()) != 0);
+    if (m && __lane_id() == (unsigned)(__ffsll((unsigned long long)m) - 1))
+        (void)__hip_atomic_fetch_min(a.first, (unsigned long long)(F::off(u) + first_symbol<F>(any)), __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <class F>
+hipError_t syndrome_scan_f(const ScanArgs &a, hipStream_t s) {
+    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
+    if (a.rows) hipLaunchKernelGGL((k_syndrome_scan<F, true>), grid_x(units), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_syndrome_scan<F, false>), grid_x(units), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+// Unit widths by launch_update's grid rule (one stripe).
+hipError_t launch_syndrome_scan(int bits, const ScanArgs &a, hipStream_t s) {
+    constexpr uint64_t kScanMinBlocks = 1024;
+    if (a.p <= 0 || a.S == 0 || a.S % 64 || !a.rowbad || !a.first) return hipErrorInvalidValue;
+    if (!a.rows && (!a.stored || !a.fresh)) return hipErrorInvalidValue;
+    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256;
+    const bool narrow = pick_narrow(wide_blocks < kScanMinBlocks);
+    if (bits == 16) return narrow ? syndrome_scan_f<F16<2>>(a, s) : syndrome_scan_f<F16<4>>(a, s);
+    return narrow ? syndrome_scan_f<F8<2>>(a, s) : syndrome_scan_f<F8<4>>(a, s);
 }
 
 }  // namespace rs

@@ -31,6 +31,9 @@ struct EncodeArgs {
     const uint32_t *tw_ifft;  // nchunks * ifft_slots(logm) twiddle tables
     const uint32_t *tw_fft;   // fft_slots(logm) twiddle tables
     int *mismatch;            // verify: set to 1 on any parity mismatch
+    // verify: ints between the mismatch words of consecutive stripes (stripe z
+    // sets mismatch[z * mismatch_stride]); 0: one word for the whole launch
+    int mismatch_stride;
     // Optional (GF(2^16), LDS kernel, even log m): the final FFT in subfield
     // coordinates.  Every fftDIT twiddle of an m <= 256 encode is fftSkew[< 255],
     // an element of GF(2^8) (leopard16.go:218-221), so the transform runs on
@@ -99,7 +102,8 @@ struct ZcRows {
 hipError_t launch_zc_copy(const ZcRows &r, uint8_t *slab, uint64_t pitch, uint64_t off, uint64_t w, bool to_host,
                           hipStream_t s);
 hipError_t launch_xor_rows(int bits, uint8_t *dst, const uint8_t *src, uint64_t S, int rows, hipStream_t s);
-// out.row(r) = work[r]  (verify: compare, set *mismatch)
+// out.row(r) = work[r]  (verify: compare, set *mismatch; one stripe per call, so
+// a per-stripe verify hands in that stripe's word)
 hipError_t launch_copy_out(int bits, RowSet out, const uint8_t *work, uint64_t S, int rows, int *mismatch,
                            hipStream_t s);
 // work[r] = src[r] ? src[r] * tw[r] : 0 for r in [0, rows); src: device array of row pointers
@@ -182,6 +186,7 @@ struct BsArgs {
     int tpw, tile_step;            // set by the launcher: tiles per workgroup, tile distance between them
     uint32_t span, pspan;          // set by the launcher: (k-1)*row_stride + S, (p-1)*row_stride + S
     int *mismatch;          // verify
+    int mismatch_stride;    // verify: ints per stripe between mismatch words, 0: one word (EncodeArgs)
 };
 // True when the tables cover (k, p) and agree with the geometry's own
 // schedule (encode_schedule: nchunks * ifft_slots(logm) IFFT logs, then
@@ -243,5 +248,24 @@ struct DecodeRowsArgs {
 // Runs the t wanted rows as ceil(t / kDecGroup) launches on s.
 hipError_t launch_decode_rows(int bits, const DecodeRowsArgs &a, hipStream_t s);
 
+
+// ---- Syndrome scan of one stripe (scrub): compares the p stored parity rows
+// with the p rows a fresh encode of the stored data gave, writes neither.
+// rowbad[i] = 1 when parity row i differs anywhere (cleared by the caller);
+// *first = min(*first, byte offset within a row of the first differing symbol
+// of the stripe: its low byte in GF(2^16), 32 below its high byte), the caller
+// presets it to all ones.  One lane owns one unit of one column of every row.
+struct ScanArgs {
+    // pointer form (rows != nullptr): a device array of the p stored rows, then the p fresh rows
+    uint8_t *const *rows;
+    // strided form: row i at stored + i*stored_stride and fresh + i*fresh_stride
+    const uint8_t *stored, *fresh;
+    uint64_t stored_stride, fresh_stride;
+    uint64_t S;
+    int p;
+    int *rowbad;
+    unsigned long long *first;
+};
+hipError_t launch_syndrome_scan(int bits, const ScanArgs &a, hipStream_t s);
 
 }  // namespace rs

@@ -237,6 +237,60 @@ int rs_reconstruct_dev(rs_codec *codec, uint8_t *const *d_shards, const uint8_t 
 int rs_reconstruct_dev_batch(rs_codec *codec, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
                              const uint8_t *present, size_t shard_size, int recover_all, void *stream);
 
+/* ---------------- One erasure pattern per stripe (beyond the reference) --------
+ * rs_reconstruct_dev_batch over the same slab, but stripe z uses the k+p flags
+ * at present + pattern_of[z]*(k+p): a store that rotates or hashes the shard
+ * order per object loses a different shard index (a rack: a different set of
+ * indices) in every stripe when a device goes.  present is a table of
+ * npatterns rows (1 .. 65536; equal rows and rows no stripe names are fine),
+ * pattern_of a HOST array of nstripes row numbers; both may be freed on return.
+ * Per stripe the result is what rs_reconstruct_dev_batch writes for that
+ * stripe alone with that pattern, with the exact locators of the pattern: like
+ * the rs_reconstruct_rows* calls this one neither reads nor stores the
+ * reference-keyed GF(2^8) inversion cache.  A stripe whose pattern has nothing
+ * to rebuild (nothing missing, or only parity with recover_all == 0) is not
+ * touched, and no byte outside the rebuilt rows is written.
+ * Errors, all decided before any device call, in this order: NULL codec /
+ * base / present / pattern_of, nstripes > INT32_MAX, a multi-device codec,
+ * npatterns == 0 or > 65536, a pattern_of[z] >= npatterns: RS_ERR_INVALID_ARG;
+ * shard_size == 0 or a table row with no shard present: RS_ERR_SHARD_NO_DATA;
+ * a table row (named by a stripe or not) with fewer than k present:
+ * RS_ERR_TOO_FEW_SHARDS; shard_size % 64: RS_ERR_INVALID_SHARD_SIZE; the
+ * stride rules of rs_reconstruct_dev_batch: RS_ERR_INVALID_ARG; a geometry
+ * whose reconstruct panics in the reference: RS_ERR_PANIC.  Then nstripes == 0
+ * or no stripe with anything to rebuild: RS_OK, nothing launched.
+ * Stream semantics of rs_reconstruct_dev_batch: stream-ordered, nothing waits
+ * for the kernel where the codec has an LDS-resident reconstruct (n <= 8192
+ * for GF(2^16), every GF(2^8) codec); larger codecs run stripe by stripe.
+ *
+ * One launch serves the slab.  The LDS-resident reconstruct (grid.y = stripe):
+ * every workgroup reads its stripe's descriptor index, then the descriptor
+ * (table pointers, output count, revealed-row mask) with scalar loads.  Codecs
+ * of the bit-sliced n = 256 decoder (128+32): that kernel, persistent over the
+ * tiles of the stripes with something to rebuild, each tile with its stripe's
+ * descriptor.
+ * Measured on one MI355X, us per stripe (profiles/patterns_c4.txt, DESIGN.md
+ * 4.13; a pass over the slab to a device synchronise, five alternating passes
+ * that agree within 1 %): 128+32 x 1 MiB, 256 stripes, shard order rotated per
+ * stripe, one device lost (160 patterns, one erasure each): this call 95.8
+ * (150.0 through the LDS-resident kernel), one rs_reconstruct_dev per stripe
+ * 307.6, one rs_reconstruct_dev_batch per pattern over a slab sorted by
+ * pattern 187.7, rs_reconstruct_dev_batch with one pattern for all 92.6; 32
+ * devices lost (32 erasures each): 108.3 (168.5) / 308.2 / 188.2 / 103.0.
+ * 1024+256 x 256 KiB, 8 stripes, 8 patterns of one erasure: 503.8 / 526.3 /
+ * 521.1 / 504.5; of 256 erasures: 523.1 / 547.6 / 542.0 / 510.2.
+ * The tables of the distinct patterns of a call that have something to
+ * rebuild live in one device blob, built on first use and cached per codec
+ * (4 sets, least recently used, keyed by recover_all and the patterns in order
+ * of first use); only the 4-byte index per stripe is uploaded per call.  Table
+ * bytes per pattern: 27392 (one erasure) to 30208 (32) at 128+32, 213760 to
+ * 238848 at 1024+256.  A call whose patterns need more than 64 MiB of tables,
+ * or with more than 2^18 stripes, runs as several launches over stripe ranges. */
+int rs_reconstruct_dev_batch_patterns(rs_codec *codec, uint8_t *base, size_t row_stride, size_t stripe_stride,
+                                      size_t nstripes, const uint8_t *present /* npatterns x (k+p) */,
+                                      size_t npatterns, const uint32_t *pattern_of /* nstripes, host */,
+                                      size_t shard_size, int recover_all, void *stream);
+
 /* ---------------- Selective reconstruct (beyond the reference) ----------------
  * The reference's ReconstructSome reads only len(required) (leopard16.go:343-348)
  * and rebuilds all missing shards or all missing data shards.  The three calls
@@ -508,7 +562,14 @@ int rs_debug_encode_bs_fits(int data_shards, int parity_shards, size_t row_strid
  *                     present rows in (bit 0) and the rebuilt rows out (bit 1) (default 3);
  *                     a cleared bit keeps that direction's per-run hipMemcpy copies,
  *   "rows_direct" -1/0/1  rs_reconstruct_rows_dev*: the direct decode kernel by the measured
- *                     threshold (-1, default), never (0), or always where n <= 2048 admits it (1).
+ *                     threshold (-1, default), never (0), or always where n <= 2048 admits it (1),
+ *   "pat_tier" 0/1/2  rs_reconstruct_dev_batch_patterns: the kernel that serves codecs of the
+ *                     bit-sliced n = 256 decoder (128+32): automatic (0, default: the decoder),
+ *                     the LDS-resident kernel with a descriptor per stripe (1), the bit-sliced
+ *                     decoder with a descriptor per tile (2); other codecs have the first only,
+ *   "bsdec_grid" >= 0 workgroups of the bit-sliced decoder's persistent grid: one per compute
+ *                     unit (0, default) or at most this many, so that a few small stripes make
+ *                     one workgroup walk from stripe to stripe.
  * Returns RS_ERR_INVALID_ARG for an unknown knob or value.  Host only. */
 int rs_debug_set_path(const char *knob, int value);
 

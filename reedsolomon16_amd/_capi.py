@@ -50,6 +50,7 @@ def lib() -> C.CDLL:
     L.rs_verify_dev.argtypes = [vp, P(vp), sz, P(i32), vp]
     L.rs_reconstruct_dev.argtypes = [vp, P(vp), P(C.c_uint8), sz, i32, vp]
     L.rs_reconstruct_dev_batch.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint8), sz, i32, vp]
+    L.rs_reconstruct_dev_batch_patterns.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint8), sz, P(C.c_uint32), sz, i32, vp]
     L.rs_reconstruct_rows_dev.argtypes = [vp, P(vp), P(C.c_uint8), P(C.c_uint8), sz, vp]
     L.rs_reconstruct_rows_dev_batch.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint8), P(C.c_uint8), sz, vp]
     L.rs_reconstruct_rows.argtypes = [vp, P(vp), P(sz), i32, P(C.c_uint8)]
@@ -96,7 +97,7 @@ def lib() -> C.CDLL:
     return L
 
 
-_PATH_DEFAULTS = {"bs": 1, "sub": 1, "prune": 1, "unit_width": -1, "hp_tiles": 0, "hp_step": 0, "zc": 3, "hp_tune": 1, "rec_half": 0, "dec_lab": 0, "lds_big": 1, "rows_direct": -1}
+_PATH_DEFAULTS = {"bs": 1, "sub": 1, "prune": 1, "unit_width": -1, "hp_tiles": 0, "hp_step": 0, "zc": 3, "hp_tune": 1, "rec_half": 0, "dec_lab": 0, "lds_big": 1, "rows_direct": -1, "pat_tier": 0, "bsdec_grid": 0}
 
 
 def set_path(knob: str, value: int) -> None:

@@ -744,6 +744,27 @@ class ReedSolomon:
         _check(self._L.rs_reconstruct_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, pr, S,
                                                 int(recover_all), _stream_handle(stream)))
 
+    def reconstruct_dev_batch_patterns(self, slab, patterns, pattern_of: Sequence[int], recover_all: bool = True,
+                                       stream=None) -> None:
+        """reconstruct_dev_batch with an erasure pattern per stripe
+        (rs_reconstruct_dev_batch_patterns): `patterns` is an
+        [npatterns, k+p] table of present flags, stripe z of the
+        [nstripes, k+p, S] slab uses row pattern_of[z] of it.  A stripe whose
+        pattern has nothing to rebuild is left alone."""
+        n, S = self._slab(slab)
+        table = np.ascontiguousarray(np.asarray(patterns, dtype=bool).astype(np.uint8))
+        if table.ndim != 2 or table.shape[1] != self.total_shards():
+            raise ErrTooFewShards("patterns must have %d flags per row" % self.total_shards())
+        of = np.ascontiguousarray(np.asarray(pattern_of, dtype=np.int64))
+        if of.shape != (n,):
+            raise TypeError("pattern_of must name one pattern per stripe")
+        if of.size and (of.min() < 0 or of.max() >= 1 << 32):
+            raise ErrInvalidArg("pattern_of entries must be pattern numbers")
+        of = of.astype(np.uint32)
+        _check(self._L.rs_reconstruct_dev_batch_patterns(
+            self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, table.ctypes.data_as(C.POINTER(C.c_uint8)),
+            table.shape[0], of.ctypes.data_as(C.POINTER(C.c_uint32)), S, int(recover_all), _stream_handle(stream)))
+
     def _flags(self, flags: Sequence[bool], what: str):
         if len(flags) != self.total_shards():
             raise ErrTooFewShards("need %d %s flags, got %d" % (self.total_shards(), what, len(flags)))

@@ -126,10 +126,16 @@ constexpr uint32_t z_after(uint32_t z, int qb) {
 // segment at each use: the persistent loop would otherwise keep every field
 // it touches in SGPRs for the whole loop (hundreds of SGPR spills).
 typedef __attribute__((address_space(4))) const RecArgs cargs_t;
+// PAT (k_rec_bs256_pat): the pattern's share of the arguments comes from the
+// descriptor of the tile being worked on (HBM, read the same way); phase 1
+// works on the next tile and phase 3 on the current one, so set_tile() points
+// pp at the right one before either.
+typedef __attribute__((address_space(4))) const RecPattern cpat_t;
 
-template <bool STRIDED>
+template <bool STRIDED, bool PAT = false>
 struct Dec {
     cargs_t *ap;        // the kernel's RecArgs (first kernel argument, kernarg offset 0)
+    cpat_t *pp;         // PAT: the descriptor of the tile's stripe
     // A layout: V[i] (i < 8) = row 16u + 2i + z of the unit being worked on
     // (byte form: row 16u + t at V[t >> 1][4 (t & 1) ..]); V[8..15] park a
     // second unit.  B layout (phase 2): V[q] = row z + 2v + 16q.
@@ -143,6 +149,32 @@ struct Dec {
         cargs_t *p = ap;
         asm volatile("" : "+s"(p));
         return *p;
+    }
+    __device__ __forceinline__ cpat_t &pat() const {
+        cpat_t *p = pp;
+        asm volatile("" : "+s"(p));
+        return *p;
+    }
+    // the pattern's tables: from the descriptor (PAT) or from the launch arguments
+    __device__ __forceinline__ const int *src_idx_of(cargs_t &a) const {
+        if constexpr (PAT) return pat().src_idx;
+        else return a.src_idx;
+    }
+    __device__ __forceinline__ const int *dst_idx_of(cargs_t &a) const {
+        if constexpr (PAT) return pat().dst_idx;
+        else return a.dst_idx;
+    }
+    __device__ __forceinline__ const uint32_t *tw_in_of(cargs_t &a) const {
+        if constexpr (PAT) return pat().tw_in;
+        else return a.tw_in;
+    }
+    __device__ __forceinline__ const uint32_t *tw_out_of(cargs_t &a) const {
+        if constexpr (PAT) return pat().tw_out;
+        else return a.tw_out;
+    }
+    __device__ __forceinline__ Need need_of(cargs_t &a) const {
+        if constexpr (PAT) return load_need(pat().need);
+        else return load_need(a.need);
     }
 
     __device__ __forceinline__ uint32_t *bytes(int t) { return &V[t >> 1][4 * (t & 1)]; }
@@ -164,18 +196,18 @@ struct Dec {
         const uint8_t *row;
         bool live;
         if constexpr (STRIDED) {
-            const int i = ((ci32_t *)a.src_idx)[r];
+            const int i = ((ci32_t *)src_idx_of(a))[r];
             live = i >= 0;
             row = sbase + (uint64_t)(live ? i : 0) * a.stride;
         } else {
             row = ((cptr_t *)a.src)[r];
             live = row != nullptr;
-            row = live ? row : (const uint8_t *)a.tw_in;
+            row = live ? row : (const uint8_t *)tw_in_of(a);
         }
         return row_rsrc(a, row, live ? 0u : 1u);
     }
     __device__ __forceinline__ uint8_t *dst_row(cargs_t &a, int j) const {
-        if constexpr (STRIDED) return sbase + (uint64_t)((ci32_t *)a.dst_idx)[j] * a.stride;
+        if constexpr (STRIDED) return sbase + (uint64_t)((ci32_t *)dst_idx_of(a))[j] * a.stride;
         else return ((cptr_t *)a.dst)[j];
     }
     // one row's 1 KB through a buffer descriptor whose range ends at the row end
@@ -212,7 +244,7 @@ struct Dec {
     // 16 at once would not fit the SGPRs).
     __device__ __forceinline__ void scale(int u) {
         cargs_t &a = args();
-        cu32_t *base = ctab(a.tw_in) + (uint64_t)(16 * u) * kTw16;
+        cu32_t *base = ctab(tw_in_of(a)) + (uint64_t)(16 * u) * kTw16;
         Tab<20> cur = tab_at<20>(base);
         sfor<16>([&](auto T) __attribute__((always_inline)) {
             constexpr int t = decltype(T)::value;
@@ -520,7 +552,7 @@ struct Dec {
     }
     __device__ __forceinline__ void phase3(int u) {
         cargs_t &a = args();
-        const Need need = load_need(a.need);
+        const Need need = need_of(a);
         const uint32_t nw = __builtin_amdgcn_readfirstlane(unit_need(need, u));
         fft_a(u);
         uint32_t pairs = 0;  // register rows holding a revealed row (either z)
@@ -576,7 +608,7 @@ struct Dec {
             const u32x4 x = *(const lds_u4 *)(uintptr_t)(sb + (uint32_t)(t >> 1) * 2048u + (uint32_t)(t & 1) * 1024u);
             uint32_t o[4];
             const uint32_t y[4] = {x[0], x[1], x[2], x[3]};
-            mul16(o, y, tab_at<20>(ctab(a.tw_out) + (uint64_t)j * kTw16));
+            mul16(o, y, tab_at<20>(ctab(tw_out_of(a)) + (uint64_t)j * kTw16));
             swap32(o[0], o[2]);  // back to lo bytes (p = 0) / hi bytes (p = 1) of symbols 16g..16g+15
             swap32(o[1], o[3]);
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{o[0], o[1], o[2], o[3]}, row_rsrc(a, dst_row(a, j)), off, 0, 0);
@@ -610,23 +642,48 @@ struct DecPlan {
 //   (waves < 8) -> Y into the image -> phase-3 waves read their rows ->
 //   barrier (image free) -> early units into the image; phase 3 of t_(i-1);
 //   late phase-1 units of t_i -> barrier (u of t_i in the image).
-template <bool STRIDED>
-__global__ void __launch_bounds__(64 * kWaves, kWaves / 4) k_rec_bs256(RecArgs a, DecPlan pl) {
+// PAT: tile t belongs to the stripe tiles[t / ntx] names, with that stripe's
+// descriptor: the phase-3 fields of the wave code follow the pattern of the
+// tile in phases 2-3, the phase-1 fields are pl's for every tile (they depend
+// on mtrunc only), so which waves pass which barriers never depends on a pattern.
+typedef __attribute__((address_space(4))) const RecStripe cstripe_t;
+// The per-pattern kernel's extra arguments (none for the one-pattern kernel).
+template <bool PAT> struct PatRefs {};
+template <> struct PatRefs<true> {
+    const RecPattern *pats;   // device array of descriptors
+    const RecStripe *tiles;   // device array: the stripes with something to rebuild
+};
+// (RecArgs first: Dec::ap reads it at kernarg offset 0)
+template <bool STRIDED, bool PAT = false>
+__global__ void __launch_bounds__(64 * kWaves, kWaves / 4) k_rec_bs256(RecArgs a, DecPlan pl, PatRefs<PAT> pr) {
+    cpat_t *pats = nullptr;
+    cstripe_t *tiles = nullptr;
+    if constexpr (PAT) {
+        pats = (cpat_t *)pr.pats;
+        tiles = (cstripe_t *)pr.tiles;
+    }
     __shared__ __attribute__((aligned(16))) uint32_t lds[kImgRows * kTile / 4];
-    Dec<STRIDED> d;
+    Dec<STRIDED, PAT> d;
     d.ap = (cargs_t *)__builtin_amdgcn_kernarg_segment_ptr();
+    d.pp = nullptr;
     d.lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)lds;
     d.w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int w = d.w;
     const uint64_t cw = w < 4 ? pl.code[0] : w < 8 ? pl.code[1] : pl.code[2];
     const uint32_t code = (uint32_t)(cw >> (16 * (w & 3))) & 0xFFFFu;
-    const int u3a = (int)(code & 15u) - 1, u3b = (int)((code >> 4) & 15u) - 1;
+    int u3a = (int)(code & 15u) - 1, u3b = (int)((code >> 4) & 15u) - 1;
+    uint64_t code0 = 0;  // PAT: the wave code of waves 0-3 for tile t (the last iteration's second phase-3 units)
     const int u1a = (int)((code >> 8) & 15u) - 1, u1b = (int)((code >> 12) & 15u) - 1;
     const bool early = w >= 8;
     auto set_tile = [&](int t) {
         const int y = t / pl.ntx;
         d.col = (uint64_t)(t - y * pl.ntx) * kTile;
-        if constexpr (STRIDED) {
+        if constexpr (PAT) {
+            cargs_t &ar = d.args();
+            const int stripe = tiles[y].stripe, pat = tiles[y].pat;
+            d.sbase = ar.base + (uint64_t)stripe * ar.stripe_stride;
+            d.pp = pats + pat;
+        } else if constexpr (STRIDED) {
             cargs_t &ar = d.args();
             d.sbase = ar.base + (uint64_t)y * ar.stripe_stride;
         } else {
@@ -637,6 +694,15 @@ __global__ void __launch_bounds__(64 * kWaves, kWaves / 4) k_rec_bs256(RecArgs a
     if (tn >= pl.ntiles) return;
     for (;;) {
         const bool cur = t >= 0, more = tn < pl.ntiles;
+        if constexpr (PAT) {
+            if (cur) {  // the phase-3 units of this wave for tile t's pattern
+                cpat_t &p = pats[tiles[t / pl.ntx].pat];
+                const uint64_t c3 = w < 4 ? p.code[0] : w < 8 ? p.code[1] : p.code[2];
+                const uint32_t c = (uint32_t)(c3 >> (16 * (w & 3))) & 0xFFFFu;
+                u3a = (int)(c & 15u) - 1, u3b = (int)((c >> 4) & 15u) - 1;
+                code0 = p.code[0];
+            }
+        }
         // The first iteration has no phase 2 / 3: every wave is free, so
         // wave w takes phase-1 unit w (one each) instead of the plan's split.
         const bool first = t < 0;
@@ -648,7 +714,7 @@ __global__ void __launch_bounds__(64 * kWaves, kWaves / 4) k_rec_bs256(RecArgs a
         bool pre = false;  // a late wave's phase-1 rows already in flight (lab bit 8)
         if (!more) {
             if (early) {
-                p3a = (int)((uint32_t)(pl.code[0] >> (16 * (w - 8))) >> 4 & 15u) - 1;
+                p3a = (int)((uint32_t)((PAT ? code0 : pl.code[0]) >> (16 * (w - 8))) >> 4 & 15u) - 1;
                 p3b = -1;
             } else if (w + 8 < kWaves) {
                 p3b = -1;
@@ -671,7 +737,7 @@ __global__ void __launch_bounds__(64 * kWaves, kWaves / 4) k_rec_bs256(RecArgs a
                     int wt = w;
                     asm volatile("" : "+s"(wt));
 #pragma unroll
-                    for (int q = 0; q < Dec<STRIDED>::NQ; q++) d.img_put(2 * wt + 16 * q, d.V[q]);
+                    for (int q = 0; q < Dec<STRIDED, PAT>::NQ; q++) d.img_put(2 * wt + 16 * q, d.V[q]);
                     // lab bit 8: a late wave with no phase-3 unit issues its phase-1
                     // unit's row loads now, so they are in flight across the Y barrier
                     if ((d.args().lab & 8) && more && p1a >= 0 && p3a < 0 && 16 * p1a < d.args().mtrunc) {
@@ -747,7 +813,9 @@ __global__ void __launch_bounds__(64 * kWaves, kWaves / 4) k_rec_bs256(RecArgs a
 // units go round-robin, at most two per wave (run one after the other), to
 // the waves < 8 without phase 1: about 4 per wave everywhere at C4.
 // Wave w runs on SIMD w & 3: waves 8-11 land one per SIMD.
-DecPlan make_plan(const RecArgs &a) {
+// fixed_e >= 0: only that number of phase-1 units on the early waves (a set of
+// patterns shares one phase-1 plan, rec_bs256_pattern_plan); best_e: the E chosen.
+DecPlan make_plan(const RecArgs &a, int fixed_e = -1, int *best_e = nullptr) {
     // phase 1 writes every image row: units past mtrunc write zeros (Dec::phase1)
     const int G = kUnits;
     uint32_t rmask = 0;  // units with revealed rows
@@ -756,7 +824,8 @@ DecPlan make_plan(const RecArgs &a) {
     static std::mutex mu;
     static std::map<uint32_t, DecPlan> cache;
     const uint32_t key = (uint32_t)a.mtrunc << 16 | rmask;  // the costs depend on which units lie past mtrunc
-    {
+    const bool cached = fixed_e < 0 && !best_e;
+    if (cached) {
         std::lock_guard<std::mutex> lk(mu);
         auto it = cache.find(key);
         if (it != cache.end()) return it->second;
@@ -776,6 +845,7 @@ DecPlan make_plan(const RecArgs &a) {
     int best = INT_MAX;
     for (int E = std::min(G, 2 * ne); E >= 0; E--) {
         if (G - E > 8) break;
+        if (fixed_e >= 0 && E != fixed_e) continue;
         int t1[kWaves][2], t3[kWaves][2], cost[kWaves] = {0};
         for (int w = 0; w < kWaves; w++) t1[w][0] = t1[w][1] = t3[w][0] = t3[w][1] = -1;
         for (int i = 0; i < E; i++) {
@@ -805,6 +875,7 @@ DecPlan make_plan(const RecArgs &a) {
         for (int w = 0; w < kWaves; w++) mx = std::max(mx, cost[w]);
         if (mx < best) {
             best = mx;
+            if (best_e) *best_e = E;
             std::memcpy(u1, t1, sizeof u1);
             std::memcpy(u3, t3, sizeof u3);
         }
@@ -820,6 +891,7 @@ DecPlan make_plan(const RecArgs &a) {
                            (uint64_t)(u1[w][1] + 1) << 12;
         bp.code[w >> 2] |= c << (16 * (w & 3));
     }
+    if (!cached) return bp;
     std::lock_guard<std::mutex> lk(mu);
     cache[key] = bp;
     return bp;
@@ -842,27 +914,82 @@ bool rec_bs256_available(int bits, int logn, bool sub, int mtrunc) {
     return bits == 16 && logn == 8 && sub && mtrunc <= kImgRows;
 }
 
-hipError_t launch_rec_bs256(const RecArgs &a, hipStream_t s) {
-    if (a.mtrunc > kImgRows) return hipErrorNotSupported;
+namespace {
+// Compute units of the current device (the persistent grid's size).
+hipError_t device_cus(int &cus) {
     static std::atomic<int> cus_of[64];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    int cus = dev < 64 ? cus_of[dev].load() : 0;
+    cus = dev < 64 ? cus_of[dev].load() : 0;
     if (!cus) {
         e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         if (e != hipSuccess) return e;
         if (dev < 64) cus_of[dev].store(cus);
     }
+    return hipSuccess;
+}
+}  // namespace
+
+// The phase-1 plan is that of the union of the patterns' revealed units (the
+// set's heaviest phase 3 decides how many units the early waves take); each
+// pattern then gets its own phase-3 placement beside it.
+bool rec_bs256_pattern_plan(int mtrunc, RecPattern *pats, int npat, uint64_t code1[3]) {
+    if (mtrunc < 1 || mtrunc > kImgRows || npat < 1) return false;
+    RecArgs u{};
+    u.mtrunc = mtrunc;
+    for (int i = 0; i < npat; i++)
+        for (int k = 0; k < 8; k++) u.need[k] |= pats[i].need[k];
+    int e = -1;
+    const DecPlan shared = make_plan(u, -1, &e);
+    if (shared.ntiles < 0 || e < 0) return false;
+    for (int j = 0; j < 3; j++) code1[j] = shared.code[j];
+    for (int i = 0; i < npat; i++) {
+        RecArgs a{};
+        a.mtrunc = mtrunc;
+        for (int k = 0; k < 8; k++) a.need[k] = pats[i].need[k];
+        const DecPlan pl = make_plan(a, e);
+        if (pl.ntiles < 0) return false;
+        for (int j = 0; j < 3; j++) {
+            // same E and mtrunc: the same phase-1 fields as the shared plan
+            if ((pl.code[j] ^ shared.code[j]) & 0xFF00FF00FF00FF00ull) return false;
+            pats[i].code[j] = pl.code[j];
+        }
+    }
+    return true;
+}
+
+hipError_t launch_rec_bs256_patterns(const RecBsPatArgs &a, hipStream_t s) {
+    if (a.a.mtrunc > kImgRows || !a.a.base || !a.pat || !a.tiles || a.nactive < 1) return hipErrorInvalidValue;
+    int cus = 0;
+    hipError_t e = device_cus(cus);
+    if (e != hipSuccess) return e;
+    DecPlan pl{};
+    for (int j = 0; j < 3; j++) pl.code[j] = a.code1[j];
+    pl.ntx = (int)((a.a.S + kTile - 1) / kTile);
+    if ((uint64_t)pl.ntx * (uint64_t)a.nactive > (uint64_t)INT32_MAX) return hipErrorInvalidValue;
+    pl.ntiles = pl.ntx * a.nactive;
+    unsigned grid = (unsigned)std::min<int>(pl.ntiles, std::max(cus, 1));
+    if (const int cap = bsdec_grid_override(); cap > 0) grid = std::min(grid, (unsigned)cap);
+    hipLaunchKernelGGL((k_rec_bs256<true, true>), dim3(grid), dim3(64 * kWaves), 0, s, a.a, pl, PatRefs<true>{a.pat, a.tiles});
+    return hipGetLastError();
+}
+
+hipError_t launch_rec_bs256(const RecArgs &a, hipStream_t s) {
+    if (a.mtrunc > kImgRows) return hipErrorNotSupported;
+    int cus = 0;
+    hipError_t e = device_cus(cus);
+    if (e != hipSuccess) return e;
     DecPlan pl = make_plan(a);
     if (pl.ntiles < 0) return hipErrorNotSupported;  // cannot happen for mtrunc <= kImgRows
     pl.ntx = (int)((a.S + kTile - 1) / kTile);
     const uint64_t ny = a.base && a.nstripes > 1 ? (uint64_t)a.nstripes : 1;
     if ((uint64_t)pl.ntx * ny > (uint64_t)INT32_MAX) return hipErrorInvalidValue;
     pl.ntiles = (int)(pl.ntx * ny);
-    const unsigned grid = (unsigned)std::min<int>(pl.ntiles, std::max(cus, 1));
-    if (a.base) hipLaunchKernelGGL(k_rec_bs256<true>, dim3(grid), dim3(64 * kWaves), 0, s, a, pl);
-    else hipLaunchKernelGGL(k_rec_bs256<false>, dim3(grid), dim3(64 * kWaves), 0, s, a, pl);
+    unsigned grid = (unsigned)std::min<int>(pl.ntiles, std::max(cus, 1));
+    if (const int cap = bsdec_grid_override(); cap > 0) grid = std::min(grid, (unsigned)cap);  // rs_debug_set_path "bsdec_grid"
+    if (a.base) hipLaunchKernelGGL((k_rec_bs256<true, false>), dim3(grid), dim3(64 * kWaves), 0, s, a, pl, PatRefs<false>{});
+    else hipLaunchKernelGGL((k_rec_bs256<false, false>), dim3(grid), dim3(64 * kWaves), 0, s, a, pl, PatRefs<false>{});
     return hipGetLastError();
 }
 

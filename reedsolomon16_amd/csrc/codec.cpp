@@ -173,6 +173,23 @@ struct DevPlan : StreamUses {
     }
 };
 
+// The device tables of a set of erasure patterns
+// (rs_reconstruct_dev_batch_patterns): per pattern what a DevPlan holds (less
+// pos, which the LDS-resident kernels do not read), in one blob, and the array
+// of descriptors that point into it; a stripe names its pattern by descriptor index.
+struct PatternSet : StreamUses {
+    DevBuf<uint8_t> blob;
+    const RecPattern *desc = nullptr;  // device array, one per pattern of the set
+    // codecs of the bit-sliced n = 256 decoder: the phase-1 wave plan the set's
+    // patterns share (each descriptor holds its own phase-3 placement)
+    bool bs_ok = false;
+    uint64_t code1[3] = {};
+    ~PatternSet() {
+        drain();
+        blob.release();
+    }
+};
+
 // The device tables of an incremental update for one ordered list of changed
 // data rows: p x t multiply-by-G[i][idx[j]] images (make_update_tables) and
 // the indices themselves (the strided kernel reads them).
@@ -299,6 +316,10 @@ struct rs_codec {
     Lru<std::vector<int>, std::unique_ptr<UpdPlan>, 16> uplan_cache;
     // direct-decode tables keyed by (erasure pattern, rows rebuilt), likewise
     Lru<std::vector<uint8_t>, std::unique_ptr<RowsPlan>, 16> rowsplan_cache;
+    // pattern sets keyed by (recover_all, the set's erasure patterns in order);
+    // one set holds every pattern of a call (or of a stripe range of it), so a
+    // rotated layout's 160 patterns take one slot here and none of dplan_cache
+    Lru<std::vector<uint8_t>, std::unique_ptr<PatternSet>, 4> pset_cache;
     // scrub (rs_verify_dev_batch_map / rs_locate_dev / rs_scrub_dev_batch): the
     // ratio map of the data shards (built on the first locate), the device
     // tables of a repaired row keyed by its data shard (UpdPlan::tw: the three
@@ -364,6 +385,7 @@ struct rs_codec {
         dplan_cache.items.clear();  // each plan waits for its last launch
         uplan_cache.items.clear();
         rowsplan_cache.items.clear();
+        pset_cache.items.clear();
         fixplan_cache.items.clear();
         scrub_rows.release(); scrub_dev.release();
         scrub_host.release();
@@ -454,7 +476,7 @@ int upload_split(rs_codec *c) {
 // the reconstruct FFT unpruned, the narrow / wide LDS units) on the same small
 // inputs.  Process-wide; read when a codec is created (bs) or at each launch.
 std::atomic<int> g_path_bs{1}, g_path_sub{1}, g_path_prune{1}, g_path_unit_width{-1}, g_path_hp_tiles{0}, g_path_hp_step{0},
-    g_path_zc{3}, g_path_hp_tune{1}, g_path_rec_half{0}, g_path_dec_lab{0}, g_path_lds_big{1}, g_path_rows_direct{-1};
+    g_path_zc{3}, g_path_hp_tune{1}, g_path_rec_half{0}, g_path_dec_lab{0}, g_path_lds_big{1}, g_path_rows_direct{-1}, g_path_pat_tier{0}, g_path_bsdec_grid{0};
 bool bs_enabled() { return g_path_bs.load(std::memory_order_relaxed) != 0; }
 bool sub_enabled() { return g_path_sub.load(std::memory_order_relaxed) != 0; }
 bool prune_enabled() { return g_path_prune.load(std::memory_order_relaxed) != 0; }
@@ -465,6 +487,7 @@ int rs::hp_tiles_override() { return g_path_hp_tiles.load(std::memory_order_rela
 int rs::hp_step_override() { return g_path_hp_step.load(std::memory_order_relaxed); }
 bool rs::hp_tune_enabled() { return g_path_hp_tune.load(std::memory_order_relaxed) != 0; }
 bool rs::rec_half_enabled() { return g_path_rec_half.load(std::memory_order_relaxed) != 0; }
+int rs::bsdec_grid_override() { return g_path_bsdec_grid.load(std::memory_order_relaxed); }
 namespace {
 
 // One LDS-resident encode launch covers m <= 256 (both fields) and, for
@@ -2165,6 +2188,237 @@ int reconstruct_dev_call(rs_codec *c, uint8_t *const *d, const std::vector<uint8
     return reconstruct_device(c, d, pr, S, want, s);
 }
 
+// ---- One erasure pattern per stripe (rs_reconstruct_dev_batch_patterns)
+// Offsets of one pattern's tables in a PatternSet blob (every table 256-byte
+// aligned): tw_in at 0, n images; tw_out, one image per rebuilt row; the
+// source shard of each work row; the rebuilt shards; the revealed-row mask;
+// the output index of each work row.
+struct PatLayout {
+    size_t o_out, o_si, o_di, o_nw, o_rev, total;
+};
+PatLayout pattern_layout(const rs_codec *c, int nd) {
+    const size_t img = (size_t)c->twd * 4;
+    PatLayout l;
+    l.o_out = align256((size_t)c->n * img);
+    l.o_si = l.o_out + align256((size_t)std::max(nd, 1) * img);
+    l.o_di = l.o_si + align256((size_t)c->n * 4);
+    l.o_nw = l.o_di + align256((size_t)std::max(nd, 1) * 4);
+    l.o_rev = l.o_nw + align256((size_t)std::max(c->n / 32, 1) * 4);
+    l.total = l.o_rev + align256((size_t)c->n * 4);
+    return l;
+}
+// Table bytes of one launch's pattern set; a call whose patterns need more
+// runs as several launches over stripe ranges, each with a set of its own.
+// 64 MiB holds over 2000 patterns of a 128+32 codec (n = 256: 27392 bytes
+// each with one erasure, 30208 with 32), 280 of a 1024+256 codec (n = 2048:
+// 213760 bytes with one erasure, 238848 with 256) and about 70 of an
+// n = 8192 codec, plus sizeof(RecPattern) per descriptor.
+constexpr size_t kPatSetBudget = 64ull << 20;
+// Stripes per launch: bounds the per-call index upload (4 bytes a stripe, a ring slot).
+constexpr size_t kPatMaxStripes = 1u << 18;
+
+// The cached device set of the patterns `pats` (k+p present flags each, all
+// different, each with something to rebuild), built and uploaded on first use.
+// The locators are the exact ones of each pattern, computed here: neither the
+// reference-keyed inversion cache nor the 16-slot plan caches see these patterns.
+int pattern_set(rs_codec *c, const std::vector<const uint8_t *> &pats, bool all, PatternSet **out) {
+    const int total = c->total, n = c->n;
+    std::vector<uint8_t> key;
+    key.reserve(pats.size() * total + 1);
+    key.push_back(all ? 1 : 0);
+    for (const uint8_t *p : pats)
+        for (int i = 0; i < total; i++) key.push_back(p[i] != 0);
+    if (auto *hit = c->pset_cache.find(key)) {
+        *out = hit->get();
+        return RS_OK;
+    }
+    std::vector<RecPlan> plans(pats.size());
+    std::vector<size_t> off(pats.size());
+    std::vector<uint8_t> present(total), erased(total);
+    std::vector<uint32_t> el;
+    size_t bytes = align256(pats.size() * sizeof(RecPattern));
+    for (size_t q = 0; q < pats.size(); q++) {
+        for (int i = 0; i < total; i++) present[i] = pats[q][i] != 0, erased[i] = !present[i];
+        if (!error_locators(*c->F, c->k, c->p, erased.data(), el)) return RS_ERR_PANIC;
+        if (int e = plan_reconstruct_new(c, present, Want(all), el, plans[q])) return e;
+        off[q] = bytes;
+        bytes += pattern_layout(c, (int)plans[q].dst_shard.size()).total;
+    }
+    auto ps = std::make_unique<PatternSet>();
+    HIP_TRY(ps->blob.ensure(bytes));
+    uint8_t *g = ps->blob.p;
+    std::vector<uint8_t> h(bytes, 0);
+    RecPattern *desc = (RecPattern *)h.data();
+    for (size_t q = 0; q < pats.size(); q++) {
+        const RecPlan &pl = plans[q];
+        const int nd = (int)pl.dst_shard.size();
+        const PatLayout l = pattern_layout(c, nd);
+        uint8_t *t = h.data() + off[q];
+        std::memcpy(t, pl.tw_in.data(), pl.tw_in.size() * 4);
+        std::memcpy(t + l.o_out, pl.tw_out.data(), pl.tw_out.size() * 4);
+        std::memcpy(t + l.o_si, pl.src_shard.data(), (size_t)n * 4);
+        std::memcpy(t + l.o_di, pl.dst_shard.data(), (size_t)nd * 4);
+        uint32_t *nw = (uint32_t *)(t + l.o_nw);
+        int *rev = (int *)(t + l.o_rev);
+        for (int r = 0; r < n; r++) rev[r] = -1;
+        RecPattern &d = desc[q];
+        for (int j = 0; j < nd; j++) {
+            const int r = pl.pos[j];
+            nw[r >> 5] |= 1u << (r & 31);
+            rev[r] = j;
+            if (r < 256) d.need[r >> 5] |= 1u << (r & 31);
+        }
+        const uint8_t *gt = g + off[q];
+        d.tw_in = (const uint32_t *)gt;
+        d.tw_out = (const uint32_t *)(gt + l.o_out);
+        d.src_idx = (const int *)(gt + l.o_si);
+        d.dst_idx = (const int *)(gt + l.o_di);
+        d.need_w = (const uint32_t *)(gt + l.o_nw);
+        d.rev = (const int *)(gt + l.o_rev);
+        d.nd = nd;
+    }
+    if (rec_bs256_available(c->bits, c->logn, c->dec_sub, c->m + c->k))
+        ps->bs_ok = rec_bs256_pattern_plan(c->m + c->k, desc, (int)pats.size(), ps->code1);
+    HIP_TRY(hipMemcpy(g, h.data(), bytes, hipMemcpyHostToDevice));
+    ps->desc = (const RecPattern *)g;
+    *out = c->pset_cache.put(std::move(key), std::move(ps))->get();  // an eviction waits for that set's last launch
+    return RS_OK;
+}
+
+// rs_reconstruct_dev_batch_patterns after its NULL checks.
+int reconstruct_patterns_call(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
+                              const uint8_t *present, size_t npat, const uint32_t *pattern_of, size_t S, bool all,
+                              void *stream) {
+    const int total = c->total, k = c->k;
+    for (size_t z = 0; z < nstripes; z++)
+        if (pattern_of[z] >= npat) return RS_ERR_INVALID_ARG;
+    // per pattern: rows present, and missing rows the call rebuilds
+    std::vector<int> todo(npat, 0);
+    bool too_few = false;
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    for (size_t q = 0; q < npat; q++) {
+        const uint8_t *pr = present + q * total;
+        int np = 0;
+        for (int i = 0; i < total; i++) {
+            if (pr[i]) np++;
+            else if (all || i < k) todo[q]++;
+        }
+        if (np == 0) return RS_ERR_SHARD_NO_DATA;
+        too_few = too_few || np < k;
+    }
+    if (too_few) return RS_ERR_TOO_FEW_SHARDS;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (row_stride < S || (nstripes > 1 && stripe_stride < (size_t)total * row_stride)) return RS_ERR_INVALID_ARG;
+    if ((long)c->m + k > (long)c->F->order) return RS_ERR_PANIC;  // error_locators / decode_schedule: the reference panics
+    bool any = false;
+    for (size_t z = 0; z < nstripes && !any; z++) any = todo[pattern_of[z]] > 0;
+    if (!any) return RS_OK;
+
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    if (int e = build_decode_plan(c)) return e;
+    if (!c->dec_ok) return RS_ERR_PANIC;
+    if (!rec_lds_ok(c)) {
+        // multi-pass codecs: stripe by stripe (the exact locators: the
+        // reference-keyed cache exists for GF(2^8) only, which is never multi-pass)
+        std::vector<uint8_t *> rows(total);
+        for (size_t z = 0; z < nstripes; z++) {
+            const size_t q = pattern_of[z];
+            if (!todo[q]) continue;
+            for (int i = 0; i < total; i++) rows[i] = base + z * stripe_stride + (uint64_t)i * row_stride;
+            const std::vector<uint8_t> pr(present + q * total, present + (q + 1) * total);
+            if (int e = reconstruct_device(c, rows.data(), pr, S, all, s)) return e;
+        }
+        return RS_OK;
+    }
+    // Equal rows of the table share a descriptor: canon[q] is the first
+    // referenced row with q's flags (-1: not looked at yet).
+    std::vector<int> canon(npat, -1);
+    std::map<std::vector<uint8_t>, int> seen;
+    auto canon_of = [&](size_t q) {
+        if (canon[q] < 0) {
+            std::vector<uint8_t> f(total);
+            for (int i = 0; i < total; i++) f[i] = present[q * total + i] != 0;
+            canon[q] = seen.emplace(std::move(f), (int)q).first->second;
+        }
+        return canon[q];
+    };
+    // Stripe ranges [z0, z1), each within the table budget and the stripe
+    // limit, each one launch over a pattern set of its own.
+    std::vector<int> desc_of(npat, -1);  // descriptor of a canonical pattern in the current range
+    std::vector<int> idx;
+    for (size_t z0 = 0; z0 < nstripes;) {
+        std::vector<const uint8_t *> pats;
+        std::vector<int> members;
+        size_t bytes = 0, z1 = z0;
+        idx.clear();
+        for (; z1 < nstripes && z1 - z0 < kPatMaxStripes; z1++) {
+            const size_t q = pattern_of[z1];
+            if (!todo[q]) {
+                idx.push_back(-1);
+                continue;
+            }
+            const int cq = canon_of(q);
+            if (desc_of[cq] < 0) {
+                const size_t need = pattern_layout(c, todo[cq]).total + sizeof(RecPattern);
+                if (!pats.empty() && bytes + need > kPatSetBudget) break;
+                bytes += need;
+                desc_of[cq] = (int)pats.size();
+                pats.push_back(present + (size_t)cq * total);
+                members.push_back(cq);
+            }
+            idx.push_back(desc_of[cq]);
+        }
+        for (int cq : members) desc_of[cq] = -1;
+        if (!pats.empty()) {
+            PatternSet *ps = nullptr;
+            if (int e = pattern_set(c, pats, all, &ps)) return e;
+            // the bit-sliced decoder where the codec has one (rs_debug_set_path
+            // "pat_tier" 1: the LDS-resident kernel there too)
+            const bool bs = ps->bs_ok && g_path_pat_tier.load(std::memory_order_relaxed) != 1;
+            int slot = 0;
+            uint8_t *h = nullptr, *g = nullptr;
+            const size_t ib = idx.size() * (bs ? sizeof(RecStripe) : sizeof(int));
+            if (int e = ring_acquire(c, ib, slot, h, g)) return e;
+            DevPlan none;  // the shared fields only: the descriptors carry the pattern's
+            RecArgs ra = rec_args(c, &none, S);
+            ra.base = base + z0 * stripe_stride;
+            ra.stride = row_stride;
+            ra.stripe_stride = stripe_stride;
+            ra.nstripes = (int)(z1 - z0);
+            if (bs) {
+                // the stripes with something to rebuild, each with its descriptor
+                RecStripe *list = (RecStripe *)h;
+                int na = 0;
+                for (size_t i = 0; i < idx.size(); i++)
+                    if (idx[i] >= 0) list[na++] = RecStripe{(int)i, idx[i]};
+                HIP_TRY(hipMemcpyAsync(g, h, (size_t)na * sizeof(RecStripe), hipMemcpyHostToDevice, s));
+                RecBsPatArgs ba{};
+                ba.a = ra;
+                ba.pat = ps->desc;
+                ba.tiles = (const RecStripe *)g;
+                ba.nactive = na;
+                std::memcpy(ba.code1, ps->code1, sizeof(ba.code1));
+                HIP_TRY(launch_rec_bs256_patterns(ba, s));
+            } else {
+                std::memcpy(h, idx.data(), ib);
+                HIP_TRY(hipMemcpyAsync(g, h, ib, hipMemcpyHostToDevice, s));
+                RecPatArgs pa{};
+                pa.a = ra;
+                pa.pat = ps->desc;
+                pa.pat_of = (const int *)g;
+                HIP_TRY(launch_rec_lds_patterns(c->bits, c->logn, c->dec_sub, pa, s));
+            }
+            HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+            c->ring_used[slot] = true;
+            HIP_TRY(ps->mark_used(s));
+        }
+        z0 = z1;
+    }
+    return dc.finish(RS_OK);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- multi-device parts (multi.hpp)
@@ -2531,6 +2785,16 @@ int rs_reconstruct_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size
     if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
     const std::vector<uint8_t> pr(present, present + c->total);
     return reconstruct_dev_batch_call(c, base, row_stride, stripe_stride, nstripes, pr, recover_all != 0, S, stream);
+}
+
+int rs_reconstruct_dev_batch_patterns(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride,
+                                      size_t nstripes, const uint8_t *present, size_t npatterns,
+                                      const uint32_t *pattern_of, size_t S, int recover_all, void *stream) {
+    if (!c || !base || !present || !pattern_of || nstripes > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    if (npatterns == 0 || npatterns > 65536) return RS_ERR_INVALID_ARG;
+    return reconstruct_patterns_call(c, base, row_stride, stripe_stride, nstripes, present, npatterns, pattern_of, S,
+                                     recover_all != 0, stream);
 }
 
 int rs_reconstruct_rows_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
@@ -2954,6 +3218,8 @@ int rs_debug_set_path(const char *knob, int value) {
     else if (k == "lds_big" && value >= 0 && value <= 1) g_path_lds_big = value;
     else if (k == "zc" && value >= 0 && value <= 3) g_path_zc = value;
     else if (k == "rows_direct" && value >= -1 && value <= 1) g_path_rows_direct = value;
+    else if (k == "pat_tier" && value >= 0 && value <= 2) g_path_pat_tier = value;
+    else if (k == "bsdec_grid" && value >= 0) g_path_bsdec_grid = value;
     else return RS_ERR_INVALID_ARG;
     return RS_OK;
 }

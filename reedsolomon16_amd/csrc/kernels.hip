@@ -1352,8 +1352,10 @@ template <int LOGN> struct BigSub {
     static constexpr int FEND = big_sub_fft_end(LOGN);   // FFT passes [0, FEND) subfield
 };
 
-template <class F, class FT, int LOGN, bool BSUB = false, int PKV = 1>
-__global__ void __launch_bounds__((rec_threads<LOGN, PKV>()), (PKV == 2 && LOGN < 12 ? 2 : 1)) k_rec_lds(RecArgs a) {
+// The kernel's body: k_rec_lds runs it on its launch arguments, k_rec_lds_pat
+// on a copy with the stripe's own pattern fields.
+template <class F, class FT, int LOGN, bool BSUB, int PKV>
+__device__ __forceinline__ void rec_lds_body(const RecArgs &a) {
     typedef LTile<F, PKV> L;  // packed 64-byte tiles (LTile PK), or half / quarter tiles (PKV = 2 / 4)
     typedef typename F::Vec V;
     constexpr int N = 1 << LOGN, U = L::U, NT = rec_threads<LOGN, PKV>();
@@ -1549,6 +1551,35 @@ __global__ void __launch_bounds__((rec_threads<LOGN, PKV>()), (PKV == 2 && LOGN 
     } else {
         lds_transform<FT, false, LOGN, LdsIO<FT, PKV>, Reveal, NoNeed, 0, 32, NT, false, PKV>(lds, a.mtrunc, a.tw_fft, NoNeed{}, lio, rv);
     }
+}
+
+template <class F, class FT, int LOGN, bool BSUB = false, int PKV = 1>
+__global__ void __launch_bounds__((rec_threads<LOGN, PKV>()), (PKV == 2 && LOGN < 12 ? 2 : 1)) k_rec_lds(RecArgs a) {
+    rec_lds_body<F, FT, LOGN, BSUB, PKV>(a);
+}
+
+// One erasure pattern per stripe (rs_reconstruct_dev_batch_patterns): stripe
+// blockIdx.y takes descriptor pat_of[blockIdx.y] of the pattern set, whose
+// fields stand in for the pattern's share of RecArgs.  The index and the
+// descriptor are read through the constant address space (scalar loads: they
+// are the same for the whole workgroup); a stripe with index -1 has nothing
+// to rebuild and its workgroups leave before they touch the LDS.
+template <class F, class FT, int LOGN, bool BSUB = false, int PKV = 1>
+__global__ void __launch_bounds__((rec_threads<LOGN, PKV>()), (PKV == 2 && LOGN < 12 ? 2 : 1)) k_rec_lds_pat(RecPatArgs pa) {
+    const int d = ((const __attribute__((address_space(4))) int *)pa.pat_of)[blockIdx.y];
+    if (d < 0) return;
+    const __attribute__((address_space(4))) RecPattern &p = ((const __attribute__((address_space(4))) RecPattern *)pa.pat)[d];
+    RecArgs a = pa.a;
+    a.src_idx = p.src_idx;
+    a.dst_idx = p.dst_idx;
+    a.tw_in = p.tw_in;
+    a.tw_out = p.tw_out;
+    a.need_w = p.need_w;
+    a.rev = p.rev;
+    a.nd = p.nd;
+#pragma unroll
+    for (int k = 0; k < 8; k++) a.need[k] = p.need[k];
+    rec_lds_body<F, FT, LOGN, BSUB, PKV>(a);
 }
 
 // Encode for 32 < m <= 256 (leopard16.go:128-224 / leopard8.go:153-277):
@@ -1759,17 +1790,33 @@ hipError_t rec_lds_tb(const RecArgs &a, hipStream_t s) {
         hipLaunchKernelGGL((k_rec_lds<F, FT, LOGN, BSUB, PKV>), dim3(gx, (unsigned)ny), dim3(NT), 0, s, b);
     });
 }
-template <class F, class FT, int LOGN>
-hipError_t rec_lds_t(const RecArgs &a, hipStream_t s) {
+// a pattern per stripe: a slice of grid.y moves the stripe base and the
+// per-stripe descriptor indices together
+template <class F, class FT, int LOGN, bool BSUB, int PKV = 1>
+hipError_t rec_lds_tb(const RecPatArgs &a, hipStream_t s) {
+    constexpr int TB = LTile<F, PKV>::TB, NT = rec_threads<LOGN, PKV>();
+    const unsigned gx = (unsigned)((a.a.S + TB - 1) / TB);
+    return for_y(a.a.nstripes, [&](int y0, int ny) {
+        RecPatArgs b = a;
+        b.a.base = a.a.base + (uint64_t)y0 * a.a.stripe_stride;
+        b.pat_of = a.pat_of + y0;
+        hipLaunchKernelGGL((k_rec_lds_pat<F, FT, LOGN, BSUB, PKV>), dim3(gx, (unsigned)ny), dim3(NT), 0, s, b);
+    });
+}
+inline const RecArgs &rec_core(const RecArgs &a) { return a; }
+inline const RecArgs &rec_core(const RecPatArgs &a) { return a.a; }
+template <class F, class FT, int LOGN, class A>
+hipError_t rec_lds_t(const A &a, hipStream_t s) {
+    const RecArgs &c = rec_core(a);
     if constexpr (LOGN >= 13 && std::is_same<F, F16<2>>::value) {  // n = 8192: quarter tiles
-        if (a.tw_ifft_sub && a.tw_fft_sub && a.tw_dmap) return rec_lds_tb<F, FT, LOGN, true, 4>(a, s);
+        if (c.tw_ifft_sub && c.tw_fft_sub && c.tw_dmap) return rec_lds_tb<F, FT, LOGN, true, 4>(a, s);
         return rec_lds_tb<F, FT, LOGN, false, 4>(a, s);
     }
     if constexpr (LOGN >= 10 && LOGN < 13 && std::is_same<F, F16<2>>::value) {
         // n = 1024, 2048: half tiles, two workgroups per CU (rs_debug_set_path "rec_half");
         // n = 4096: half tiles always
         if (LOGN >= 12 || rec_half_enabled()) {
-            if (a.tw_ifft_sub && a.tw_fft_sub && a.tw_dmap) return rec_lds_tb<F, FT, LOGN, true, 2>(a, s);
+            if (c.tw_ifft_sub && c.tw_fft_sub && c.tw_dmap) return rec_lds_tb<F, FT, LOGN, true, 2>(a, s);
             return rec_lds_tb<F, FT, LOGN, false, 2>(a, s);
         }
     }
@@ -1777,12 +1824,12 @@ hipError_t rec_lds_t(const RecArgs &a, hipStream_t s) {
         return hipErrorInvalidValue;  // (unreachable: half tiles above)
     } else {
         if constexpr (LOGN > 8)
-            if (a.tw_ifft_sub && a.tw_fft_sub && a.tw_dmap) return rec_lds_tb<F, FT, LOGN, true>(a, s);
+            if (c.tw_ifft_sub && c.tw_fft_sub && c.tw_dmap) return rec_lds_tb<F, FT, LOGN, true>(a, s);
         return rec_lds_tb<F, FT, LOGN, false>(a, s);
     }
 }
-template <class F, class FT = F>
-hipError_t rec_lds_f(int logn, const RecArgs &a, hipStream_t s) {
+template <class F, class FT = F, class A>
+hipError_t rec_lds_f(int logn, const A &a, hipStream_t s) {
     switch (logn) {
         case 1: return rec_lds_t<F, FT, 1>(a, s);
         case 2: return rec_lds_t<F, FT, 2>(a, s);
@@ -2044,8 +2091,8 @@ hipError_t launch_reveal(int bits, uint8_t *const *dst, const uint8_t *work, uin
 }
 
 
-template <int W>
-hipError_t rec_lds_w(int bits, int logn, bool sub, const RecArgs &a, hipStream_t s) {
+template <int W, class A>
+hipError_t rec_lds_w(int bits, int logn, bool sub, const A &a, hipStream_t s) {
     if (bits != 16) return rec_lds_f<F8<W>>(logn, a, s);
     return sub ? rec_lds_f<F16<W>, F16S<W>>(logn, a, s) : rec_lds_f<F16<W>>(logn, a, s);
 }
@@ -2057,6 +2104,16 @@ hipError_t launch_rec_lds(int bits, int logn, bool sub, const RecArgs &a, hipStr
     }
     const uint64_t ns = a.base && a.nstripes > 1 ? (uint64_t)a.nstripes : 1;
     const bool narrow = pick_narrow((a.S + 127) / 128 * ns < kLdsMinGrid);
+    return narrow ? rec_lds_w<2>(bits, logn, sub, a, s) : rec_lds_w<4>(bits, logn, sub, a, s);
+}
+
+hipError_t launch_rec_lds_patterns(int bits, int logn, bool sub, const RecPatArgs &a, hipStream_t s) {
+    if (!a.a.base || a.a.nstripes < 1 || !a.pat || !a.pat_of) return hipErrorInvalidValue;
+    if (logn > 8) {
+        if (bits != 16 || sub || logn > kMaxLdsRecLogN16) return hipErrorInvalidValue;
+        return rec_lds_f<F16<2>>(logn, a, s);
+    }
+    const bool narrow = pick_narrow((a.a.S + 127) / 128 * (uint64_t)a.a.nstripes < kLdsMinGrid);
     return narrow ? rec_lds_w<2>(bits, logn, sub, a, s) : rec_lds_w<4>(bits, logn, sub, a, s);
 }
 

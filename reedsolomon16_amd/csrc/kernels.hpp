@@ -69,6 +69,8 @@ int hp_tiles_override();
 int hp_step_override();
 bool hp_tune_enabled();
 bool rec_half_enabled();
+// Workgroups of the bit-sliced decoder's persistent grid: 0 = one per compute unit, n >= 1 at most n.
+int bsdec_grid_override();
 
 hipError_t launch_encode_reg(int bits, int logm, bool verify, const EncodeArgs &a, hipStream_t s);
 // Half-wave split encode (GF(2^16), logm 2..5, strided rows only: data.table ==
@@ -167,6 +169,51 @@ hipError_t launch_rec_lds(int bits, int logn, bool sub, const RecArgs &a, hipStr
 // m + k <= 160 (its LDS image).
 bool rec_bs256_available(int bits, int logn, bool sub, int mtrunc);
 hipError_t launch_rec_bs256(const RecArgs &a, hipStream_t s);
+
+// ---- A slab of stripes, each with an erasure pattern of its own
+// (rs_reconstruct_dev_batch_patterns).  Everything of RecArgs that depends on
+// the pattern, as one descriptor per pattern in HBM (codec.cpp PatternSet).
+struct RecPattern {
+    const int *src_idx, *dst_idx;
+    const uint32_t *tw_in, *tw_out;
+    const uint32_t *need_w;  // n > 256
+    const int *rev;          // n > 256
+    uint32_t need[8];        // n <= 256
+    int nd;
+    int pad;
+    // bit-sliced decoder: the pattern's wave plan (bitslice_dec.hip DecPlan::code;
+    // its phase-3 fields are read, phase 1 follows the launch's shared plan)
+    uint64_t code[3];
+};
+struct RecPatArgs {
+    // strided form only (base set); src_idx, dst_idx, tw_in, tw_out, need_w,
+    // rev, need, nd and pos are not read: the stripe's descriptor replaces them
+    RecArgs a;
+    const RecPattern *pat;  // device array
+    const int *pat_of;      // device array, a.nstripes entries: stripe y's descriptor, -1: leave the stripe alone
+};
+// The LDS-resident reconstruct (k_rec_lds_pat) over every geometry
+// launch_rec_lds serves; n = 256 GF(2^16) codecs of the bit-sliced decoder run
+// the subfield LDS kernel here.
+hipError_t launch_rec_lds_patterns(int bits, int logn, bool sub, const RecPatArgs &a, hipStream_t s);
+// The same through the bit-sliced decoder (k_rec_bs256_pat; codecs with
+// rec_bs256_available): persistent over the column tiles of the stripes listed
+// in `tiles` (those with something to rebuild), each tile with the descriptor
+// of its stripe.  code1: the launch's phase-1 wave plan, shared by all patterns.
+struct RecStripe {
+    int stripe, pat;
+};
+struct RecBsPatArgs {
+    RecArgs a;               // as RecPatArgs::a
+    const RecPattern *pat;   // device array
+    const RecStripe *tiles;  // device array, nactive entries
+    int nactive;
+    uint64_t code1[3];
+};
+// Host: fills pats[i].code for every pattern of a set (need set) and code1,
+// the phase-1 plan they share; false when mtrunc does not fit the decoder.
+bool rec_bs256_pattern_plan(int mtrunc, RecPattern *pats, int npat, uint64_t code1[3]);
+hipError_t launch_rec_bs256_patterns(const RecBsPatArgs &a, hipStream_t s);
 // Encode (or verify) for 2 <= logm <= 8, and GF(2^16) up to kMaxLdsEncLogM16
 // (64-byte tiles, 32-byte half tiles at m = 2048, 16-byte quarter tiles at
 // m = 4096), twiddles as for launch_encode_reg.

@@ -343,6 +343,65 @@ int rs_reconstruct_rows_dev(rs_codec *codec, uint8_t *const *d_shards, const uin
 int rs_reconstruct_rows_dev_batch(rs_codec *codec, uint8_t *base, size_t row_stride, size_t stripe_stride,
                                   size_t nstripes, const uint8_t *present, const uint8_t *required,
                                   size_t shard_size, void *stream);
+/* Strided form with a (present, required) pair per stripe: the selective
+ * reconstruct of a store that rotates or hashes its shard order per object.
+ * Stripe z of the slab uses row pattern_of[z] of both tables (npatterns rows of
+ * k+p flags each, 1 .. 65536 rows; equal rows and rows no stripe names are
+ * fine) and rebuilds exactly its rows with !present[i] && required[i].
+ * required == NULL: every missing row, the set recover_all = 1 names, so the
+ * call expresses all that rs_reconstruct_dev_batch_patterns does.  pattern_of is
+ * a HOST array; the three arrays may be freed on return.
+ * Per stripe the result is bit for bit what rs_reconstruct_rows_dev_batch
+ * writes for that stripe alone with that pair: the reference's Reconstruct for
+ * the same `present` on every input, with the exact locators of the pattern
+ * (the reference-keyed GF(2^8) inversion cache is neither read nor stored).  A
+ * stripe with nothing to rebuild is not touched; no byte outside the rebuilt
+ * rows is written.
+ * Errors, all decided before any device call, in the order of
+ * rs_reconstruct_dev_batch_patterns (a non-NULL required adds none): NULL codec
+ * / base / present / pattern_of, nstripes > INT32_MAX, a multi-device codec,
+ * npatterns == 0 or > 65536, a pattern_of[z] >= npatterns: RS_ERR_INVALID_ARG;
+ * shard_size == 0 or a table row with no shard present: RS_ERR_SHARD_NO_DATA;
+ * a table row (named by a stripe or not) with fewer than k present:
+ * RS_ERR_TOO_FEW_SHARDS; shard_size % 64: RS_ERR_INVALID_SHARD_SIZE; the
+ * stride rules of rs_reconstruct_dev_batch: RS_ERR_INVALID_ARG; a geometry
+ * whose reconstruct panics in the reference: RS_ERR_PANIC.  Then nstripes == 0
+ * or no stripe with anything to rebuild: RS_OK, nothing launched.
+ * Stream semantics of rs_reconstruct_rows_dev_batch.
+ *
+ * The tier is chosen per stripe by its wanted-row count, with the thresholds
+ * of rs_reconstruct_rows_dev_batch except at n = 256, where this call's direct
+ * tier takes t <= 7 (below); one call may mix both.  Direct stripes are
+ * grouped by that count, one launch of the streaming kernel per count (one
+ * launch in all where every stripe misses one row) over a device list of
+ * (stripe, descriptor) entries: a workgroup reads its entry and the descriptor
+ * (tables, index lists, present-row count) with scalar loads.  The tables of
+ * the distinct pairs live in one device blob per stripe range, built on first
+ * use and cached per codec (4 sets, least recently used, keyed by the pairs in
+ * order of first use); table bytes per pair t * np * 80 in GF(2^16): 12720 for
+ * one erasure at 128+32.  The other stripes run the kernels of
+ * rs_reconstruct_dev_batch_patterns with their output set narrowed to the
+ * wanted rows (pattern sets keyed by the selection).  Both kinds of tables
+ * share that call's 64 MiB / 2^18-stripe bounds per stripe range.
+ * Measured on one MI355X, us per stripe (profiles/rows_patterns_c4.txt,
+ * DESIGN.md 4.14; a pass over the slab to a device synchronise, five
+ * alternating passes, medians; the passes of a route agree within 1 % at
+ * 128+32 and 6 % at 1024+256): this call / rs_reconstruct_dev_batch_patterns on
+ * the same slab / one rs_reconstruct_rows_dev_batch per pair over a slab sorted
+ * by pair / rs_reconstruct_rows_dev_batch with one pair for all.  128+32 x
+ * 1 MiB, 256 stripes, shard order rotated per stripe, one device lost (160
+ * pairs, one row each): 29.3 / 95.7 / 195.6 / 30.3; 32 devices lost, the first
+ * missing data row wanted: 24.1 / 108.8 / 194.4 / 25.0.  1024+256 x 256 KiB,
+ * 8 stripes, 8 pairs: one erasure 87.8 / 535.1 / 495.5 / 95.1; 256 erasures
+ * 72.0 / 557.3 / 398.0 / 77.3.  Tier choice on the 32-erasure rotated slab,
+ * direct kernel / restricted transform: t = 6 70.6 / 92.1, t = 7 81.2 / 92.2,
+ * t = 8 92.0 / 92.6; at 1024+256 t = 8 434.8 / 515.7, t = 9 498.7 / 513.4.
+ * Not measured: kernel time alone, set building, GF(2^8), n = 512 and 1024. */
+int rs_reconstruct_rows_dev_batch_patterns(rs_codec *codec, uint8_t *base, size_t row_stride, size_t stripe_stride,
+                                           size_t nstripes, const uint8_t *present /* npatterns x (k+p) */,
+                                           const uint8_t *required /* npatterns x (k+p), or NULL */,
+                                           size_t npatterns, const uint32_t *pattern_of /* nstripes, host */,
+                                           size_t shard_size, void *stream);
 /* Host memory, through the host pipeline of rs_reconstruct (pinned, pageable
  * and zero-copy rows; single- and multi-device codecs, where the locators are
  * computed once and every part gets the same `required`).  lens[i] == 0 marks

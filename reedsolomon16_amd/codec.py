@@ -796,6 +796,34 @@ class ReedSolomon:
                                                      self._flags(present, "present"), self._flags(required, "required"),
                                                      S, _stream_handle(stream)))
 
+    def reconstruct_rows_dev_batch_patterns(self, slab, patterns, required, pattern_of: Sequence[int],
+                                            stream=None) -> None:
+        """reconstruct_rows_dev_batch with a (present, required) pair per stripe
+        (rs_reconstruct_rows_dev_batch_patterns): `patterns` and `required` are
+        [npatterns, k+p] tables of flags, stripe z of the [nstripes, k+p, S]
+        slab uses row pattern_of[z] of both and rebuilds its missing and
+        required rows.  required=None: every missing row.  A stripe with
+        nothing to rebuild is left alone."""
+        n, S = self._slab(slab)
+        table = np.ascontiguousarray(np.asarray(patterns, dtype=bool).astype(np.uint8))
+        if table.ndim != 2 or table.shape[1] != self.total_shards():
+            raise ErrTooFewShards("patterns must have %d flags per row" % self.total_shards())
+        req = None
+        if required is not None:
+            req = np.ascontiguousarray(np.asarray(required, dtype=bool).astype(np.uint8))
+            if req.shape != table.shape:
+                raise ErrTooFewShards("required must have the shape of patterns")
+        of = np.ascontiguousarray(np.asarray(pattern_of, dtype=np.int64))
+        if of.shape != (n,):
+            raise TypeError("pattern_of must name one pattern per stripe")
+        if of.size and (of.min() < 0 or of.max() >= 1 << 32):
+            raise ErrInvalidArg("pattern_of entries must be pattern numbers")
+        of = of.astype(np.uint32)
+        _check(self._L.rs_reconstruct_rows_dev_batch_patterns(
+            self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, table.ctypes.data_as(C.POINTER(C.c_uint8)),
+            req.ctypes.data_as(C.POINTER(C.c_uint8)) if req is not None else None, table.shape[0],
+            of.ctypes.data_as(C.POINTER(C.c_uint32)), S, _stream_handle(stream)))
+
     def encode_dev_batch(self, slab, stream=None) -> None:
         """Encode a [nstripes, k+p, S] uint8 CUDA tensor in one launch.  Any
         view whose rows are contiguous works (stride(2) == 1): stripe and row

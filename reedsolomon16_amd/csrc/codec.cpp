@@ -217,6 +217,21 @@ struct RowsPlan : StreamUses {
     }
 };
 
+// The device tables of a set of (present, rows rebuilt) pairs
+// (rs_reconstruct_rows_dev_batch_patterns' direct tier): per pair what a
+// RowsPlan holds, in one blob (gf_host.hpp make_rows_set), and the array of
+// descriptors that point into it.
+struct RowsSet : StreamUses {
+    DevBuf<uint8_t> blob;
+    const RowsPattern *desc = nullptr;  // device array
+    std::vector<int> first_desc;        // pair q's descriptors: [first_desc[q], first_desc[q + 1])
+    std::vector<int> desc_t;            // rows each descriptor rebuilds (1..kDecGroup)
+    ~RowsSet() {
+        drain();
+        blob.release();
+    }
+};
+
 // A small bounded LRU, most recent first.  find() moves a hit to the front;
 // put() inserts at the front and evicts past the cache's capacity, which runs
 // the evicted value's destructor (a DevPlan / UpdPlan waits there for its last
@@ -320,6 +335,9 @@ struct rs_codec {
     // one set holds every pattern of a call (or of a stripe range of it), so a
     // rotated layout's 160 patterns take one slot here and none of dplan_cache
     Lru<std::vector<uint8_t>, std::unique_ptr<PatternSet>, 4> pset_cache;
+    // rows sets keyed by their (present, rows rebuilt) pairs in order of first
+    // use: the direct tier's counterpart of pset_cache
+    Lru<std::vector<uint8_t>, std::unique_ptr<RowsSet>, 4> rset_cache;
     // scrub (rs_verify_dev_batch_map / rs_locate_dev / rs_scrub_dev_batch): the
     // ratio map of the data shards (built on the first locate), the device
     // tables of a repaired row keyed by its data shard (UpdPlan::tw: the three
@@ -386,6 +404,7 @@ struct rs_codec {
         uplan_cache.items.clear();
         rowsplan_cache.items.clear();
         pset_cache.items.clear();
+        rset_cache.items.clear();
         fixplan_cache.items.clear();
         scrub_rows.release(); scrub_dev.release();
         scrub_host.release();
@@ -2221,13 +2240,20 @@ constexpr size_t kPatMaxStripes = 1u << 18;
 // different, each with something to rebuild), built and uploaded on first use.
 // The locators are the exact ones of each pattern, computed here: neither the
 // reference-keyed inversion cache nor the 16-slot plan caches see these patterns.
-int pattern_set(rs_codec *c, const std::vector<const uint8_t *> &pats, bool all, PatternSet **out) {
+// wants != nullptr (rs_reconstruct_rows_dev_batch_patterns): per pattern the
+// k+p flags of the rows to rebuild, all of them missing; `all` is not read and
+// the key is (2, each pattern's present flags followed by its wanted flags).
+int pattern_set(rs_codec *c, const std::vector<const uint8_t *> &pats, bool all, PatternSet **out,
+                const std::vector<const uint8_t *> *wants = nullptr) {
     const int total = c->total, n = c->n;
     std::vector<uint8_t> key;
-    key.reserve(pats.size() * total + 1);
-    key.push_back(all ? 1 : 0);
-    for (const uint8_t *p : pats)
-        for (int i = 0; i < total; i++) key.push_back(p[i] != 0);
+    key.reserve(pats.size() * total * (wants ? 2 : 1) + 1);
+    key.push_back(wants ? 2 : all ? 1 : 0);
+    for (size_t q = 0; q < pats.size(); q++) {
+        for (int i = 0; i < total; i++) key.push_back(pats[q][i] != 0);
+        if (wants)
+            for (int i = 0; i < total; i++) key.push_back((*wants)[q][i] != 0);
+    }
     if (auto *hit = c->pset_cache.find(key)) {
         *out = hit->get();
         return RS_OK;
@@ -2240,7 +2266,9 @@ int pattern_set(rs_codec *c, const std::vector<const uint8_t *> &pats, bool all,
     for (size_t q = 0; q < pats.size(); q++) {
         for (int i = 0; i < total; i++) present[i] = pats[q][i] != 0, erased[i] = !present[i];
         if (!error_locators(*c->F, c->k, c->p, erased.data(), el)) return RS_ERR_PANIC;
-        if (int e = plan_reconstruct_new(c, present, Want(all), el, plans[q])) return e;
+        std::vector<uint8_t> rows;
+        if (wants) rows.assign((*wants)[q], (*wants)[q] + total);
+        if (int e = plan_reconstruct_new(c, present, wants ? Want(rows) : Want(all), el, plans[q])) return e;
         off[q] = bytes;
         bytes += pattern_layout(c, (int)plans[q].dst_shard.size()).total;
     }
@@ -2413,6 +2441,258 @@ int reconstruct_patterns_call(rs_codec *c, uint8_t *base, size_t row_stride, siz
             HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
             c->ring_used[slot] = true;
             HIP_TRY(ps->mark_used(s));
+        }
+        z0 = z1;
+    }
+    return dc.finish(RS_OK);
+}
+
+// ---- A (present, required) pair per stripe (rs_reconstruct_rows_dev_batch_patterns)
+static_assert(sizeof(RowsSetDesc) == sizeof(RowsPattern) && offsetof(RowsSetDesc, tw) == offsetof(RowsPattern, tw) &&
+                  offsetof(RowsSetDesc, src_idx) == offsetof(RowsPattern, src_idx) &&
+                  offsetof(RowsSetDesc, dst_idx) == offsetof(RowsPattern, dst_idx) &&
+                  offsetof(RowsSetDesc, np) == offsetof(RowsPattern, np) && offsetof(RowsSetDesc, t) == offsetof(RowsPattern, t),
+              "make_rows_set writes the kernel's descriptors");
+
+// The per-stripe tier choice: rows_direct with a threshold of this call's own
+// at n = 256.  The stripes the direct tier does not take run the per-stripe-
+// pattern reconstruct kernels, which cost more than the one-pattern restricted
+// transform kRowsDirectAuto was measured against, so the direct kernel wins one
+// row later (profiles/rows_patterns_c4.txt; 128+32 x 1 MiB, 256
+// rotated stripes of 32 erasures, us per stripe direct / restricted): t = 6
+// 70.6 / 92.1, t = 7 81.2 / 92.2, t = 8 92.0 / 92.6 (inside the spread: not
+// taken), t = 9 (5 + 4) 92.2 / 92.9.  At 1024+256 (n = 2048) t = 8 434.8 /
+// 515.7 confirms kRowsDirectAuto2048; t = 9 (5 + 4) 498.7 / 513.4 is left to
+// the restricted tier as there.  Other n are unmeasured and keep kRowsDirectAuto.
+constexpr int kRowsPatDirectAuto256 = 7;
+
+bool rows_pat_direct(const rs_codec *c, int t) {
+    if (c->n == 256 && g_path_rows_direct.load(std::memory_order_relaxed) < 0) return c->dec_ok && t <= kRowsPatDirectAuto256;
+    return rows_direct(c, t);
+}
+
+// The cached device set of `pairs` (all different, each with something to
+// rebuild; wanted rows are missing ones), built and uploaded on first use from
+// the exact locators of each pattern: rowsplan_cache, plan_cache, dplan_cache
+// and el_cache do not see these patterns.
+int rows_set(rs_codec *c, const std::vector<RowsSetPair> &pairs, RowsSet **out) {
+    const int total = c->total;
+    std::vector<uint8_t> key;
+    key.reserve(pairs.size() * total * 2);
+    for (const RowsSetPair &p : pairs) {
+        for (int i = 0; i < total; i++) key.push_back(p.present[i] != 0);
+        for (int i = 0; i < total; i++) key.push_back(p.wanted[i] != 0);
+    }
+    if (auto *hit = c->rset_cache.find(key)) {
+        *out = hit->get();
+        return RS_OK;
+    }
+    auto rs = std::make_unique<RowsSet>();
+    std::vector<uint8_t> h;
+    if (!make_rows_set(*c->F, c->k, c->p, c->dec_ifft_logs, c->dec_fft_logs, pairs, kDecGroup, 0, h, rs->first_desc))
+        return RS_ERR_PANIC;
+    HIP_TRY(rs->blob.ensure(h.size()));
+    // the image holds offsets: make them addresses of the blob
+    const uint64_t g = (uint64_t)(uintptr_t)rs->blob.p;
+    RowsSetDesc *d = (RowsSetDesc *)h.data();
+    for (int i = 0; i < rs->first_desc.back(); i++) {
+        d[i].tw += g, d[i].src_idx += g, d[i].dst_idx += g;
+        rs->desc_t.push_back(d[i].t);
+    }
+    HIP_TRY(hipMemcpy(rs->blob.p, h.data(), h.size(), hipMemcpyHostToDevice));
+    rs->desc = (const RowsPattern *)rs->blob.p;
+    *out = c->rset_cache.put(std::move(key), std::move(rs))->get();  // an eviction waits for that set's last launch
+    return RS_OK;
+}
+
+// rs_reconstruct_rows_dev_batch_patterns after its NULL checks.
+int reconstruct_rows_patterns_call(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride,
+                                   size_t nstripes, const uint8_t *present, const uint8_t *required, size_t npat,
+                                   const uint32_t *pattern_of, size_t S, void *stream) {
+    const int total = c->total, k = c->k;
+    for (size_t z = 0; z < nstripes; z++)
+        if (pattern_of[z] >= npat) return RS_ERR_INVALID_ARG;
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    // per table row: normalized present flags, the rows the call rebuilds
+    // (missing and required; required == NULL: every missing row), their counts
+    std::vector<uint8_t> pres(npat * total), want(npat * total);
+    std::vector<int> todo(npat, 0), npres(npat, 0);
+    bool too_few = false;
+    for (size_t q = 0; q < npat; q++) {
+        for (int i = 0; i < total; i++) {
+            const size_t at = q * total + i;
+            pres[at] = present[at] != 0;
+            want[at] = !pres[at] && (!required || required[at]);
+            npres[q] += pres[at];
+            todo[q] += want[at];
+        }
+        if (npres[q] == 0) return RS_ERR_SHARD_NO_DATA;
+        too_few = too_few || npres[q] < k;
+    }
+    if (too_few) return RS_ERR_TOO_FEW_SHARDS;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (row_stride < S || (nstripes > 1 && stripe_stride < (size_t)total * row_stride)) return RS_ERR_INVALID_ARG;
+    if ((long)c->m + k > (long)c->F->order) return RS_ERR_PANIC;  // error_locators / decode_schedule: the reference panics
+    bool any = false;
+    for (size_t z = 0; z < nstripes && !any; z++) any = todo[pattern_of[z]] > 0;
+    if (!any) return RS_OK;
+
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    if (int e = build_decode_plan(c)) return e;
+    if (!c->dec_ok) return RS_ERR_PANIC;
+    if (!rec_lds_ok(c)) {
+        // multi-pass codecs (n > 2048: never the direct tier): stripe by stripe
+        std::vector<uint8_t *> rows(total);
+        for (size_t z = 0; z < nstripes; z++) {
+            const size_t q = pattern_of[z];
+            if (!todo[q]) continue;
+            for (int i = 0; i < total; i++) rows[i] = base + z * stripe_stride + (uint64_t)i * row_stride;
+            const std::vector<uint8_t> pr(pres.begin() + q * total, pres.begin() + (q + 1) * total);
+            const std::vector<uint8_t> rq(want.begin() + q * total, want.begin() + (q + 1) * total);
+            if (int e = reconstruct_device(c, rows.data(), pr, S, Want(rq), s)) return e;
+        }
+        return RS_OK;
+    }
+    // Equal pairs share a descriptor: canon[q] is the first referenced table
+    // row with q's present and wanted flags (-1: not looked at yet).
+    std::vector<int> canon(npat, -1);
+    std::map<std::vector<uint8_t>, int> seen;
+    auto canon_of = [&](size_t q) {
+        if (canon[q] < 0) {
+            std::vector<uint8_t> f(pres.begin() + q * total, pres.begin() + (q + 1) * total);
+            f.insert(f.end(), want.begin() + q * total, want.begin() + (q + 1) * total);
+            canon[q] = seen.emplace(std::move(f), (int)q).first->second;
+        }
+        return canon[q];
+    };
+    // Stripe ranges [z0, z1), each within the table budget (direct and
+    // restricted tables together) and the stripe limit.  Per range: one rows
+    // set and one launch per wanted-row count for the direct stripes, one
+    // pattern set and one launch for the others.
+    std::vector<int> id_of(npat, -1);  // a canonical pair's number in the current range (pair or pattern)
+    std::vector<int> idx;              // restricted tier: descriptor per stripe of the range, -1: not its stripe
+    std::vector<RecStripe> direct;     // direct tier: (stripe of the range, pair of the range)
+    for (size_t z0 = 0; z0 < nstripes;) {
+        std::vector<RowsSetPair> pairs;
+        std::vector<const uint8_t *> pats, wants;
+        std::vector<int> members;
+        size_t bytes = 0, z1 = z0;
+        int nrest = 0;
+        idx.clear();
+        direct.clear();
+        for (; z1 < nstripes && z1 - z0 < kPatMaxStripes; z1++) {
+            const size_t q = pattern_of[z1];
+            if (!todo[q]) {
+                idx.push_back(-1);
+                continue;
+            }
+            const int cq = canon_of(q);
+            const bool dir = rows_pat_direct(c, todo[cq]);
+            if (id_of[cq] < 0) {
+                const size_t need = dir ? rows_set_pair_bytes(c->bits, npres[cq], todo[cq], kDecGroup)
+                                        : pattern_layout(c, todo[cq]).total + sizeof(RecPattern);
+                if (!members.empty() && bytes + need > kPatSetBudget) break;
+                bytes += need;
+                if (dir) {
+                    id_of[cq] = (int)pairs.size();
+                    pairs.push_back(RowsSetPair{pres.data() + (size_t)cq * total, want.data() + (size_t)cq * total});
+                } else {
+                    id_of[cq] = (int)pats.size();
+                    pats.push_back(pres.data() + (size_t)cq * total);
+                    wants.push_back(want.data() + (size_t)cq * total);
+                }
+                members.push_back(cq);
+            }
+            if (dir) {
+                direct.push_back(RecStripe{(int)(z1 - z0), id_of[cq]});
+                idx.push_back(-1);
+            } else {
+                idx.push_back(id_of[cq]);
+                nrest++;
+            }
+        }
+        for (int cq : members) id_of[cq] = -1;
+        if (!members.empty()) {
+            RowsSet *rs = nullptr;
+            PatternSet *ps = nullptr;
+            // direct stripes by wanted-row count: one list, one launch each; a
+            // pair of more than kDecGroup rows is in several lists
+            std::vector<RecStripe> lists[kDecGroup + 1];
+            if (!pairs.empty()) {
+                if (int e = rows_set(c, pairs, &rs)) return e;
+                for (const RecStripe &st : direct)
+                    for (int d = rs->first_desc[st.pat]; d < rs->first_desc[st.pat + 1]; d++)
+                        lists[rs->desc_t[d]].push_back(RecStripe{st.stripe, d});
+            }
+            if (!pats.empty())
+                if (int e = pattern_set(c, pats, false, &ps, &wants)) return e;
+            const bool bs = ps && ps->bs_ok && g_path_pat_tier.load(std::memory_order_relaxed) != 1;
+            // one ring slot: the restricted tier's list, then the direct lists
+            size_t off[kDecGroup + 1] = {};
+            size_t ib = ps ? align256(bs ? (size_t)nrest * sizeof(RecStripe) : idx.size() * sizeof(int)) : 0;
+            for (int t = 1; t <= kDecGroup; t++) {
+                off[t] = ib;
+                ib += align256(lists[t].size() * sizeof(RecStripe));
+            }
+            int slot = 0;
+            uint8_t *h = nullptr, *g = nullptr;
+            if (int e = ring_acquire(c, ib, slot, h, g)) return e;
+            if (ps) {
+                if (bs) {
+                    RecStripe *list = (RecStripe *)h;
+                    int na = 0;
+                    for (size_t i = 0; i < idx.size(); i++)
+                        if (idx[i] >= 0) list[na++] = RecStripe{(int)i, idx[i]};
+                } else {
+                    std::memcpy(h, idx.data(), idx.size() * sizeof(int));
+                }
+            }
+            for (int t = 1; t <= kDecGroup; t++)
+                if (!lists[t].empty()) std::memcpy(h + off[t], lists[t].data(), lists[t].size() * sizeof(RecStripe));
+            HIP_TRY(hipMemcpyAsync(g, h, ib, hipMemcpyHostToDevice, s));
+            uint8_t *rb = base + z0 * stripe_stride;
+            for (int t = 1; t <= kDecGroup; t++) {
+                if (lists[t].empty()) continue;
+                DecodeRowsPatArgs da{};
+                da.base = rb;
+                da.row_stride = row_stride;
+                da.stripe_stride = stripe_stride;
+                da.pat = rs->desc;
+                da.list = (const RecStripe *)(g + off[t]);
+                da.S = S;
+                da.nlist = (int)lists[t].size();
+                da.nt = t;
+                HIP_TRY(launch_decode_rows_patterns(c->bits, da, s));
+            }
+            if (ps) {
+                DevPlan none;  // the shared fields only: the descriptors carry the pattern's
+                RecArgs ra = rec_args(c, &none, S);
+                ra.base = rb;
+                ra.stride = row_stride;
+                ra.stripe_stride = stripe_stride;
+                ra.nstripes = (int)(z1 - z0);
+                if (bs) {
+                    RecBsPatArgs ba{};
+                    ba.a = ra;
+                    ba.pat = ps->desc;
+                    ba.tiles = (const RecStripe *)g;
+                    ba.nactive = nrest;
+                    std::memcpy(ba.code1, ps->code1, sizeof(ba.code1));
+                    HIP_TRY(launch_rec_bs256_patterns(ba, s));
+                } else {
+                    RecPatArgs pa{};
+                    pa.a = ra;
+                    pa.pat = ps->desc;
+                    pa.pat_of = (const int *)g;
+                    HIP_TRY(launch_rec_lds_patterns(c->bits, c->logn, c->dec_sub, pa, s));
+                }
+                HIP_TRY(ps->mark_used(s));
+            }
+            HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+            c->ring_used[slot] = true;
+            if (rs) HIP_TRY(rs->mark_used(s));
         }
         z0 = z1;
     }
@@ -2795,6 +3075,16 @@ int rs_reconstruct_dev_batch_patterns(rs_codec *c, uint8_t *base, size_t row_str
     if (npatterns == 0 || npatterns > 65536) return RS_ERR_INVALID_ARG;
     return reconstruct_patterns_call(c, base, row_stride, stripe_stride, nstripes, present, npatterns, pattern_of, S,
                                      recover_all != 0, stream);
+}
+
+int rs_reconstruct_rows_dev_batch_patterns(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride,
+                                           size_t nstripes, const uint8_t *present, const uint8_t *required,
+                                           size_t npatterns, const uint32_t *pattern_of, size_t S, void *stream) {
+    if (!c || !base || !present || !pattern_of || nstripes > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    if (npatterns == 0 || npatterns > 65536) return RS_ERR_INVALID_ARG;
+    return reconstruct_rows_patterns_call(c, base, row_stride, stripe_stride, nstripes, present, required, npatterns,
+                                          pattern_of, S, stream);
 }
 
 int rs_reconstruct_rows_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,

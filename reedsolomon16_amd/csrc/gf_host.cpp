@@ -1,6 +1,7 @@
 // Host-side finite-field tables and GPU twiddle-table construction (see gf_host.hpp).
 #include "gf_host.hpp"
 
+#include <cstring>
 #include <mutex>
 
 namespace rs {
@@ -528,6 +529,67 @@ void make_decode_tables(const Field &F, int k, int p, const uint8_t *erased, con
                 o += twd;
             }
     }
+}
+
+namespace {
+size_t rows_set_align(size_t x) { return (x + 255) & ~(size_t)255; }
+}  // namespace
+
+int rows_set_descs(int t, int group) { return (t + group - 1) / group; }
+
+size_t rows_set_pair_bytes(int bits, int np, int t, int group) {
+    return rows_set_align((size_t)t * np * tw_dwords(bits) * 4) + rows_set_align((size_t)np * 4) +
+           rows_set_align((size_t)t * 4) + (size_t)rows_set_descs(t, group) * sizeof(RowsSetDesc);
+}
+
+bool make_rows_set(const Field &F, int k, int p, const std::vector<uint32_t> &ifft, const std::vector<uint32_t> &fft,
+                   const std::vector<RowsSetPair> &pairs, int group, uint64_t base, std::vector<uint8_t> &image,
+                   std::vector<int> &first_desc) {
+    const int total = k + p, twd = tw_dwords(F.bits);
+    const size_t npairs = pairs.size();
+    std::vector<std::vector<int>> src(npairs), dst(npairs);
+    std::vector<size_t> off(npairs);
+    first_desc.assign(npairs + 1, 0);
+    for (size_t q = 0; q < npairs; q++) {
+        for (int i = 0; i < total; i++) {
+            if (pairs[q].present[i]) src[q].push_back(i);
+            else if (pairs[q].wanted[i]) dst[q].push_back(i);
+        }
+        if (src[q].empty() || dst[q].empty()) return false;
+        first_desc[q + 1] = first_desc[q] + rows_set_descs((int)dst[q].size(), group);
+    }
+    size_t bytes = rows_set_align((size_t)first_desc[npairs] * sizeof(RowsSetDesc));
+    for (size_t q = 0; q < npairs; q++) {
+        off[q] = bytes;
+        bytes += rows_set_pair_bytes(F.bits, (int)src[q].size(), (int)dst[q].size(), group) -
+                 (size_t)(first_desc[q + 1] - first_desc[q]) * sizeof(RowsSetDesc);
+    }
+    image.assign(bytes, 0);
+    std::vector<uint8_t> erased(total);
+    std::vector<uint32_t> el;
+    for (size_t q = 0; q < npairs; q++) {
+        const int np = (int)src[q].size(), t = (int)dst[q].size();
+        for (int i = 0; i < total; i++) erased[i] = !pairs[q].present[i];
+        if (!error_locators(F, k, p, erased.data(), el)) return false;
+        const size_t o_tw = off[q], o_si = o_tw + rows_set_align((size_t)t * np * twd * 4);
+        const size_t o_di = o_si + rows_set_align((size_t)np * 4);
+        make_decode_tables(F, k, p, erased.data(), el, ifft, fft, dst[q].data(), t, (uint32_t *)(image.data() + o_tw));
+        std::memcpy(image.data() + o_si, src[q].data(), (size_t)np * 4);
+        std::memcpy(image.data() + o_di, dst[q].data(), (size_t)t * 4);
+        // ceil(t / group) descriptors of sizes as equal as t allows
+        const int nl = first_desc[q + 1] - first_desc[q];
+        for (int g = 0, j0 = 0, nt = 0; g < nl; g++, j0 += nt) {
+            nt = t / nl + (g < t % nl ? 1 : 0);
+            RowsSetDesc d;
+            d.tw = base + o_tw + (uint64_t)j0 * np * twd * 4;
+            d.src_idx = base + o_si;
+            d.dst_idx = base + o_di + (uint64_t)j0 * 4;
+            d.np = np;
+            d.t = nt;
+            std::memcpy(image.data() + (size_t)(first_desc[q] + g) * sizeof(RowsSetDesc), &d, sizeof(d));
+        }
+    }
+    return true;
 }
 
 bool generator_rows(const Field &F, int k, int p, int nrows, std::vector<uint32_t> &rows) {

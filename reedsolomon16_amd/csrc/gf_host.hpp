@@ -167,6 +167,34 @@ void make_decode_tables(const Field &F, int k, int p, const uint8_t *erased, con
                         const std::vector<uint32_t> &ifft_logs, const std::vector<uint32_t> &fft_logs, const int *rows,
                         int t, uint32_t *out);
 
+// ---- Rows set: the decode tables of several (present, wanted rows) pairs in
+// one blob (rs_reconstruct_rows_dev_batch_patterns, codec.cpp RowsSet).
+// Layout: the descriptor array, then per pair its t x np tables
+// (make_decode_tables from the pair's exact error_locators), its np present
+// shard indices and its t wanted ones, each part 256-byte aligned.  A pair
+// with t > group wanted rows takes ceil(t / group) descriptors of near-equal
+// row counts (as decode_rows_f splits its launches): each points at its own
+// rows of the pair's tables and wanted indices and shares the present indices.
+struct RowsSetDesc {     // kernels.hpp RowsPattern with addresses as integers
+    uint64_t tw, src_idx, dst_idx;  // base + offset in the image
+    int32_t np, t;
+};
+struct RowsSetPair {
+    const uint8_t *present, *wanted;  // k+p flags each; a row is rebuilt when !present && wanted
+};
+// Descriptors and bytes (descriptors included) a pair with np present and t
+// rebuilt rows adds to a set.
+int rows_set_descs(int t, int group);
+size_t rows_set_pair_bytes(int bits, int np, int t, int group);
+// Builds the image for a blob that will live at address `base` (0: the
+// descriptors hold plain offsets).  first_desc: npairs + 1 entries, pair q's
+// descriptors are [first_desc[q], first_desc[q + 1]).  False where
+// error_locators refuses the geometry (the reference panics) or a pair has
+// nothing to rebuild.
+bool make_rows_set(const Field &F, int k, int p, const std::vector<uint32_t> &ifft_logs,
+                   const std::vector<uint32_t> &fft_logs, const std::vector<RowsSetPair> &pairs, int group,
+                   uint64_t base, std::vector<uint8_t> &image, std::vector<int> &first_desc);
+
 // ---- Scrub: which single data shard explains a syndrome.
 // Rows [0, nrows) of the encode's generator matrix: rows[i * k + j] = G[i][j].
 // With every data shard present and every parity shard erased, the decode map

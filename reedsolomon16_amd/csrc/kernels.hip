@@ -2422,6 +2422,103 @@ hipError_t launch_decode_rows(int bits, const DecodeRowsArgs &a, hipStream_t s) 
     return narrow ? decode_rows_f<F8<2>>(a, s) : decode_rows_f<F8<4>>(a, s);
 }
 
+// ---------------------------------------------------------------- direct decode, a pattern per stripe
+// k_decode_rows over a list of (stripe, descriptor) pairs
+// (rs_reconstruct_rows_dev_batch_patterns, kernels.hpp DecodeRowsPatArgs):
+// every stripe of a launch rebuilds NT rows, each from the tables and index
+// lists of its own descriptor.
+namespace {
+
+typedef __attribute__((address_space(4))) const RecStripe dec_cstripe_t;
+typedef __attribute__((address_space(4))) const RowsPattern dec_cpat_t;
+
+// List entry blockIdx.y + y0.  The entry and its descriptor are the same for
+// the whole workgroup and read-only for the launch: scalar loads through the
+// constant address space (as k_rec_lds_pat reads its descriptor).  The loop is
+// k_decode_rows's own (a copy: that kernel's 64 instantiations keep their
+// registers); np differs between the stripes of a launch but not within a
+// wave, so the loop bound is wave-uniform.  All addresses are 64-bit.
+template <class F, int NT>
+__global__ void __launch_bounds__(256, 2) k_decode_rows_pat(DecodeRowsPatArgs a, int y0) {
+    typedef typename F::Vec V;
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    dec_cstripe_t &e = ((dec_cstripe_t *)a.list)[(uint64_t)blockIdx.y + (uint64_t)y0];
+    dec_cpat_t &d = ((dec_cpat_t *)a.pat)[e.pat];
+    uint8_t *sb = a.base + (uint64_t)e.stripe * a.stripe_stride;
+    const int np = d.np;
+    const uint32_t *tw = d.tw;  // table (j, i) at tw + (j * np + i) * TWD
+    upd_cint_t *si = (upd_cint_t *)d.src_idx, *di = (upd_cint_t *)d.dst_idx;
+    auto srow = [&](int i) -> const uint8_t * { return sb + (uint64_t)si[i] * a.row_stride; };
+    V acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; j++) acc[j] = F::zero();
+    const uint64_t trow = (uint64_t)np * F::TWD;
+    int i = 0;
+    for (; i + kDecRows <= np; i += kDecRows) {
+        V x[kDecRows];
+#pragma unroll
+        for (int q = 0; q < kDecRows; q++) x[q] = F::load(srow(i + q), u);
+#pragma unroll
+        for (int q = 0; q < kDecRows; q++) {
+            UpdMasks<F> mk;
+            mk.prepare(x[q]);
+#pragma unroll
+            for (int j = 0; j < NT; j++) {
+                const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)(i + q) * F::TWD);
+                mk.mul_add(acc[j], tb.v);
+            }
+        }
+    }
+    for (; i < np; i++) {
+        UpdMasks<F> mk;
+        mk.prepare(F::load(srow(i), u));
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)i * F::TWD);
+            mk.mul_add(acc[j], tb.v);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NT; j++) F::store(sb + (uint64_t)di[j] * a.row_stride, u, acc[j]);
+}
+
+template <class F, int NT>
+hipError_t decode_pat_group(const DecodeRowsPatArgs &a, hipStream_t s) {
+    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
+    return for_y(a.nlist, [&](int y0, int ny) {
+        hipLaunchKernelGGL((k_decode_rows_pat<F, NT>), dim3(grid_x(units).x, ny), dim3(256), 0, s, a, y0);
+    });
+}
+
+template <class F>
+hipError_t decode_rows_pat_f(const DecodeRowsPatArgs &a, hipStream_t s) {
+    static_assert(kDecGroup == 8, "decode_rows_pat_f dispatches group sizes 1..8");
+    switch (a.nt) {
+        case 1: return decode_pat_group<F, 1>(a, s);
+        case 2: return decode_pat_group<F, 2>(a, s);
+        case 3: return decode_pat_group<F, 3>(a, s);
+        case 4: return decode_pat_group<F, 4>(a, s);
+        case 5: return decode_pat_group<F, 5>(a, s);
+        case 6: return decode_pat_group<F, 6>(a, s);
+        case 7: return decode_pat_group<F, 7>(a, s);
+        default: return decode_pat_group<F, 8>(a, s);
+    }
+}
+
+}  // namespace
+
+// Unit widths by launch_decode_rows's grid rule over the list's stripes.
+hipError_t launch_decode_rows_patterns(int bits, const DecodeRowsPatArgs &a, hipStream_t s) {
+    constexpr uint64_t kDecMinBlocks = 1024;
+    if (a.nt <= 0 || a.nt > kDecGroup || a.nlist <= 0 || a.S == 0 || a.S % 64) return hipErrorInvalidValue;
+    if (!a.base || !a.pat || !a.list) return hipErrorInvalidValue;
+    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * (uint64_t)a.nlist;
+    const bool narrow = pick_narrow(wide_blocks < kDecMinBlocks);
+    if (bits == 16) return narrow ? decode_rows_pat_f<F16<2>>(a, s) : decode_rows_pat_f<F16<4>>(a, s);
+    return narrow ? decode_rows_pat_f<F8<2>>(a, s) : decode_rows_pat_f<F8<4>>(a, s);
+}
+
 // ---------------------------------------------------------------- syndrome scan (scrub)
 // Stored parity rows against freshly encoded ones (kernels.hpp ScanArgs):
 // k_update's shape without a product.  A stream: every byte of the 2 p rows is

@@ -295,6 +295,26 @@ struct DecodeRowsArgs {
 // Runs the t wanted rows as ceil(t / kDecGroup) launches on s.
 hipError_t launch_decode_rows(int bits, const DecodeRowsArgs &a, hipStream_t s);
 
+// The same with a (present, wanted rows) pair per stripe
+// (rs_reconstruct_rows_dev_batch_patterns): what DecodeRowsArgs holds per
+// pair, as one descriptor in HBM (codec.cpp RowsSet; gf_host.hpp RowsSetDesc
+// is its host image), and a launch over a device list of (stripe, descriptor)
+// entries whose descriptors all rebuild nt rows.  Strided form only.
+struct RowsPattern {
+    const uint32_t *tw;             // t x np tables, (j, i) at (j*np + i) * tw_dwords
+    const int *src_idx, *dst_idx;   // np present shard indices, t wanted ones
+    int np, t;
+};
+struct DecodeRowsPatArgs {
+    uint8_t *base;  // shard i of stripe z at base + z*stripe_stride + i*row_stride
+    uint64_t row_stride, stripe_stride;
+    const RowsPattern *pat;  // device array
+    const RecStripe *list;   // device array, nlist entries; every pat[list[].pat].t == nt
+    uint64_t S;
+    int nlist, nt;           // 1 <= nt <= kDecGroup
+};
+hipError_t launch_decode_rows_patterns(int bits, const DecodeRowsPatArgs &a, hipStream_t s);
+
 
 // ---- Syndrome scan of one stripe (scrub): compares the p stored parity rows
 // with the p rows a fresh encode of the stored data gave, writes neither.

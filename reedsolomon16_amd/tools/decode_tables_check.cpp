@@ -6,10 +6,14 @@
 // table evaluated the way the kernel does equals the field's own multiply by
 // its coefficient, both entry points agree, a codeword's erased rows come back
 // through the coefficients, and bad rows are refused.
+// Then builds the host image of a rows set (make_rows_set, the tables of
+// rs_reconstruct_rows_dev_batch_patterns' direct tier) for three pairs at 37+9
+// and two at GF(2^8) geometries and reads it back through its descriptors.
 // (The coefficients themselves are checked against the oracle by
 // tests/test_rows_cpu.py.)
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 #include <vector>
 
 #include "../csrc/gf_host.hpp"
@@ -99,9 +103,122 @@ void run(int bits, int k, int p, const std::vector<int> &erased_rows, const std:
                !decode_coefficients(F, k, p, erased.data(), el, -1, co.data()),
            "row out of range", bits, k, p);
 }
+
+// The host image of a rows set (make_rows_set) for `pairs` of (missing rows,
+// wanted rows among them): every table read through its descriptor's offsets,
+// as k_decode_rows_pat reads it, equals the field's multiply by the pair's
+// coefficient, the index lists are the pair's, a pair of more than `group`
+// wanted rows is split into near-equal descriptors, and a codeword's erased
+// rows come back.
+void run_set(int bits, int k, int p, const std::vector<std::pair<std::vector<int>, std::vector<int>>> &pairs,
+             int group) {
+    const Field &F = field(bits);
+    const int total = k + p, twd = tw_dwords(bits);
+    std::vector<uint32_t> il, fl, el;
+    if (!decode_schedule(F, k, p, il, fl)) {
+        expect(false, "decode_schedule", bits, k, p);
+        return;
+    }
+    std::vector<std::vector<uint8_t>> present(pairs.size(), std::vector<uint8_t>(total, 1)),
+        wanted(pairs.size(), std::vector<uint8_t>(total, 0));
+    std::vector<RowsSetPair> in;
+    size_t expect_bytes = 0;
+    int expect_descs = 0;
+    for (size_t q = 0; q < pairs.size(); q++) {
+        for (int i : pairs[q].first) present[q][i] = 0;
+        for (int i : pairs[q].second) wanted[q][i] = 1;
+        in.push_back(RowsSetPair{present[q].data(), wanted[q].data()});
+        const int np = total - (int)pairs[q].first.size(), t = (int)pairs[q].second.size();
+        expect_bytes += rows_set_pair_bytes(bits, np, t, group);
+        expect_descs += rows_set_descs(t, group);
+    }
+    std::vector<uint8_t> image;
+    std::vector<int> first;
+    if (!make_rows_set(F, k, p, il, fl, in, group, 0, image, first)) {
+        expect(false, "make_rows_set", bits, k, p);
+        return;
+    }
+    expect(first.size() == pairs.size() + 1 && first.back() == expect_descs, "descriptor count", bits, k, p);
+    const size_t desc_bytes = ((size_t)expect_descs * sizeof(RowsSetDesc) + 255) & ~(size_t)255;
+    expect(image.size() == expect_bytes - (size_t)expect_descs * sizeof(RowsSetDesc) + desc_bytes,
+           "image size == sum of rows_set_pair_bytes", bits, k, p);
+    // a codeword, one symbol per row
+    uint32_t seed = 4242u + (uint32_t)k * 31u + (uint32_t)p;
+    std::vector<uint32_t> word(total, 0), col, co(total);
+    for (int j = 0; j < k; j++) {
+        seed = seed * 1664525u + 1013904223u;
+        word[j] = (seed >> 8) & F.mod;
+        if (!generator_column(F, k, p, j, col)) {
+            expect(false, "generator_column", bits, k, p);
+            return;
+        }
+        for (int i = 0; i < p; i++)
+            if (col[i] && word[j]) word[k + i] ^= F.mul_log(word[j], F.log[col[i]]);
+    }
+    const RowsSetDesc *desc = (const RowsSetDesc *)image.data();
+    for (size_t q = 0; q < pairs.size(); q++) {
+        std::vector<uint8_t> erased(total);
+        for (int i = 0; i < total; i++) erased[i] = !present[q][i];
+        expect(error_locators(F, k, p, erased.data(), el), "error_locators", bits, k, p);
+        const int np = total - (int)pairs[q].first.size(), t = (int)pairs[q].second.size();
+        std::vector<int> rebuilt;
+        int lo = t, hi = 0;
+        for (int d = first[q]; d < first[q + 1]; d++) {
+            const RowsSetDesc &ds = desc[d];
+            expect(ds.np == np && ds.t >= 1 && ds.t <= group, "descriptor counts", bits, k, p);
+            lo = ds.t < lo ? ds.t : lo, hi = ds.t > hi ? ds.t : hi;
+            const size_t tw_end = ds.tw + (size_t)ds.t * np * twd * 4;
+            if (ds.tw % 4 || tw_end > image.size() || ds.src_idx + (size_t)np * 4 > image.size() ||
+                ds.dst_idx + (size_t)ds.t * 4 > image.size()) {
+                expect(false, "descriptor offsets inside the image", bits, k, p);
+                return;
+            }
+            const uint32_t *tw = (const uint32_t *)(image.data() + ds.tw);
+            const int *si = (const int *)(image.data() + ds.src_idx), *di = (const int *)(image.data() + ds.dst_idx);
+            for (int i = 0, ip = 0; i < total; i++)
+                if (present[q][i]) expect(si[ip++] == i, "present index list", bits, k, p);
+            for (int j = 0; j < ds.t; j++) {
+                const int row = di[j];
+                rebuilt.push_back(row);
+                expect(row >= 0 && row < total && wanted[q][row] && !present[q][row], "wanted index", bits, k, p);
+                if (row < 0 || row >= total) return;
+                expect(decode_coefficients(F, k, p, erased.data(), el, row, co.data()), "decode_coefficients", bits, k, p);
+                uint32_t acc = 0;
+                for (int i = 0; i < np; i++) {
+                    const uint32_t *tb = tw + ((size_t)j * np + i) * twd;
+                    seed = seed * 1664525u + 1013904223u;
+                    const uint32_t x = (seed >> 8) & F.mod, c = co[si[i]];
+                    expect(table_mul(F, tb, x) == (c ? F.mul_log(x, F.log[c]) : 0), "set table == field product", bits, k, p);
+                    acc ^= table_mul(F, tb, word[si[i]]);
+                }
+                expect(acc == word[row], "the set rebuilds a codeword's row", bits, k, p);
+            }
+        }
+        expect(rebuilt == pairs[q].second, "every wanted row once, ascending", bits, k, p);
+        expect(hi - lo <= 1, "near-equal groups", bits, k, p);
+    }
+}
 }  // namespace
 
 int main() {
+    // three pairs at 37+9: one erasure, nine erasures all wanted (two descriptors
+    // of 5 + 4 rows at group 8), nine erasures of which two are wanted
+    run_set(16, 37, 9, {{{20}, {20}},
+                        {{0, 5, 12, 13, 14, 36, 37, 40, 45}, {0, 5, 12, 13, 14, 36, 37, 40, 45}},
+                        {{1, 6, 13, 14, 15, 37, 38, 41, 45}, {6, 41}}},
+            8);
+    run_set(8, 100, 28, {{{0, 31, 32, 99, 100, 127}, {0, 99, 100, 127}}, {{7}, {7}}}, 8);
+    run_set(8, 10, 4, {{{0, 3, 11, 13}, {0, 3, 11, 13}}, {{9, 12}, {12}}}, 3);
+    {
+        // a pair with nothing to rebuild is refused
+        const Field &F = field(16);
+        std::vector<uint32_t> il, fl;
+        std::vector<uint8_t> pr(46, 1), wt(46, 0), image;
+        std::vector<int> first;
+        expect(decode_schedule(F, 37, 9, il, fl) &&
+                   !make_rows_set(F, 37, 9, il, fl, {RowsSetPair{pr.data(), wt.data()}}, 8, 0, image, first),
+               "a pair with nothing to rebuild is refused", 16, 37, 9);
+    }
     run(16, 37, 9, {0, 5, 36, 37, 40, 45, 12, 13, 14}, {0, 5, 36, 37, 40, 45, 12, 13, 14});
     run(16, 37, 9, {20}, {20});
     std::vector<int> many;

@@ -474,6 +474,67 @@ int rs_update_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, siz
                         const int *idx, int nidx, const uint8_t *d_new, size_t new_row_stride,
                         size_t new_stripe_stride, size_t shard_size, void *stream);
 
+/* Batched Update from a list of changed rows, a different set per stripe (no
+ * counterpart in the reference; the same linearity): the dirty rows of a
+ * write-back cache in one call.  The slab has rs_encode_dev_batch's layout.
+ * Entry e says that data shard idx_of[e] of stripe stripe_of[e] becomes the row
+ * at d_new + e*new_row_stride.  Entries come in any order; those of one stripe
+ * need be neither adjacent nor sorted.  stripe_of and idx_of are HOST arrays
+ * and may be freed on return.  For every stripe that is named the result is
+ * bit for bit what rs_update_dev_batch writes for that stripe alone with that
+ * stripe's index list: parity ^= G * (new ^ old), the new rows stored over the
+ * old ones, the stripe ends as the encoded stripe of the new data.  A stripe no
+ * entry names is neither read nor written; no byte outside the changed data
+ * rows and the parity rows of named stripes is written.  d_new is not written
+ * and must not overlap the slab.  Stream semantics of rs_update_dev_batch;
+ * nothing waits for a kernel.  Single-device codecs only.
+ * Errors, all decided before any device call, in this order: NULL codec /
+ * d_base / stripe_of / idx_of / d_new, nstripes or nrows > INT32_MAX, a
+ * multi-device codec, a stripe_of[e] >= nstripes, an idx_of[e] outside [0, k),
+ * the same (stripe, index) pair twice: RS_ERR_INVALID_ARG; shard_size == 0:
+ * RS_ERR_SHARD_NO_DATA; shard_size % 64: RS_ERR_INVALID_SHARD_SIZE; row_stride
+ * < shard_size, new_row_stride < shard_size, stripe_stride < (k+p)*row_stride
+ * when nstripes > 1: RS_ERR_INVALID_ARG; a geometry whose encode panics in the
+ * reference: RS_ERR_PANIC.  Then nrows == 0: RS_OK, nothing launched.
+ *
+ * The entries are grouped by stripe on the host; a stripe with t changed rows
+ * is cut into ceil(t / 8) groups of near-equal size (9 -> 5 + 4, as
+ * rs_update_dev_batch cuts its launches), and the groups of one size run as
+ * one launch of the streaming kernel (k_update_list) over a device list of
+ * group descriptors (stripe; per row its data index, table slot and entry
+ * number), read with scalar loads.  A lane owns its stripe's parity units for
+ * a launch, so the second group of a stripe goes into a second launch behind
+ * the first on the stream (a round), never into the same list.  The tables are
+ * per column: p tables of 96 bytes in GF(2^16) (32 in GF(2^8)), 3072 bytes per
+ * column at 128+32, shared by every stripe that changes that shard; the
+ * distinct columns of a call live in one device blob, built on first use and
+ * cached per codec (4 sets, least recently used, keyed by the sorted column
+ * list; a cached set that holds every column of a call serves it too).  Calls
+ * whose distinct columns pass rs_update_dev_batch's 32 MiB table bound run as
+ * several passes over subsets of the entries.  The call does not re-encode
+ * heavy stripes by itself: see rs_update_dev_batch for the crossover.
+ * Measured on one MI355X (profiles/update_list_c3.txt; 128+32 x
+ * 1 MiB, 256 stripes, routes alternating in one process, three passes of >= 1 s,
+ * HIP events, medians; the passes of a route agree within 0.4 %), us per dirty
+ * stripe: this call / one rs_update_dev_batch per dirty stripe / rs_update_dev_batch
+ * with one index for all (the ceiling).  One row per stripe, index z mod 128:
+ * 13.75 / 42.83 / 13.59; 1..4 rows per stripe: 14.66 / 55.80 / -; one stripe in
+ * eight dirty: 13.50 / 21.10 / 13.26; 1024+256 x 256 KiB, 8 stripes, a row
+ * each: 27.98 / 79.44 / 26.23.  The 1-7 % to the ceiling is kernel time (a
+ * kernel trace: 3.514 against 3.475 ms per launch): every stripe reads the
+ * tables of its own columns.  With many rows per stripe that costs more: 6
+ * rows, a different set per stripe, 27.57 against 18.36 for one set for all.
+ * Crossover to a full re-encode (31.05 us per stripe, plus copying the rows
+ * in): this call takes 27.57 / 31.41 / 34.21 / 38.72 us at t = 6 / 7 / 8 / 9
+ * rows in every stripe; with the rows copied in by an indexed torch copy the
+ * re-encode costs 54-65, with a copy at the stream's rate (not measured) about
+ * 34-35: re-encode from about nine changed rows per stripe on.  Not measured:
+ * GF(2^8) codecs, building a column set, lists beyond one ring slot. */
+int rs_update_dev_batch_list(rs_codec *codec, uint8_t *d_base, size_t row_stride, size_t stripe_stride,
+                             size_t nstripes, const uint32_t *stripe_of /* nrows, host */,
+                             const int *idx_of /* nrows, host */, size_t nrows, const uint8_t *d_new,
+                             size_t new_row_stride, size_t shard_size, void *stream);
+
 /* ---------------- Scrub (beyond the reference) ----------------
  * The reference's Verify returns one bool per stripe (leopard16.go:361-387) and
  * nothing says which shard of a bad stripe is wrong.  The code is linear, so
@@ -557,6 +618,18 @@ int rs_debug_error_locators(int field_bits, int data_shards, int parity_shards, 
  * row idx (the constants of the incremental update).  RS_ERR_INVALID_ARG for bad
  * arguments, RS_ERR_PANIC where the reference's encode panics. */
 int rs_debug_generator(int field_bits, int data_shards, int parity_shards, int idx, uint32_t *out /* p symbols */);
+/* The launches rs_update_dev_batch_list would make for a list of changed rows on
+ * a codec of data_shards data shards whose columns fit one pass, in stream
+ * order, after the same checks of the list (RS_ERR_INVALID_ARG for a NULL
+ * array, counts > INT32_MAX, a stripe_of[e] >= nstripes, an idx_of[e] outside
+ * [0, k), a repeated pair).  *nlaunches launches; launch l is launches[3 l ..
+ * 3 l + 2] = its group size nt, its round and its number of groups; stripes
+ * holds the stripe of each group, launch after launch; entries holds the nt
+ * entry numbers of each group, group after group.  The caller sizes launches
+ * for 3 * nrows and stripes and entries for nrows values (a launch has at
+ * least one group, a group at least one row). */
+int rs_debug_update_list_plan(int data_shards, size_t nstripes, const uint32_t *stripe_of, const int *idx_of,
+                              size_t nrows, int *nlaunches, int32_t *launches, uint32_t *stripes, uint32_t *entries);
 /* Row `row` of the decode map of an erasure pattern: out[i] is the constant by
  * which present shard i enters the shard the reference's Reconstruct puts into
  * `row` (0 at the missing shards), the constants of rs_reconstruct_rows_dev's

@@ -62,6 +62,8 @@ def lib() -> C.CDLL:
     L.rs_update_dev.argtypes = [vp, P(vp), P(vp), sz, vp]
     L.rs_encode_idx_dev.argtypes = [vp, vp, i32, P(vp), sz, vp]
     L.rs_update_dev_batch.argtypes = [vp, vp, sz, sz, i32, P(i32), i32, vp, sz, sz, sz, vp]
+    L.rs_update_dev_batch_list.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint32), P(i32), sz, vp, sz, sz, vp]
+    L.rs_debug_update_list_plan.argtypes = [i32, sz, P(C.c_uint32), P(i32), sz, P(i32), vp, vp, vp]
     L.rs_verify_dev_batch_map.argtypes = [vp, vp, sz, sz, i32, sz, vp, P(i32), vp]
     L.rs_locate_dev.argtypes = [vp, P(vp), sz, i32, P(i32), vp]
     L.rs_scrub_dev_batch.argtypes = [vp, vp, sz, sz, i32, sz, i32, vp, P(i32), vp]

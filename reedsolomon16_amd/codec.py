@@ -881,6 +881,32 @@ class ReedSolomon:
         _check(self._L.rs_update_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, arr, len(idx),
                                            new.data_ptr(), new.stride(1), new.stride(0), S, _stream_handle(stream)))
 
+    def update_dev_batch_list(self, slab, stripes: Sequence[int], idx: Sequence[int], new, stream=None) -> None:
+        """Replace data shard idx[e] of stripe stripes[e] of a [nstripes, k+p, S]
+        slab by new[e] (new: [len(idx), S]) for every entry e, in any order, and
+        update the parity rows of the stripes named to match, in place
+        (rs_update_dev_batch_list).  Both are uint8 CUDA tensors with contiguous
+        rows; strides come from the tensors."""
+        if slab.dim() != 3 or slab.shape[1] != self.total_shards():
+            raise TypeError("slab must be a [nstripes, k+p, S] uint8 CUDA tensor")
+        if not slab.is_cuda or slab.dtype.itemsize != 1 or slab.stride(2) != 1:
+            raise TypeError("slab rows must be contiguous uint8 on a CUDA device")
+        stripes = [int(z) for z in stripes]
+        idx = [int(i) for i in idx]
+        if len(stripes) != len(idx):
+            raise TypeError("stripes and idx must name the same number of rows")
+        if any(z < 0 for z in stripes):
+            raise ErrInvalidArg("negative stripe number")
+        n, _, S = slab.shape
+        if new.dim() != 2 or tuple(new.shape) != (len(idx), S):
+            raise TypeError("new must be a [len(idx), S] uint8 CUDA tensor")
+        if not new.is_cuda or new.dtype.itemsize != 1 or new.stride(1) != 1:
+            raise TypeError("new rows must be contiguous uint8 on a CUDA device")
+        zarr = (C.c_uint32 * max(len(idx), 1))(*stripes)
+        iarr = (C.c_int * max(len(idx), 1))(*idx)
+        _check(self._L.rs_update_dev_batch_list(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, zarr, iarr,
+                                                len(idx), new.data_ptr(), new.stride(0), S, _stream_handle(stream)))
+
     # ---------------- scrub (beyond the reference: its Verify returns one bool;
     # the encode is GF-linear, so the syndrome names a single corrupt shard)
     def _slab(self, slab):

@@ -203,6 +203,19 @@ struct UpdPlan : StreamUses {
     }
 };
 
+// The device tables of a set of changed columns (rs_update_dev_batch_list):
+// per column of `cols` (ascending) its p x 1 update tables, slot by slot
+// (gf_host.hpp make_update_columns).
+struct UpdColSet : StreamUses {
+    DevBuf<uint8_t> blob;
+    const uint32_t *tw = nullptr;
+    std::vector<int> cols;
+    ~UpdColSet() {
+        drain();
+        blob.release();
+    }
+};
+
 // The device tables of a direct decode (rs_reconstruct_rows_dev*) for one
 // (present, rows rebuilt) pair: t x np multiply-by-D[j][i] images
 // (make_decode_tables) and the present / rebuilt shard indices.
@@ -329,6 +342,10 @@ struct rs_codec {
     // incremental-update tables keyed by the ordered list of changed indices
     // (bounded LRU, as dplan_cache); their row pointers use the ring above
     Lru<std::vector<int>, std::unique_ptr<UpdPlan>, 16> uplan_cache;
+    // column sets of rs_update_dev_batch_list keyed by the sorted distinct
+    // changed columns of a call (or of a pass of it); a set that holds every
+    // column asked for serves the call too
+    Lru<std::vector<int>, std::unique_ptr<UpdColSet>, 4> ucol_cache;
     // direct-decode tables keyed by (erasure pattern, rows rebuilt), likewise
     Lru<std::vector<uint8_t>, std::unique_ptr<RowsPlan>, 16> rowsplan_cache;
     // pattern sets keyed by (recover_all, the set's erasure patterns in order);
@@ -402,6 +419,7 @@ struct rs_codec {
         rc_host.release();
         dplan_cache.items.clear();  // each plan waits for its last launch
         uplan_cache.items.clear();
+        ucol_cache.items.clear();
         rowsplan_cache.items.clear();
         pset_cache.items.clear();
         rset_cache.items.clear();
@@ -1338,6 +1356,100 @@ int update_device_batch(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_
         a.nstripes = nstripes;
         HIP_TRY(launch_update(c->bits, a, s));
         HIP_TRY(up->mark_used(s));
+    }
+    return RS_OK;
+}
+
+// ---- A list of changed rows, a different set per stripe (rs_update_dev_batch_list)
+static_assert(kUpdListGroup == kUpdGroup, "the host plan cuts the groups k_update_list runs");
+
+// The cached device set with the tables of `cols` (ascending, distinct), built
+// and uploaded on first use.  A cached set that holds more columns serves as
+// well (a slot is a column's position in the set's own list), so the changing
+// subsets of a write-back cache's flushes settle on one set.
+int upd_col_set(rs_codec *c, const std::vector<int> &cols, UpdColSet **out) {
+    if (auto *hit = c->ucol_cache.find(cols)) {
+        *out = hit->get();
+        return RS_OK;
+    }
+    auto &items = c->ucol_cache.items;
+    for (auto it = items.begin(); it != items.end(); ++it) {
+        const std::vector<int> &have = it->second->cols;
+        if (!std::includes(have.begin(), have.end(), cols.begin(), cols.end())) continue;
+        items.splice(items.begin(), items, it);
+        *out = items.front().second.get();
+        return RS_OK;
+    }
+    std::vector<uint8_t> h(cols.size() * c->p * c->twd * 4);
+    make_update_columns(*c->F, c->k, c->p, cols.data(), (int)cols.size(), c->enc_ifft_logs, c->enc_fft_logs,
+                        (uint32_t *)h.data());
+    auto us = std::make_unique<UpdColSet>();
+    if (int e = upload(us->blob, h)) return e;
+    us->tw = (const uint32_t *)us->blob.p;
+    us->cols = cols;
+    *out = c->ucol_cache.put(cols, std::move(us))->get();  // an eviction waits for that set's last launch
+    return RS_OK;
+}
+
+// The plan's launches in order.  The descriptor lists of as many launches of a
+// pass as fit kUpdListSlotBytes travel through one ring slot (a longer list is
+// cut: its groups are in different stripes, so the pieces are independent), so
+// nothing waits for a kernel.
+int update_device_list(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, const UpdListPlan &plan,
+                       const int *idx_of, const uint8_t *nbase, uint64_t new_row_stride, uint64_t S, hipStream_t s) {
+    constexpr size_t kUpdListSlotBytes = 4u << 20;
+    struct Piece {
+        size_t launch, g0, g1, off;
+    };
+    std::vector<Piece> pieces;
+    const size_t nl = plan.launches.size();
+    for (size_t li = 0, g0 = 0; li < nl;) {
+        const int pass = plan.launches[li].pass;
+        size_t bytes = 0;
+        pieces.clear();
+        while (li < nl && plan.launches[li].pass == pass) {
+            const UpdListLaunch &l = plan.launches[li];
+            const size_t per = upd_list_desc_dwords(l.nt) * 4;
+            const size_t room = bytes < kUpdListSlotBytes ? (kUpdListSlotBytes - bytes) / per : 0;
+            if (!room) break;
+            const size_t g1 = std::min(l.stripes.size(), g0 + room);
+            pieces.push_back(Piece{li, g0, g1, bytes});
+            bytes += align256((g1 - g0) * per);
+            if (g1 < l.stripes.size()) {
+                g0 = g1;
+                break;
+            }
+            li++;
+            g0 = 0;
+        }
+        UpdColSet *us = nullptr;
+        if (int e = upd_col_set(c, plan.pass_cols[pass], &us)) return e;
+        int slot = 0;
+        uint8_t *h = nullptr, *g = nullptr;
+        if (int e = ring_acquire(c, bytes, slot, h, g)) return e;
+        for (const Piece &pc : pieces)
+            write_update_list_descs(plan.launches[pc.launch], pc.g0, pc.g1, idx_of, us->cols.data(), (int)us->cols.size(),
+                                    (uint32_t *)(h + pc.off));
+        HIP_TRY(hipMemcpyAsync(g, h, bytes, hipMemcpyHostToDevice, s));
+        for (const Piece &pc : pieces) {
+            UpdateListArgs a{};
+            a.base = base;
+            a.nbase = nbase;
+            a.row_stride = row_stride;
+            a.stripe_stride = stripe_stride;
+            a.new_row_stride = new_row_stride;
+            a.tw = us->tw;
+            a.list = (const uint32_t *)(g + pc.off);
+            a.S = S;
+            a.k = c->k;
+            a.p = c->p;
+            a.nlist = (int)(pc.g1 - pc.g0);
+            a.nt = plan.launches[pc.launch].nt;
+            HIP_TRY(launch_update_list(c->bits, a, s));
+        }
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+        HIP_TRY(us->mark_used(s));
     }
     return RS_OK;
 }
@@ -3393,6 +3505,42 @@ int rs_update_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t st
     if (dc.err) return dc.err;
     return dc.finish(update_device_batch(c, base, row_stride, stripe_stride, nstripes, std::vector<int>(idx, idx + nidx),
                                          d_new, new_row_stride, new_stripe_stride, S, dc.s));
+}
+
+int rs_update_dev_batch_list(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
+                             const uint32_t *stripe_of, const int *idx_of, size_t nrows, const uint8_t *d_new,
+                             size_t new_row_stride, size_t S, void *stream) {
+    if (!c || !base || !stripe_of || !idx_of || !d_new) return RS_ERR_INVALID_ARG;
+    if (nstripes > (size_t)INT32_MAX || nrows > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    UpdListPlan plan;
+    if (!make_update_list_plan(c->k, nstripes, stripe_of, idx_of, nrows, upd_piece(c), plan)) return RS_ERR_INVALID_ARG;
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (row_stride < S || new_row_stride < S) return RS_ERR_INVALID_ARG;
+    if (nstripes > 1 && stripe_stride < (size_t)c->total * row_stride) return RS_ERR_INVALID_ARG;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    if (nrows == 0) return RS_OK;
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    return dc.finish(update_device_list(c, base, row_stride, stripe_stride, plan, idx_of, d_new, new_row_stride, S, dc.s));
+}
+
+int rs_debug_update_list_plan(int k, size_t nstripes, const uint32_t *stripe_of, const int *idx_of, size_t nrows,
+                              int *nlaunches, int32_t *launches, uint32_t *stripes, uint32_t *entries) {
+    if (k <= 0 || !stripe_of || !idx_of || !nlaunches || !launches || !stripes || !entries) return RS_ERR_INVALID_ARG;
+    if (nstripes > (size_t)INT32_MAX || nrows > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
+    UpdListPlan plan;
+    if (!make_update_list_plan(k, nstripes, stripe_of, idx_of, nrows, k, plan)) return RS_ERR_INVALID_ARG;
+    *nlaunches = (int)plan.launches.size();
+    for (const UpdListLaunch &l : plan.launches) {
+        *launches++ = l.nt;
+        *launches++ = l.round;
+        *launches++ = (int32_t)l.stripes.size();
+        stripes = std::copy(l.stripes.begin(), l.stripes.end(), stripes);
+        entries = std::copy(l.entries.begin(), l.entries.end(), entries);
+    }
+    return RS_OK;
 }
 
 int rs_debug_generator(int bits, int k, int p, int idx, uint32_t *out) {

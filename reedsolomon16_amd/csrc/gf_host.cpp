@@ -1,6 +1,8 @@
 // Host-side finite-field tables and GPU twiddle-table construction (see gf_host.hpp).
 #include "gf_host.hpp"
 
+#include <algorithm>
+#include <array>
 #include <cstring>
 #include <mutex>
 
@@ -405,6 +407,89 @@ void make_update_tables(const Field &F, int k, int p, const int *idx, int t, con
         // log[0] is not a log: a zero coefficient ships as the zero twiddle's all-zero table
         for (int i = 0; i < p; i++)
             make_twiddle(F, col[i] ? F.log[col[i]] : F.mod, out + ((size_t)i * t + j) * twd, true);
+    }
+}
+
+void make_update_columns(const Field &F, int k, int p, const int *cols, int ncols, const std::vector<uint32_t> &ifft,
+                         const std::vector<uint32_t> &fft, uint32_t *out) {
+    const size_t per = (size_t)p * tw_dwords(F.bits);
+    for (int s = 0; s < ncols; s++) make_update_tables(F, k, p, cols + s, 1, ifft, fft, out + (size_t)s * per);
+}
+
+bool make_update_list_plan(int k, size_t nstripes, const uint32_t *stripe_of, const int *idx_of, size_t nrows, int piece,
+                           UpdListPlan &plan) {
+    plan.pass_cols.clear();
+    plan.launches.clear();
+    for (size_t e = 0; e < nrows; e++)
+        if (stripe_of[e] >= nstripes || idx_of[e] < 0 || idx_of[e] >= k) return false;
+    // entries by (stripe, data index): a stripe's entries become adjacent, a repeated pair too
+    std::vector<uint32_t> order(nrows);
+    for (size_t e = 0; e < nrows; e++) order[e] = (uint32_t)e;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        return stripe_of[a] != stripe_of[b] ? stripe_of[a] < stripe_of[b] : idx_of[a] < idx_of[b];
+    });
+    for (size_t i = 1; i < nrows; i++)
+        if (stripe_of[order[i]] == stripe_of[order[i - 1]] && idx_of[order[i]] == idx_of[order[i - 1]]) return false;
+    if (!nrows) return true;
+    // the distinct columns, ascending, and the pass of each
+    std::vector<int> pass_of((size_t)k, -1);
+    for (size_t e = 0; e < nrows; e++) pass_of[idx_of[e]] = 0;
+    if (piece < 1) piece = 1;
+    int ncols = 0;
+    for (int j = 0; j < k; j++) {
+        if (pass_of[j] < 0) continue;
+        pass_of[j] = ncols++ / piece;
+        if ((int)plan.pass_cols.size() <= pass_of[j]) plan.pass_cols.emplace_back();
+        plan.pass_cols.back().push_back(j);
+    }
+    // A pass's columns are a range of data indices, so its entries of a stripe
+    // are a run [i0, i1) of `order`.
+    for (int pass = 0; pass < (int)plan.pass_cols.size(); pass++) {
+        std::vector<std::array<int, kUpdListGroup + 1>> at;  // at[round][nt]: launch number of the pass, -1: none yet
+        std::vector<UpdListLaunch> ls;
+        for (size_t i0 = 0; i0 < nrows;) {
+            if (pass_of[idx_of[order[i0]]] != pass) {
+                i0++;
+                continue;
+            }
+            size_t i1 = i0 + 1;
+            while (i1 < nrows && stripe_of[order[i1]] == stripe_of[order[i0]] && pass_of[idx_of[order[i1]]] == pass) i1++;
+            const size_t t = i1 - i0, ng = (t + kUpdListGroup - 1) / kUpdListGroup;
+            for (size_t g = 0, j0 = i0; g < ng; g++) {
+                const int nt = (int)(t / ng + (g < t % ng ? 1 : 0));
+                if (at.size() <= g) {
+                    at.emplace_back();
+                    at.back().fill(-1);
+                }
+                if (at[g][nt] < 0) {
+                    at[g][nt] = (int)ls.size();
+                    ls.push_back(UpdListLaunch{pass, (int)g, nt, {}, {}});
+                }
+                UpdListLaunch &l = ls[at[g][nt]];
+                l.stripes.push_back(stripe_of[order[i0]]);
+                l.entries.insert(l.entries.end(), order.begin() + j0, order.begin() + j0 + nt);
+                j0 += nt;
+            }
+            i0 = i1;
+        }
+        for (size_t g = 0; g < at.size(); g++)
+            for (int nt = 1; nt <= kUpdListGroup; nt++)
+                if (at[g][nt] >= 0) plan.launches.push_back(std::move(ls[at[g][nt]]));
+    }
+    return true;
+}
+
+void write_update_list_descs(const UpdListLaunch &l, size_t g0, size_t g1, const int *idx_of, const int *cols, int ncols,
+                             uint32_t *out) {
+    const int nt = l.nt;
+    for (size_t g = g0; g < g1; g++, out += upd_list_desc_dwords(nt)) {
+        out[0] = l.stripes[g];
+        for (int j = 0; j < nt; j++) {
+            const uint32_t e = l.entries[g * nt + j];
+            out[1 + j] = (uint32_t)idx_of[e];
+            out[1 + nt + j] = (uint32_t)(std::lower_bound(cols, cols + ncols, idx_of[e]) - cols);
+            out[1 + 2 * nt + j] = e;
+        }
     }
 }
 

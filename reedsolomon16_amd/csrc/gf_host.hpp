@@ -136,6 +136,46 @@ void generator_column_from(const Field &F, int k, int p, int idx, const std::vec
 void make_update_tables(const Field &F, int k, int p, const int *idx, int t, const std::vector<uint32_t> &ifft_logs,
                         const std::vector<uint32_t> &fft_logs, uint32_t *out);
 
+// ---- Update list: a list of changed rows, a different set per stripe
+// (rs_update_dev_batch_list, codec.cpp UpdColSet, kernels.hpp UpdateListArgs).
+// Column tables: slot s holds make_update_tables' p x 1 output for idx =
+// {cols[s]}, table (s, i) at out + (s * p + i) * tw_dwords.
+void make_update_columns(const Field &F, int k, int p, const int *cols, int ncols, const std::vector<uint32_t> &ifft_logs,
+                         const std::vector<uint32_t> &fft_logs, uint32_t *out);
+
+constexpr int kUpdListGroup = 8;  // changed rows per group (kernels.hpp kUpdGroup)
+// One kernel launch: groups of nt changed rows each, every group in another
+// stripe.  entries holds nt entry numbers (positions in the caller's list) per
+// group, in ascending data index.
+struct UpdListLaunch {
+    int pass, round, nt;
+    std::vector<uint32_t> stripes;  // one per group, no stripe twice
+    std::vector<uint32_t> entries;  // nt per group
+};
+// Entry e: data shard idx_of[e] of stripe stripe_of[e].  The distinct columns,
+// ascending, are cut into passes of at most `piece` columns (pass_cols); a pass
+// takes the entries of its columns.  Within a pass a stripe with t entries is
+// cut into ceil(t / kUpdListGroup) groups of near-equal size (9 -> 5 + 4), its
+// g-th group goes into round g, and each (round, nt) with a group is one
+// launch.  A parity unit of a stripe is read, modified and written by one lane
+// of one group, so two groups of a stripe never share a launch; `launches` is
+// in stream order (pass, then round, then nt), which orders them.
+struct UpdListPlan {
+    std::vector<std::vector<int>> pass_cols;
+    std::vector<UpdListLaunch> launches;
+};
+// False for a stripe_of[e] >= nstripes, an idx_of[e] outside [0, k) or a
+// (stripe, index) pair named twice; the plan is then unspecified.
+bool make_update_list_plan(int k, size_t nstripes, const uint32_t *stripe_of, const int *idx_of, size_t nrows, int piece,
+                           UpdListPlan &plan);
+// Device descriptors of groups [g0, g1) of a launch, 1 + 3 * nt dwords each:
+// the stripe, then per row of the group its data index, its table slot (its
+// column's position in cols[0..ncols), ascending, which holds every column of
+// the launch) and its entry number.
+inline size_t upd_list_desc_dwords(int nt) { return 1 + 3 * (size_t)nt; }
+void write_update_list_descs(const UpdListLaunch &l, size_t g0, size_t g1, const int *idx_of, const int *cols, int ncols,
+                             uint32_t *out);
+
 // Decoder schedules over n = ceilPow2(m+k) rows (leopard16.go:573-657).
 bool decode_schedule(const Field &F, int k, int p, std::vector<uint32_t> &ifft_logs, std::vector<uint32_t> &fft_logs);
 

@@ -2310,6 +2310,108 @@ hipError_t launch_update(int bits, const UpdateArgs &a, hipStream_t s) {
     return narrow ? update_f<F8<2>>(a, s) : update_f<F8<4>>(a, s);
 }
 
+// ---------------------------------------------------------------- incremental update, a row list per stripe
+// k_update's strided body over a list of groups (rs_update_dev_batch_list,
+// kernels.hpp UpdateListArgs): every group of a launch changes NT rows of a
+// stripe of its own, each row with the tables of its own column.
+namespace {
+
+// Group blockIdx.y + y0.  Its descriptor (1 + 3 NT dwords: stripe, NT data
+// indices, NT table slots, NT entry numbers) is the same for the whole
+// workgroup and read-only for the launch: scalar loads through the constant
+// address space (as k_decode_rows_pat reads its own).  The loop is k_update's
+// (a copy: that kernel's instantiations keep their registers) with a table
+// base per row in place of one table row stride.  All addresses are 64-bit
+// (row pointer + offset).
+template <class F, int NT>
+__global__ void __launch_bounds__(256, 2) k_update_list(UpdateListArgs a, int y0) {
+    typedef typename F::Vec V;
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    cu32_t *d = (cu32_t *)a.list + ((uint64_t)blockIdx.y + (uint64_t)y0) * (uint64_t)(1 + 3 * NT);
+    uint8_t *sb = a.base + (uint64_t)d[0] * a.stripe_stride;
+    const uint64_t tcol = (uint64_t)a.p * F::TWD;  // dwords of a column's tables
+    UpdMasks<F> mk[NT];
+    const uint32_t *tw[NT];  // table (slot_j, i) at tw[j] + i * TWD
+#pragma unroll
+    for (int j = 0; j < NT; j++) {
+        uint8_t *o = sb + (uint64_t)d[1 + j] * a.row_stride;
+        tw[j] = a.tw + (uint64_t)d[1 + NT + j] * tcol;
+        const V nv = F::load(a.nbase + (uint64_t)d[1 + 2 * NT + j] * a.new_row_stride, u);
+        V x = F::load(o, u);
+        F::store(o, u, nv);
+        F::xor_into(x, nv);
+        mk[j].prepare(x);
+    }
+    uint8_t *pbase = sb + (uint64_t)a.k * a.row_stride;
+    int i = 0;
+    for (; i + kUpdRows <= a.p; i += kUpdRows) {
+        uint8_t *r[kUpdRows];
+        V x[kUpdRows];
+#pragma unroll
+        for (int q = 0; q < kUpdRows; q++) {
+            r[q] = pbase + (uint64_t)(i + q) * a.row_stride;
+            x[q] = F::load(r[q], u);
+        }
+#pragma unroll
+        for (int q = 0; q < kUpdRows; q++) {
+#pragma unroll
+            for (int j = 0; j < NT; j++) {
+                const Tab<F> tb = load_tab<F>(tw[j] + (uint64_t)(i + q) * F::TWD);
+                mk[j].mul_add(x[q], tb.v);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kUpdRows; q++) F::store(r[q], u, x[q]);
+    }
+    for (; i < a.p; i++) {
+        uint8_t *r = pbase + (uint64_t)i * a.row_stride;
+        V x = F::load(r, u);
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            const Tab<F> tb = load_tab<F>(tw[j] + (uint64_t)i * F::TWD);
+            mk[j].mul_add(x, tb.v);
+        }
+        F::store(r, u, x);
+    }
+}
+
+template <class F, int NT>
+hipError_t update_list_group(const UpdateListArgs &a, hipStream_t s) {
+    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
+    return for_y(a.nlist, [&](int y0, int ny) {
+        hipLaunchKernelGGL((k_update_list<F, NT>), dim3(grid_x(units).x, ny), dim3(256), 0, s, a, y0);
+    });
+}
+
+template <class F>
+hipError_t update_list_f(const UpdateListArgs &a, hipStream_t s) {
+    static_assert(kUpdGroup == 8, "update_list_f dispatches group sizes 1..8");
+    switch (a.nt) {
+        case 1: return update_list_group<F, 1>(a, s);
+        case 2: return update_list_group<F, 2>(a, s);
+        case 3: return update_list_group<F, 3>(a, s);
+        case 4: return update_list_group<F, 4>(a, s);
+        case 5: return update_list_group<F, 5>(a, s);
+        case 6: return update_list_group<F, 6>(a, s);
+        case 7: return update_list_group<F, 7>(a, s);
+        default: return update_list_group<F, 8>(a, s);
+    }
+}
+
+}  // namespace
+
+// Unit widths by launch_update's grid rule over the list's groups.
+hipError_t launch_update_list(int bits, const UpdateListArgs &a, hipStream_t s) {
+    constexpr uint64_t kUpdMinBlocks = 1024;
+    if (a.nt <= 0 || a.nt > kUpdGroup || a.nlist <= 0 || a.p <= 0 || a.S == 0 || a.S % 64) return hipErrorInvalidValue;
+    if (!a.base || !a.nbase || !a.tw || !a.list) return hipErrorInvalidValue;
+    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * (uint64_t)a.nlist;
+    const bool narrow = pick_narrow(wide_blocks < kUpdMinBlocks);
+    if (bits == 16) return narrow ? update_list_f<F16<2>>(a, s) : update_list_f<F16<4>>(a, s);
+    return narrow ? update_list_f<F8<2>>(a, s) : update_list_f<F8<4>>(a, s);
+}
+
 // ---------------------------------------------------------------- direct decode of a few rows
 // wanted row j = XOR over the present rows i of D[j][i] * row i (kernels.hpp
 // DecodeRowsArgs, gf_host.hpp decode_coefficients): k_update's shape

@@ -272,6 +272,22 @@ struct UpdateArgs {
 // Runs the t changed rows as ceil(t / kUpdGroup) launches on s.
 hipError_t launch_update(int bits, const UpdateArgs &a, hipStream_t s);
 
+// The strided form over a list of groups, each nt changed rows of one stripe
+// (rs_update_dev_batch_list): a workgroup's descriptor names its stripe and per
+// row the data index, the slot of the column's tables and the new row's number
+// (gf_host.hpp write_update_list_descs: 1 + 3 * nt dwords).  No stripe twice
+// in a list: the lanes of a group own the stripe's parity units for the launch.
+struct UpdateListArgs {
+    uint8_t *base;         // shard i of stripe z at base + z*stripe_stride + i*row_stride
+    const uint8_t *nbase;  // new row of entry e at nbase + e*new_row_stride, stored over the old one
+    uint64_t row_stride, stripe_stride, new_row_stride;
+    const uint32_t *tw;    // column tables, (slot, i) at (slot*p + i) * tw_dwords (make_update_columns)
+    const uint32_t *list;  // device array, nlist descriptors
+    uint64_t S;
+    int k, p, nlist, nt;   // 1 <= nt <= kUpdGroup
+};
+hipError_t launch_update_list(int bits, const UpdateListArgs &a, hipStream_t s);
+
 
 // ---- Direct decode of a few rows: wanted row j = sum over the present rows i
 // of D[j][i] * row i (gf_host.hpp decode_coefficients), the transpose of the

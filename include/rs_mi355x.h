@@ -582,18 +582,64 @@ int rs_verify_dev_batch_map(rs_codec *codec, uint8_t *d_base, size_t row_stride,
  * three-row streaming kernel that builds the repaired row and one verify. */
 int rs_locate_dev(rs_codec *codec, uint8_t *const *d_shards, size_t shard_size, int repair, int *verdict, void *stream);
 
-/* The map, then the locate (and repair) of every bad stripe, one stripe at a
- * time.  verdict: host, nstripes int32; *nbad: the number of bad stripes,
- * located or not.
+/* The map, then the locate (and repair) of every bad stripe: one stripe at a
+ * time as rs_locate_dev does, or, from two bad stripes on, all of them through
+ * rs_locate_dev_batch's shared launches (the threshold is measured: with two
+ * bad stripes among 256 the call costs 7.50-7.68 ms against 7.87-8.01, more
+ * than the pass-to-pass spread in every run; with one, the difference, 7.41-7.63
+ * against 7.50-7.69, did not clear the spread in every run).  Verdicts and
+ * slab contents are the same on both routes.  verdict: host, nstripes int32;
+ * *nbad: the number of bad stripes, located or not.
  * Measured on one MI355X at 128+32 x 1 MiB, 256 stripes (profiles/scrub_c3.txt,
  * DESIGN.md 4.12), ms per call: rs_verify_dev_batch 7.27 (the parent commit's
  * 7.27; the two differ by less than their 0.4 % pass-to-pass spread),
  * rs_verify_dev_batch_map 7.31-7.32 (+0.5 % in every run); this call on a clean slab is the
  * map; with one corrupt data shard among the 256 stripes 7.58 (locate) and 7.60
  * (locate and repair), where finding the stripe alone by re-verifying
- * sub-ranges costs 8 further rs_verify_dev_batch calls, 7.69 ms. */
+ * sub-ranges costs 8 further rs_verify_dev_batch calls, 7.69 ms.  With all 256
+ * stripes bad (profiles/scrub_batch_c3.txt): 25.2 ms (25.9 with
+ * repair) against 74.0 (75.6) one stripe at a time. */
 int rs_scrub_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, size_t stripe_stride, int nstripes,
                        size_t shard_size, int repair, int32_t *verdict, int *nbad, void *stream);
+
+/* rs_locate_dev for many stripes of a slab (rs_encode_dev_batch's layout) in
+ * shared launches.  stripes: host, nlist distinct stripe numbers in any order
+ * (free to reuse on return); verdict: host, nlist int32.  verdict[e] is exactly
+ * what rs_locate_dev returns for stripe stripes[e] alone, and with repair != 0
+ * the named shard of each located stripe ends as rs_locate_dev(repair = 1)
+ * leaves it; no other byte of the slab, of its padding or of an unlisted stripe
+ * (corrupt or not) is written.  Complete on return, ordered on the caller's
+ * stream like the other scrub calls.
+ * Work, in passes over the list: per listed stripe one encode into scratch rows,
+ * queued back to back; one scan launch over the pass (a stripe per blockIdx.y)
+ * and a tiny launch that picks the two syndrome symbols at each stripe's first
+ * differing position; one read-back; the host classifies as rs_locate_dev does.
+ * A data candidate is never accepted from the ratio alone: with
+ * t = scale * (P_0 ^ P'_0) the stripe verifies with row_j ^ t in place iff
+ * P_i ^ P'_i == G[i][j] * t in every parity row at every symbol (the encode is
+ * GF-linear), which one launch checks for all candidates on the 2 p parity rows
+ * at hand (64 rows against the 160 of a verify at 128+32); one read-back; then
+ * one launch repairs the confirmed data shards in place and one copy per
+ * located parity shard.  At most three host waits per pass, however many
+ * stripes it holds.  A pass holds at most 32768 stripes and at most 1 GiB of
+ * scratch (p rows of row_stride or shard_size bytes per stripe; always at least
+ * one stripe): 32 stripes at 128+32 x 1 MiB.
+ * Errors, all decided before any device call, in this order: NULL codec / d_base
+ * / stripes / verdict, nstripes or nlist > INT32_MAX, a multi-device codec, a
+ * stripes[e] >= nstripes, a stripe named twice -> RS_ERR_INVALID_ARG;
+ * shard_size == 0 -> RS_ERR_SHARD_NO_DATA; shard_size % 64 ->
+ * RS_ERR_INVALID_SHARD_SIZE; row_stride < shard_size -> RS_ERR_INVALID_ARG;
+ * RS_ERR_PANIC where the reference's encode of the geometry panics; then
+ * nlist == 0 -> RS_OK with nothing launched.
+ * Measured on one MI355X at 128+32 x 1 MiB, 256 stripes (profiles/scrub_batch_c3.txt,
+ * DESIGN.md 4.16), per bad stripe on top of the map, through rs_scrub_dev_batch
+ * with all 256 stripes bad in one data shard each: 69.6 us (72.3 with repair)
+ * against 260 (266) one stripe at a time; 1024+256 x 256 KiB, 8 stripes all bad:
+ * 2.84 ms per scrub against 5.78.  Not measured: GF(2^8) codecs, the split of a
+ * pass's time between its launches and its three host waits. */
+int rs_locate_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, size_t stripe_stride, size_t nstripes,
+                        const uint32_t *stripes /* nlist, host */, size_t nlist, size_t shard_size, int repair,
+                        int32_t *verdict /* nlist, host */, void *stream);
 
 /* ---------------- Host-only diagnostics (no device calls; used by CPU tests) ---------------- */
 /* Field tables as built by the engine (initLUTs/initFFTSkew, leopard16.go:940-1031). */
@@ -701,7 +747,11 @@ int rs_debug_encode_bs_fits(int data_shards, int parity_shards, size_t row_strid
  *                     decoder with a descriptor per tile (2); other codecs have the first only,
  *   "bsdec_grid" >= 0 workgroups of the bit-sliced decoder's persistent grid: one per compute
  *                     unit (0, default) or at most this many, so that a few small stripes make
- *                     one workgroup walk from stripe to stripe.
+ *                     one workgroup walk from stripe to stripe,
+ *   "scrub_batch" -1/0/1  rs_scrub_dev_batch locates its bad stripes through rs_locate_dev_batch's
+ *                     shared launches by the measured threshold (-1, default), never (0: one
+ *                     stripe at a time), or always (1),
+ *   "scrub_chunk" >= 0  listed stripes per pass of rs_locate_dev_batch, 0 = automatic (default 0).
  * Returns RS_ERR_INVALID_ARG for an unknown knob or value.  Host only. */
 int rs_debug_set_path(const char *knob, int value);
 

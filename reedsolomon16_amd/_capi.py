@@ -67,6 +67,7 @@ def lib() -> C.CDLL:
     L.rs_verify_dev_batch_map.argtypes = [vp, vp, sz, sz, i32, sz, vp, P(i32), vp]
     L.rs_locate_dev.argtypes = [vp, P(vp), sz, i32, P(i32), vp]
     L.rs_scrub_dev_batch.argtypes = [vp, vp, sz, sz, i32, sz, i32, vp, P(i32), vp]
+    L.rs_locate_dev_batch.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint32), sz, sz, i32, vp, vp]
     L.rs_debug_locate.argtypes = [i32, i32, i32, C.c_uint32, C.c_uint32, P(i32), P(C.c_uint32)]
     L.rs_debug_generator.argtypes = [i32, i32, i32, i32, vp]
     L.rs_set_host_segment.argtypes = [vp, sz]
@@ -101,7 +102,7 @@ def lib() -> C.CDLL:
     return L
 
 
-_PATH_DEFAULTS = {"bs": 1, "sub": 1, "prune": 1, "unit_width": -1, "hp_tiles": 0, "hp_step": 0, "zc": 3, "hp_tune": 1, "rec_half": 0, "dec_lab": 0, "lds_big": 1, "rows_direct": -1, "pat_tier": 0, "bsdec_grid": 0}
+_PATH_DEFAULTS = {"bs": 1, "sub": 1, "prune": 1, "unit_width": -1, "hp_tiles": 0, "hp_step": 0, "zc": 3, "hp_tune": 1, "rec_half": 0, "dec_lab": 0, "lds_big": 1, "rows_direct": -1, "pat_tier": 0, "bsdec_grid": 0, "scrub_batch": -1, "scrub_chunk": 0}
 
 
 def set_path(knob: str, value: int) -> None:

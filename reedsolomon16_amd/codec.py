@@ -949,6 +949,23 @@ class ReedSolomon:
                                           int(bool(repair)), verdict.ctypes.data, C.byref(nbad), _stream_handle(stream)))
         return verdict[:n]
 
+    def locate_dev_batch(self, slab, stripes: Sequence[int], repair: bool = False, stream=None) -> np.ndarray:
+        """locate_dev for the stripes named (distinct, in any order) of a
+        [nstripes, k+p, S] slab, in shared launches (rs_locate_dev_batch): an
+        int32 array, verdict e for stripe stripes[e].  repair: the shard named
+        for a stripe is overwritten with its right content; nothing else, and
+        no stripe that is not listed, is written."""
+        n, S = self._slab(slab)
+        stripes = [int(z) for z in stripes]
+        if any(z < 0 for z in stripes):
+            raise ErrInvalidArg("negative stripe number")
+        zarr = (C.c_uint32 * max(len(stripes), 1))(*stripes)
+        verdict = np.full(max(len(stripes), 1), SCRUB_UNLOCATED, np.int32)
+        _check(self._L.rs_locate_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, zarr,
+                                           len(stripes), S, int(bool(repair)), verdict.ctypes.data,
+                                           _stream_handle(stream)))
+        return verdict[:len(stripes)]
+
 
 class EncodeTicket:
     """Completion handle of ReedSolomon.encode_async / reconstruct_async (holds

@@ -366,6 +366,10 @@ struct rs_codec {
     Lru<int, std::unique_ptr<UpdPlan>, 16> fixplan_cache;
     DevBuf<uint8_t> scrub_rows, scrub_dev;
     PinnedBuf scrub_host;
+    // rs_locate_dev_batch: the scan, pick and confirm results of a pass with
+    // their pinned readback (the passes' recomputed parity rows are scrub_rows)
+    DevBuf<uint8_t> scrub_list_dev;
+    PinnedBuf scrub_list_host;
 
     // error-locator cache keyed by erasure pattern (bounded LRU)
     Lru<std::vector<uint8_t>, std::vector<uint32_t>, 64> el_cache;
@@ -424,8 +428,9 @@ struct rs_codec {
         pset_cache.items.clear();
         rset_cache.items.clear();
         fixplan_cache.items.clear();
-        scrub_rows.release(); scrub_dev.release();
+        scrub_rows.release(); scrub_dev.release(); scrub_list_dev.release();
         scrub_host.release();
+        scrub_list_host.release();
         for (int i = 0; i < kRing; i++)
             if (ring_ev[i]) {
                 (void)hipEventSynchronize(ring_ev[i]);
@@ -513,7 +518,7 @@ int upload_split(rs_codec *c) {
 // the reconstruct FFT unpruned, the narrow / wide LDS units) on the same small
 // inputs.  Process-wide; read when a codec is created (bs) or at each launch.
 std::atomic<int> g_path_bs{1}, g_path_sub{1}, g_path_prune{1}, g_path_unit_width{-1}, g_path_hp_tiles{0}, g_path_hp_step{0},
-    g_path_zc{3}, g_path_hp_tune{1}, g_path_rec_half{0}, g_path_dec_lab{0}, g_path_lds_big{1}, g_path_rows_direct{-1}, g_path_pat_tier{0}, g_path_bsdec_grid{0};
+    g_path_zc{3}, g_path_hp_tune{1}, g_path_rec_half{0}, g_path_dec_lab{0}, g_path_lds_big{1}, g_path_rows_direct{-1}, g_path_pat_tier{0}, g_path_bsdec_grid{0}, g_path_scrub_batch{-1}, g_path_scrub_chunk{0};
 bool bs_enabled() { return g_path_bs.load(std::memory_order_relaxed) != 0; }
 bool sub_enabled() { return g_path_sub.load(std::memory_order_relaxed) != 0; }
 bool prune_enabled() { return g_path_prune.load(std::memory_order_relaxed) != 0; }
@@ -2177,10 +2182,208 @@ int locate_stripe(rs_codec *c, uint8_t *const *d, uint64_t S, bool repair, hipSt
     return RS_OK;
 }
 
+// ---- The locate of many stripes in shared launches (rs_locate_dev_batch)
+// Scratch bytes of a pass: p recomputed parity rows per listed stripe.  A pass
+// takes as many stripes as fit this bound (always at least one), at most
+// kScrubMaxList (one per blockIdx.y), and at most the "scrub_chunk" knob.
+constexpr size_t kScrubListScratch = (size_t)1 << 30;
+// rs_scrub_dev_batch sends its bad stripes through the batched route from this
+// many on: the smallest count at which that route measured faster than one
+// stripe at a time by more than the latter's pass-to-pass spread
+// (profiles/scrub_batch_c3.txt).  At 128+32 x 1 MiB, 256
+// stripes: with two bad stripes 7.58-7.68 ms per scrub against 7.95-8.01
+// (spread 0.01-0.11) in both runs; with one, 7.53-7.63 against 7.60-7.69, which
+// cleared the spread (0.04-0.08) in one run and not in the other, so a single
+// bad stripe keeps the one-stripe route.
+constexpr size_t kScrubBatchMin = 2;
+
+// locate_stripe for stripes[0..nlist) of the slab at `base` (distinct, checked
+// by the caller), verdict[e] for stripes[e], on the caller's stream s inside
+// the caller's scratch_acquire / scratch_release.  Per pass: the stripes'
+// encodes into their scratch slots, the list scan and the pick, one readback
+// (host wait 1); the host classifies as locate_stripe does; the data
+// candidates' confirm on the 2 p parity rows, one readback (host wait 2); the
+// repairs are queued and left to the caller's final wait.
+int locate_list_device(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, const uint32_t *stripes,
+                       size_t nlist, uint64_t S, bool repair, hipStream_t s, int32_t *verdict) {
+    const int k = c->k, p = c->p;
+    for (size_t e = 0; e < nlist; e++) verdict[e] = RS_SCRUB_UNLOCATED;
+    if (!nlist) return RS_OK;
+    // scratch rows at the data rows' own stride where that keeps the bit-sliced
+    // kernel eligible, else packed (locate_stripe's rule)
+    uint64_t qs = S;
+    const uint64_t ds = k > 1 ? row_stride : 0;
+    if (c->bs_ok && ds >= S && ds <= 2 * S && encode_bs_fits(k, p, ds, S)) qs = ds;
+    const size_t slot_bytes = align256((size_t)p * qs);
+    size_t chunk = std::min<size_t>(nlist, (size_t)kScrubMaxList);
+    chunk = std::min(chunk, std::max<size_t>(1, kScrubListScratch / slot_bytes));
+    if (const int knob = g_path_scrub_chunk.load(std::memory_order_relaxed)) chunk = std::min(chunk, (size_t)knob);
+    if (int e = scratch_ensure(c, c->scrub_rows, chunk * slot_bytes)) return e;
+    // results of a pass: [first, 8 bytes per entry][rowbad, p ints][symbols, 2 dwords][confirm word]
+    const size_t o_rowbad = align256(8 * chunk), o_sym = o_rowbad + align256(4 * chunk * p);
+    const size_t o_bad = o_sym + align256(8 * chunk), res_bytes = o_bad + align256(4 * chunk);
+    if (int e = scratch_ensure(c, c->scrub_list_dev, res_bytes)) return e;
+    if (res_bytes > c->scrub_list_host.n) {
+        if (int e = scratch_host_wait(c)) return e;
+        HIP_TRY(c->scrub_list_host.ensure(res_bytes));
+    }
+    if (p > 1 && !c->locate_built) {
+        make_locate_map(*c->F, k, p, c->locate_map);
+        c->locate_built = true;
+    }
+    uint8_t *q = c->scrub_rows.p, *dev = c->scrub_list_dev.p;
+    uint8_t *host = c->scrub_list_host.p;
+    ScrubListArgs a{};
+    a.base = base;
+    a.row_stride = row_stride;
+    a.stripe_stride = stripe_stride;
+    a.fresh = q;
+    a.fresh_stride = qs;
+    a.fresh_slot_stride = slot_bytes;
+    a.S = S;
+    a.k = k;
+    a.p = p;
+    a.first = (unsigned long long *)dev;
+    a.rowbad = (int *)(dev + o_rowbad);
+    a.sym = (uint32_t *)(dev + o_sym);
+    a.bad = (int *)(dev + o_bad);
+    struct Cand {
+        uint32_t e;  // entry of the pass (its scratch slot)
+        int j;
+        uint32_t scale;
+    };
+    std::vector<Cand> cand;
+    std::vector<std::pair<uint32_t, int>> parity;  // (entry, parity row) located by the scan alone
+    std::vector<int> cols;
+    const int piece = upd_piece(c);
+    for (size_t c0 = 0; c0 < nlist; c0 += chunk) {
+        const size_t n = std::min(chunk, nlist - c0);
+        const uint32_t *zs = stripes + c0;
+        int32_t *v = verdict + c0;
+        int slot = 0;
+        uint8_t *h = nullptr, *g = nullptr;
+        if (int e = ring_acquire(c, 4 * n, slot, h, g)) return e;
+        std::memcpy(h, zs, 4 * n);
+        HIP_TRY(hipMemcpyAsync(g, h, 4 * n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(dev, 0xff, 8 * n, s));
+        HIP_TRY(hipMemsetAsync(dev + o_rowbad, 0, res_bytes - o_rowbad, s));
+        for (size_t e = 0; e < n; e++) {
+            const RowSet data{nullptr, base + (size_t)zs[e] * stripe_stride, ds};
+            const RowSet par{nullptr, q + e * slot_bytes, p > 1 ? qs : 0};
+            if (int err = encode_device(c, data, par, S, 0, 1, nullptr, s)) return err;
+        }
+        a.list = (const uint32_t *)g;
+        a.nlist = (int)n;
+        HIP_TRY(launch_syndrome_scan_list(c->bits, a, s));
+        HIP_TRY(launch_syndrome_pick(c->bits, a, s));
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+        HIP_TRY(hipMemcpyAsync((void *)host, dev, o_bad, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        cand.clear();
+        parity.clear();
+        const volatile uint64_t *first = (const volatile uint64_t *)host;
+        const volatile uint32_t *sym = (const volatile uint32_t *)(host + o_sym);
+        for (size_t e = 0; e < n; e++) {
+            const volatile int *rowbad = (const volatile int *)(host + o_rowbad) + e * p;
+            int nb = 0, bi = -1;
+            for (int i = 0; i < p; i++)
+                if (rowbad[i]) nb++, bi = i;
+            if (!nb) {
+                v[e] = RS_SCRUB_CLEAN;
+            } else if (p == 1) {  // one syndrome row cannot tell the shards apart
+            } else if (nb == 1) {
+                v[e] = k + bi;
+                if (repair) parity.emplace_back((uint32_t)e, bi);
+            } else if (nb == p && first[e] < S) {  // a data shard's difference shows in every parity row
+                uint32_t scale = 0;
+                const int j = locate_shard(*c->F, c->locate_map, sym[2 * e], sym[2 * e + 1], &scale);
+                if (j >= 0) cand.push_back(Cand{(uint32_t)e, j, scale});
+            }
+        }
+        if (!cand.empty()) {
+            // never from the ratio alone.  Candidate number = position by
+            // column; a pass of the confirm takes the candidates of at most
+            // `piece` distinct columns (one column set)
+            std::stable_sort(cand.begin(), cand.end(), [](const Cand &x, const Cand &y) { return x.j < y.j; });
+            const size_t nc = cand.size(), twb = (size_t)c->twd * 4, db = 4 * (size_t)kScrubDescDwords;
+            const size_t o_tw = align256(db * nc), o_fix = o_tw + align256(nc * twb);
+            if (int e = ring_acquire(c, o_fix + align256(db * nc), slot, h, g)) return e;
+            for (size_t i = 0; i < nc; i++)
+                make_twiddle(*c->F, c->F->log[cand[i].scale], (uint32_t *)(h + o_tw + i * twb), true);
+            HIP_TRY(hipMemcpyAsync(g + o_tw, h + o_tw, nc * twb, hipMemcpyHostToDevice, s));
+            a.scale_tw = (const uint32_t *)(g + o_tw);
+            for (size_t n0 = 0, n1 = 0; n0 < nc; n0 = n1) {
+                cols.clear();
+                for (n1 = n0; n1 < nc; n1++) {
+                    if (!cols.empty() && cols.back() == cand[n1].j) continue;
+                    if ((int)cols.size() == piece) break;
+                    cols.push_back(cand[n1].j);
+                }
+                UpdColSet *us = nullptr;
+                if (int e = upd_col_set(c, cols, &us)) return e;
+                uint32_t *d = (uint32_t *)h + n0 * kScrubDescDwords;
+                for (size_t i = n0; i < n1; i++, d += kScrubDescDwords) {
+                    d[0] = zs[cand[i].e];
+                    d[1] = cand[i].e;
+                    d[2] = (uint32_t)(std::lower_bound(us->cols.begin(), us->cols.end(), cand[i].j) - us->cols.begin());
+                    d[3] = (uint32_t)i;
+                }
+                HIP_TRY(hipMemcpyAsync(g + db * n0, h + db * n0, db * (n1 - n0), hipMemcpyHostToDevice, s));
+                a.list = (const uint32_t *)(g + db * n0);
+                a.nlist = (int)(n1 - n0);
+                a.col_tw = us->tw;
+                HIP_TRY(launch_syndrome_confirm(c->bits, a, s));
+                HIP_TRY(us->mark_used(s));
+            }
+            HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+            c->ring_used[slot] = true;
+            HIP_TRY(hipMemcpyAsync((void *)(host + o_bad), dev + o_bad, 4 * nc, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            const volatile int *bad = (const volatile int *)(host + o_bad);
+            size_t nfix = 0;
+            uint32_t *d = (uint32_t *)(h + o_fix);
+            for (size_t i = 0; i < nc; i++) {
+                if (bad[i]) continue;
+                v[cand[i].e] = cand[i].j;
+                d[0] = zs[cand[i].e], d[1] = cand[i].e, d[2] = (uint32_t)cand[i].j, d[3] = (uint32_t)i;
+                d += kScrubDescDwords, nfix++;
+            }
+            if (repair && nfix) {
+                HIP_TRY(hipMemcpyAsync(g + o_fix, h + o_fix, db * nfix, hipMemcpyHostToDevice, s));
+                a.list = (const uint32_t *)(g + o_fix);
+                a.nlist = (int)nfix;
+                HIP_TRY(launch_syndrome_fix(c->bits, a, s));
+                HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+            }
+        }
+        for (const auto &pr : parity) {
+            uint8_t *row = base + (size_t)zs[pr.first] * stripe_stride + (size_t)(k + pr.second) * row_stride;
+            HIP_TRY(hipMemcpyAsync(row, q + pr.first * slot_bytes + (size_t)pr.second * qs, S, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    return RS_OK;
+}
+
+// rs_locate_dev_batch after its argument checks.  Complete on return.
+int locate_batch_call(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, const uint32_t *stripes,
+                      size_t nlist, uint64_t S, int repair, int32_t *verdict, void *stream) {
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    if (int e = scratch_acquire(c, s)) return e;
+    const int err = locate_list_device(c, base, row_stride, stripe_stride, stripes, nlist, S, repair != 0, s, verdict);
+    if (int e = scratch_release(c, s)) return err ? err : e;
+    if (err) return err;
+    HIP_TRY(hipStreamSynchronize(s));  // the queued repairs
+    return RS_OK;
+}
+
 // The three scrub calls after their argument checks.  d != nullptr: one stripe
 // by row pointers (verdict[0]); else the slab at `base`: the map (bad != nullptr:
 // one byte per stripe), then, with verdict != nullptr, the locate of each bad
-// stripe, one at a time.  Complete on return (the results are read back).
+// stripe: one at a time, or through locate_list_device ("scrub_batch" knob).
+// Complete on return (the results are read back).
 int scrub_call(rs_codec *c, uint8_t *const *d, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, int nstripes,
                uint64_t S, int repair, uint8_t *bad, int32_t *verdict, int *nbad, void *stream) {
     DevCall dc(c, stream);
@@ -2202,6 +2405,15 @@ int scrub_call(rs_codec *c, uint8_t *const *d, uint8_t *base, uint64_t row_strid
             if (bad) bad[z] = b;
             if (verdict) verdict[z] = b ? RS_SCRUB_UNLOCATED : RS_SCRUB_CLEAN;
             if (b && verdict) todo.push_back(z);
+        }
+        const int knob = g_path_scrub_batch.load(std::memory_order_relaxed);
+        if (!err && !todo.empty() && (knob == 1 || (knob < 0 && todo.size() >= kScrubBatchMin))) {
+            const std::vector<uint32_t> zs(todo.begin(), todo.end());
+            std::vector<int32_t> v(zs.size());
+            err = locate_list_device(c, base, row_stride, stripe_stride, zs.data(), zs.size(), S, repair != 0, s, v.data());
+            for (size_t t = 0; t < zs.size() && !err; t++)
+                verdict[zs[t]] = v[t] == RS_SCRUB_CLEAN ? RS_SCRUB_UNLOCATED : v[t];
+            todo.clear();
         }
         std::vector<uint8_t *> rows((size_t)c->total);
         for (size_t t = 0; t < todo.size() && !err; t++) {
@@ -3152,6 +3364,25 @@ int rs_scrub_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t str
     return scrub_call(c, nullptr, base, row_stride, stripe_stride, nstripes, S, repair, nullptr, verdict, nbad, stream);
 }
 
+int rs_locate_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
+                        const uint32_t *stripes, size_t nlist, size_t S, int repair, int32_t *verdict, void *stream) {
+    if (!c || !base || !stripes || !verdict) return RS_ERR_INVALID_ARG;
+    if (nstripes > (size_t)INT32_MAX || nlist > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    {
+        std::vector<uint32_t> sorted(stripes, stripes + nlist);
+        std::sort(sorted.begin(), sorted.end());
+        if (nlist && sorted.back() >= nstripes) return RS_ERR_INVALID_ARG;
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return RS_ERR_INVALID_ARG;
+    }
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (row_stride < S) return RS_ERR_INVALID_ARG;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    if (nlist == 0) return RS_OK;
+    return locate_batch_call(c, base, row_stride, stripe_stride, stripes, nlist, S, repair, verdict, stream);
+}
+
 int rs_debug_locate(int bits, int k, int p, uint32_t e0, uint32_t e1, int *shard, uint32_t *scale) {
     if ((bits != 8 && bits != 16) || !shard || !scale || k <= 0 || p <= 0) return RS_ERR_INVALID_ARG;
     *shard = -1;
@@ -3658,6 +3889,8 @@ int rs_debug_set_path(const char *knob, int value) {
     else if (k == "rows_direct" && value >= -1 && value <= 1) g_path_rows_direct = value;
     else if (k == "pat_tier" && value >= 0 && value <= 2) g_path_pat_tier = value;
     else if (k == "bsdec_grid" && value >= 0) g_path_bsdec_grid = value;
+    else if (k == "scrub_batch" && value >= -1 && value <= 1) g_path_scrub_batch = value;
+    else if (k == "scrub_chunk" && value >= 0) g_path_scrub_chunk = value;
     else return RS_ERR_INVALID_ARG;
     return RS_OK;
 }

@@ -2719,4 +2719,203 @@ hipError_t launch_syndrome_scan(int bits, const ScanArgs &a, hipStream_t s) {
     return narrow ? syndrome_scan_f<F8<2>>(a, s) : syndrome_scan_f<F8<4>>(a, s);
 }
 
+// ---------------------------------------------------------------- locate of many stripes (scrub)
+// rs_locate_dev_batch (kernels.hpp ScrubListArgs): the scan over a list of
+// stripes, the pick of the two syndrome symbols the host classifies by, the
+// confirm of its candidates on the 2 p parity rows, and the repair.  A
+// descriptor is the same for the whole workgroup and read-only for the launch:
+// scalar loads through the constant address space (as k_update_list reads its
+// own).  All row addresses are 64-bit (row pointer + offset).
+namespace {
+
+static_assert(kScrubMaxList <= kMaxGridY, "one descriptor per blockIdx.y");
+
+// k_syndrome_scan's strided body (a copy: that kernel's instantiations keep
+// their registers) with the stripe's parity rows as the stored set, scratch
+// slot blockIdx.y as the fresh one, and the entry's own rowbad and first.
+template <class F>
+__global__ void __launch_bounds__(256) k_syndrome_scan_list(ScrubListArgs a) {
+    typedef typename F::Vec V;
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    const uint64_t e = blockIdx.y;
+    const uint8_t *stored = a.base + (uint64_t)((cu32_t *)a.list)[e] * a.stripe_stride + (uint64_t)a.k * a.row_stride;
+    const uint8_t *fresh = a.fresh + e * a.fresh_slot_stride;
+    int *rowbad = a.rowbad + e * (uint64_t)a.p;
+    V any = F::zero();
+    int i = 0;
+    for (; i + kScanRows <= a.p; i += kScanRows) {
+        V x[kScanRows], y[kScanRows];
+#pragma unroll
+        for (int q = 0; q < kScanRows; q++) {
+            x[q] = F::load(stored + (uint64_t)(i + q) * a.row_stride, u);
+            y[q] = F::load(fresh + (uint64_t)(i + q) * a.fresh_stride, u);
+        }
+#pragma unroll
+        for (int q = 0; q < kScanRows; q++) {
+            F::xor_into(x[q], y[q]);
+            or_into<F>(any, x[q]);
+            flag_mismatch(rowbad + i + q, F::diff(x[q], F::zero()) != 0);
+        }
+    }
+    for (; i < a.p; i++) {
+        V x = F::load(stored + (uint64_t)i * a.row_stride, u);
+        F::xor_into(x, F::load(fresh + (uint64_t)i * a.fresh_stride, u));
+        or_into<F>(any, x);
+        flag_mismatch(rowbad + i, F::diff(x, F::zero()) != 0);
+    }
+    const uint64_t m = __ballot(F::diff(any, F::zero()) != 0);
+    if (m && __lane_id() == (unsigned)(__ffsll((unsigned long long)m) - 1))
+        (void)__hip_atomic_fetch_min(a.first + e, (unsigned long long)(F::off(u) + first_symbol<F>(any)),
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One lane per entry: eight byte loads at most, behind the scan on the stream.
+template <bool SYM16>
+__global__ void __launch_bounds__(256) k_syndrome_pick(ScrubListArgs a) {
+    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= (uint32_t)a.nlist) return;
+    const uint64_t first = a.first[e];
+    uint32_t e0 = 0, e1 = 0;
+    if (first < a.S) {
+        const uint8_t *stored = a.base + (uint64_t)a.list[e] * a.stripe_stride + (uint64_t)a.k * a.row_stride;
+        const uint8_t *fresh = a.fresh + (uint64_t)e * a.fresh_slot_stride;
+        auto symbol = [&](const uint8_t *row) -> uint32_t {
+            if constexpr (SYM16) {
+                // low bytes in [0, 32) of the 64-byte block, high bytes in [32, 64)
+                const uint64_t lo = (first & ~(uint64_t)63) + (first & 31);
+                return (uint32_t)row[lo] | (uint32_t)row[lo + 32] << 8;
+            } else {
+                return row[first];
+            }
+        };
+        e0 = symbol(stored) ^ symbol(fresh);
+        if (a.p > 1) e1 = symbol(stored + a.row_stride) ^ symbol(fresh + a.fresh_stride);
+    }
+    a.sym[2 * (uint64_t)e] = e0;
+    a.sym[2 * (uint64_t)e + 1] = e1;
+}
+
+constexpr int kConfRows = 4;  // parity rows whose two loads a lane keeps in flight (8 loads, as the scan)
+
+// Candidate blockIdx.y: t = scale * (P_0 ^ P'_0) is the difference of data row
+// j if the candidate is right; its masks are prepared once and shared by the
+// p products G[i][j] * t, each compared with the syndrome row P_i ^ P'_i.
+template <class F>
+__global__ void __launch_bounds__(256, 2) k_syndrome_confirm(ScrubListArgs a) {
+    typedef typename F::Vec V;
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubDescDwords;
+    const uint8_t *stored = a.base + (uint64_t)d[0] * a.stripe_stride + (uint64_t)a.k * a.row_stride;
+    const uint8_t *fresh = a.fresh + (uint64_t)d[1] * a.fresh_slot_stride;
+    const uint32_t *ctw = a.col_tw + (uint64_t)d[2] * (uint64_t)a.p * F::TWD;  // table (slot, i) at ctw + i * TWD
+    const uint32_t n = d[3];
+    UpdMasks<F> mk;
+    {
+        V e0 = F::load(stored, u);
+        F::xor_into(e0, F::load(fresh, u));
+        V t = F::zero();
+        const Tab<F> tb = load_tab<F>(a.scale_tw + (uint64_t)n * F::TWD);
+        F::mul_add(t, e0, tb.v);
+        mk.prepare(t);
+    }
+    V any = F::zero();
+    int i = 0;
+    for (; i + kConfRows <= a.p; i += kConfRows) {
+        V x[kConfRows], y[kConfRows];
+#pragma unroll
+        for (int q = 0; q < kConfRows; q++) {
+            x[q] = F::load(stored + (uint64_t)(i + q) * a.row_stride, u);
+            y[q] = F::load(fresh + (uint64_t)(i + q) * a.fresh_stride, u);
+        }
+#pragma unroll
+        for (int q = 0; q < kConfRows; q++) {
+            F::xor_into(x[q], y[q]);
+            const Tab<F> tb = load_tab<F>(ctw + (uint64_t)(i + q) * F::TWD);
+            mk.mul_add(x[q], tb.v);  // e_i ^ G[i][j] * t
+            or_into<F>(any, x[q]);
+        }
+    }
+    for (; i < a.p; i++) {
+        V x = F::load(stored + (uint64_t)i * a.row_stride, u);
+        F::xor_into(x, F::load(fresh + (uint64_t)i * a.fresh_stride, u));
+        const Tab<F> tb = load_tab<F>(ctw + (uint64_t)i * F::TWD);
+        mk.mul_add(x, tb.v);
+        or_into<F>(any, x);
+    }
+    flag_mismatch(a.bad + n, F::diff(any, F::zero()) != 0);
+}
+
+template <class F>
+__global__ void __launch_bounds__(256) k_syndrome_fix(ScrubListArgs a) {
+    typedef typename F::Vec V;
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubDescDwords;
+    uint8_t *sb = a.base + (uint64_t)d[0] * a.stripe_stride;
+    uint8_t *row = sb + (uint64_t)d[2] * a.row_stride;
+    V e0 = F::load(sb + (uint64_t)a.k * a.row_stride, u);
+    F::xor_into(e0, F::load(a.fresh + (uint64_t)d[1] * a.fresh_slot_stride, u));
+    V x = F::load(row, u);
+    const Tab<F> tb = load_tab<F>(a.scale_tw + (uint64_t)d[3] * F::TWD);
+    F::mul_add(x, e0, tb.v);
+    F::store(row, u, x);
+}
+
+bool scrub_list_ok(const ScrubListArgs &a) {
+    return a.p > 0 && a.k > 0 && a.nlist > 0 && a.nlist <= kScrubMaxList && a.S != 0 && a.S % 64 == 0 && a.base &&
+           a.fresh && a.list && a.row_stride >= a.S && a.fresh_stride >= a.S;
+}
+// Unit widths by launch_update's grid rule over the list.
+bool scrub_list_narrow(int bits, const ScrubListArgs &a) {
+    constexpr uint64_t kScrubMinBlocks = 1024;
+    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * (uint64_t)a.nlist;
+    return pick_narrow(wide_blocks < kScrubMinBlocks);
+}
+template <class F>
+dim3 scrub_list_grid(const ScrubListArgs &a) {
+    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
+    return dim3(grid_x(units).x, (unsigned)a.nlist);
+}
+
+}  // namespace
+
+#define RS_SCRUB_LIST_LAUNCH(kernel)                                                                                \
+    do {                                                                                                            \
+        const bool narrow = scrub_list_narrow(bits, a);                                                             \
+        if (bits == 16) {                                                                                           \
+            if (narrow) hipLaunchKernelGGL(kernel<F16<2>>, scrub_list_grid<F16<2>>(a), dim3(256), 0, s, a);         \
+            else hipLaunchKernelGGL(kernel<F16<4>>, scrub_list_grid<F16<4>>(a), dim3(256), 0, s, a);                \
+        } else {                                                                                                    \
+            if (narrow) hipLaunchKernelGGL(kernel<F8<2>>, scrub_list_grid<F8<2>>(a), dim3(256), 0, s, a);           \
+            else hipLaunchKernelGGL(kernel<F8<4>>, scrub_list_grid<F8<4>>(a), dim3(256), 0, s, a);                  \
+        }                                                                                                           \
+        return hipGetLastError();                                                                                   \
+    } while (0)
+
+hipError_t launch_syndrome_scan_list(int bits, const ScrubListArgs &a, hipStream_t s) {
+    if (!scrub_list_ok(a) || !a.rowbad || !a.first) return hipErrorInvalidValue;
+    RS_SCRUB_LIST_LAUNCH(k_syndrome_scan_list);
+}
+
+hipError_t launch_syndrome_pick(int bits, const ScrubListArgs &a, hipStream_t s) {
+    if (!scrub_list_ok(a) || !a.first || !a.sym) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.nlist + 255) / 256));
+    if (bits == 16) hipLaunchKernelGGL(k_syndrome_pick<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_syndrome_pick<false>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_syndrome_confirm(int bits, const ScrubListArgs &a, hipStream_t s) {
+    if (!scrub_list_ok(a) || !a.col_tw || !a.scale_tw || !a.bad) return hipErrorInvalidValue;
+    RS_SCRUB_LIST_LAUNCH(k_syndrome_confirm);
+}
+
+hipError_t launch_syndrome_fix(int bits, const ScrubListArgs &a, hipStream_t s) {
+    if (!scrub_list_ok(a) || !a.scale_tw) return hipErrorInvalidValue;
+    RS_SCRUB_LIST_LAUNCH(k_syndrome_fix);
+}
+#undef RS_SCRUB_LIST_LAUNCH
+
 }  // namespace rs

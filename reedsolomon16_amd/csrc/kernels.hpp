@@ -351,4 +351,44 @@ struct ScanArgs {
 };
 hipError_t launch_syndrome_scan(int bits, const ScanArgs &a, hipStream_t s);
 
+// ---- The locate of many stripes of a slab in shared launches
+// (rs_locate_dev_batch): four kernels over a device list of descriptors, one
+// descriptor per blockIdx.y.  Entry e of a pass keeps its recomputed parity
+// rows in scratch slot e.
+constexpr int kScrubMaxList = 32768;  // descriptors per launch (grid.y), so entries per pass
+constexpr int kScrubDescDwords = 4;   // a confirm / fix descriptor
+struct ScrubListArgs {
+    uint8_t *base;  // shard i of stripe z at base + z*stripe_stride + i*row_stride
+    uint64_t row_stride, stripe_stride;
+    const uint8_t *fresh;  // recomputed parity row i of slot e at fresh + e*fresh_slot_stride + i*fresh_stride
+    uint64_t fresh_stride, fresh_slot_stride;
+    uint64_t S;
+    int k, p, nlist;
+    // scan and pick: nlist stripe numbers, descriptor e is entry (and slot) e.
+    // confirm and fix: nlist descriptors of kScrubDescDwords dwords: the stripe,
+    // its slot, [2], and the candidate's number n; [2] is the slot of the data
+    // shard's column in col_tw (confirm) or the data shard itself (fix)
+    const uint32_t *list;
+    int *rowbad;                // scan: p words per entry, as ScanArgs::rowbad
+    unsigned long long *first;  // scan: one per entry, as ScanArgs::first; pick reads it
+    uint32_t *sym;              // pick: the syndrome symbols of parity rows 0 and 1 at `first`, two per entry
+    const uint32_t *col_tw;     // confirm: column tables, (slot, i) at (slot*p + i) * tw_dwords (make_update_columns)
+    const uint32_t *scale_tw;   // confirm and fix: table n = multiply by candidate n's scale (make_twiddle)
+    int *bad;                   // confirm: word n set when candidate n does not explain its stripe's syndrome
+};
+// The strided k_syndrome_scan, stripe list[e] against slot e (rowbad cleared
+// and first preset by the caller, as for launch_syndrome_scan).
+hipError_t launch_syndrome_scan_list(int bits, const ScrubListArgs &a, hipStream_t s);
+// sym[2e], sym[2e + 1] = stored ^ fresh symbol of parity rows 0 and 1 at byte
+// first[e] (GF(2^16): the low byte there, the high byte 32 above), zeros when
+// first[e] >= S; row 1 is not read when p == 1.
+hipError_t launch_syndrome_pick(int bits, const ScrubListArgs &a, hipStream_t s);
+// With t = scale_n * (P_0 ^ P'_0): bad[n] is set unless P_i ^ P'_i == G[i][j] * t
+// in all p parity rows at every symbol -- the stripe verifies with row_j ^ t in
+// place of data row j exactly then.  Reads 2 p rows, writes only bad.
+hipError_t launch_syndrome_confirm(int bits, const ScrubListArgs &a, hipStream_t s);
+// data row [2] of the stripe ^= scale_n * (P_0 ^ P'_0), in place: reads three
+// rows, writes one, each lane its own unit.
+hipError_t launch_syndrome_fix(int bits, const ScrubListArgs &a, hipStream_t s);
+
 }  // namespace rs

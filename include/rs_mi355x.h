@@ -641,6 +641,67 @@ int rs_locate_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, siz
                         const uint32_t *stripes /* nlist, host */, size_t nlist, size_t shard_size, int repair,
                         int32_t *verdict /* nlist, host */, void *stream);
 
+/* Locate (and repair) up to RS_LOCATE_SET_MAX corrupt shards per stripe.
+ * rs_locate_dev_batch's arguments and list rules; count: host, nlist int32;
+ * shards: host, nlist * max_shards int32.  With cap = min(max_shards, p / 2),
+ * never below 1:
+ *   count[e] == 0: stripe stripes[e] is clean;
+ *   count[e] == c in 1..cap: exactly the c shards shards[e * max_shards ..]
+ *     (ascending, the unused entries -1) make the stripe a codeword when they are
+ *     replaced by the content the call computed, and each of them really changes;
+ *   count[e] == RS_SCRUB_UNLOCATED: corrupt, and no set of at most cap shards
+ *     explains it; its shards entries are all -1.
+ * repair != 0: every listed shard of a located stripe ends bit for bit as the
+ * codeword has it; no other shard, no padding, no unlisted stripe and no
+ * unlocated stripe is written.  Complete on return, on a single-device codec,
+ * ordered on the caller's stream like the other scrub calls.
+ * How: the encode's code is a generalised Reed-Solomon code, so 2 * cap weighted
+ * sums of the p syndrome symbols P_i ^ P'_i at one position are power sums of
+ * that symbol's errors, and a Berlekamp-Massey decoder on the host names the
+ * shards wrong there.  No set is accepted from a decode alone:
+ * one launch checks, on the 2 p parity rows at hand, that the set explains every
+ * parity row at every symbol; where it does not, the symbols at the first
+ * failing position are decoded and the set grows, at most cap rounds and
+ * 1 + 2 * cap host waits per pass of rs_locate_dev_batch's size.  With cap == 1
+ * a stripe takes rs_locate_dev_batch's route unchanged, so p <= 3 or
+ * max_shards == 1 give its verdicts, re-encoded.
+ * Limits.  cap is 1 where p == ceil_pow2(p) and that plus k equals the field
+ * order (GF(2^8) 128+128): every field symbol is then a shard's position and no
+ * shift point is left for the locators.  A located set is the true set of
+ * corrupt shards whenever (truly corrupt shards) + count <= p; beyond that a
+ * Reed-Solomon decoder can mis-correct (the same caveat as rs_locate_dev's
+ * "fewer than p shards").
+ * Errors, all decided before any device call, in rs_locate_dev_batch's order,
+ * with NULL count / shards and max_shards outside [1, RS_LOCATE_SET_MAX] ->
+ * RS_ERR_INVALID_ARG among the NULL checks.
+ * Measured on one MI355X at 128+32 x 1 MiB, 256 stripes, repair = 0
+ * (profiles/scrub_set_c3.txt), ms per rs_scrub_set_dev_batch
+ * call with max_shards = 4 at 1 / 8 / 64 / 256 bad stripes, over a 7.38 ms map.
+ * One corrupt shard per bad stripe: 7.54 / 8.00 / 12.14 / 26.10, 0.993 / 1.000 /
+ * 1.012 / 1.012 of rs_scrub_dev_batch.  Two shards in one byte: 7.58 / 8.08 /
+ * 12.41 / 27.59 (79 us per bad stripe on top of the map at 256); in disjoint
+ * places, which takes a second round: 7.68 / 8.27 / 13.36 / 32.12 (97 us).  Four
+ * shards in one byte: 7.59 / 8.13 / 13.00 / 30.00 (88 us); in four disjoint
+ * places, four rounds: 8.00 / 8.88 / 16.70 / 46.21 (152 us).  1024+256 x
+ * 256 KiB, 8 of 8 bad with two shards each: 3.09 ms (3.39 disjoint) over a
+ * 1.10 ms map.  For scale: rebuilding a stripe with
+ * rs_reconstruct_dev_batch_patterns, once the shards are known from elsewhere,
+ * costs 96-108 us per stripe.  Not measured: GF(2^8) codecs, repair = 1, the
+ * split of a pass's time between its launches and its host waits. */
+#define RS_LOCATE_SET_MAX 4
+int rs_locate_set_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, size_t stripe_stride, size_t nstripes,
+                            const uint32_t *stripes /* nlist, host */, size_t nlist, size_t shard_size, int max_shards,
+                            int repair, int32_t *count /* nlist, host */, int32_t *shards /* nlist * max_shards, host */,
+                            void *stream);
+/* rs_verify_dev_batch_map, then rs_locate_set_dev_batch over the bad stripes:
+ * count and shards are indexed by stripe (nstripes and nstripes * max_shards
+ * entries), *nbad (may be NULL) = the number of stripes that do not verify.
+ * Errors by rs_scrub_dev_batch's rules, with NULL count / shards and a
+ * max_shards outside [1, RS_LOCATE_SET_MAX] -> RS_ERR_INVALID_ARG first. */
+int rs_scrub_set_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, size_t stripe_stride, int nstripes,
+                           size_t shard_size, int max_shards, int repair, int32_t *count /* nstripes, host */,
+                           int32_t *shards /* nstripes * max_shards, host */, int *nbad, void *stream);
+
 /* ---------------- Host-only diagnostics (no device calls; used by CPU tests) ---------------- */
 /* Field tables as built by the engine (initLUTs/initFFTSkew, leopard16.go:940-1031). */
 int rs_debug_field_tables(int field_bits, uint16_t *log_out, uint16_t *exp_out, uint16_t *skew_out,
@@ -692,6 +753,24 @@ int rs_debug_decode_coefficients(int field_bits, int data_shards, int parity_sha
  * reference's encode panics. */
 int rs_debug_locate(int field_bits, int data_shards, int parity_shards, uint32_t e0, uint32_t e1, int *shard,
                     uint32_t *scale);
+/* rs_locate_set_dev_batch's per-symbol decoder on the host: e holds the p
+ * syndrome symbols P_i ^ P'_i of one position.  *count = the number of shards
+ * in error there, their numbers ascending in shards[0 .. max_shards) (unused
+ * entries -1); 0 when e is all zero; -1 when nothing of size <= cap =
+ * max(1, min(max_shards, p / 2)) fits the 2 * cap power sums.  With cap == 1
+ * (also where no shift point exists) the answer is the one-shard route's: the
+ * parity shard of the only non-zero symbol, or rs_debug_locate(e[0], e[1]).
+ * RS_ERR_INVALID_ARG for bad arguments, RS_ERR_PANIC where the reference's
+ * encode panics. */
+int rs_debug_locate_set(int field_bits, int data_shards, int parity_shards, const uint32_t *e /* p symbols */,
+                        int max_shards, int *count, int32_t *shards /* max_shards */);
+/* Process-wide counters of the set locate's route (cap >= 2) since the last
+ * reset, summed over all codecs and threads: out[0] passes, out[1] confirm
+ * launches-and-read-backs (rounds), out[2] host waits (without each call's
+ * final one).  Per pass at most cap rounds and 1 + 2 * cap waits, which
+ * tests/test_gpu_scrub_set.py asserts with them.  reset != 0 clears them
+ * after the read.  RS_ERR_INVALID_ARG for a NULL out. */
+int rs_debug_locate_set_stats(uint64_t *out /* 3 */, int reset);
 
 /* Checks the half-wave split schedules of the GF(2^16) encode kernel
  * (logm 2..5) against the plain butterfly order on random symbols and

@@ -27,6 +27,7 @@ from .codec import (  # noqa: F401
     EmptyShard,
     SCRUB_CLEAN,
     SCRUB_UNLOCATED,
+    LOCATE_SET_MAX,
 )
 from ._capi import LIB_PATH, lib  # noqa: F401
 
@@ -34,5 +35,5 @@ __all__ = [
     "New", "New8", "New16", "ReedSolomon", "RSError", "ErrInvShardNum", "ErrMaxShardNum", "ErrTooFewShards",
     "ErrShardNoData", "ErrShardSize", "ErrInvalidShardSize", "ErrNotSupported", "ErrShortData",
     "ErrReconstructRequired", "ErrNilWriter", "ErrSize", "ErrPanic", "ErrDevice", "LIB_PATH", "lib", "alloc_pinned",
-    "EmptyShard", "SCRUB_CLEAN", "SCRUB_UNLOCATED",
+    "EmptyShard", "SCRUB_CLEAN", "SCRUB_UNLOCATED", "LOCATE_SET_MAX",
 ]

@@ -68,7 +68,11 @@ def lib() -> C.CDLL:
     L.rs_locate_dev.argtypes = [vp, P(vp), sz, i32, P(i32), vp]
     L.rs_scrub_dev_batch.argtypes = [vp, vp, sz, sz, i32, sz, i32, vp, P(i32), vp]
     L.rs_locate_dev_batch.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint32), sz, sz, i32, vp, vp]
+    L.rs_locate_set_dev_batch.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint32), sz, sz, i32, i32, vp, vp, vp]
+    L.rs_scrub_set_dev_batch.argtypes = [vp, vp, sz, sz, i32, sz, i32, i32, vp, vp, P(i32), vp]
     L.rs_debug_locate.argtypes = [i32, i32, i32, C.c_uint32, C.c_uint32, P(i32), P(C.c_uint32)]
+    L.rs_debug_locate_set.argtypes = [i32, i32, i32, vp, i32, P(i32), vp]
+    L.rs_debug_locate_set_stats.argtypes = [P(C.c_uint64), i32]
     L.rs_debug_generator.argtypes = [i32, i32, i32, i32, vp]
     L.rs_set_host_segment.argtypes = [vp, sz]
     L.rs_set_reference_inversion_cache.argtypes = [vp, i32]

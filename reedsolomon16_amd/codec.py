@@ -224,6 +224,7 @@ def _dev_rows_opt(rows, count: int):
 
 RS_NULL_STREAM = C.c_void_p(-1).value  # include/rs_mi355x.h: HIP's null stream, asynchronous
 SCRUB_CLEAN, SCRUB_UNLOCATED = -1, -2  # include/rs_mi355x.h RS_SCRUB_*: verdicts of locate_dev / scrub_dev_batch
+LOCATE_SET_MAX = 4  # RS_LOCATE_SET_MAX: the most shards locate_set_dev_batch names per stripe
 
 
 def _stream_handle(stream):
@@ -965,6 +966,43 @@ class ReedSolomon:
                                            len(stripes), S, int(bool(repair)), verdict.ctypes.data,
                                            _stream_handle(stream)))
         return verdict[:len(stripes)]
+
+    def locate_set_dev_batch(self, slab, stripes: Sequence[int], max_shards: int = LOCATE_SET_MAX, repair: bool = False,
+                             stream=None):
+        """Up to max_shards corrupt shards per stripe, for the stripes named
+        (distinct, in any order) of a [nstripes, k+p, S] slab
+        (rs_locate_set_dev_batch): (count, shards), int32 arrays of shape
+        [len(stripes)] and [len(stripes), max_shards].  count 0 is a clean
+        stripe, c > 0 the number of shards listed (ascending, padded with -1),
+        SCRUB_UNLOCATED a stripe that no set of min(max_shards, p // 2) shards
+        explains.  repair: the listed shards are overwritten with their right
+        content; nothing else is written."""
+        n, S = self._slab(slab)
+        stripes = [int(z) for z in stripes]
+        if any(z < 0 for z in stripes):
+            raise ErrInvalidArg("negative stripe number")
+        max_shards = int(max_shards)
+        zarr = (C.c_uint32 * max(len(stripes), 1))(*stripes)
+        count = np.full(max(len(stripes), 1), SCRUB_UNLOCATED, np.int32)
+        shards = np.full((max(len(stripes), 1), max(max_shards, 1)), -1, np.int32)
+        _check(self._L.rs_locate_set_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, zarr,
+                                               len(stripes), S, max_shards, int(bool(repair)), count.ctypes.data,
+                                               shards.ctypes.data, _stream_handle(stream)))
+        return count[:len(stripes)], shards[:len(stripes)]
+
+    def scrub_set_dev_batch(self, slab, max_shards: int = LOCATE_SET_MAX, repair: bool = False, stream=None):
+        """The per-stripe verify of a [nstripes, k+p, S] slab, then
+        locate_set_dev_batch over the bad stripes (rs_scrub_set_dev_batch):
+        (count, shards) indexed by stripe."""
+        n, S = self._slab(slab)
+        max_shards = int(max_shards)
+        count = np.full(max(n, 1), SCRUB_UNLOCATED, np.int32)
+        shards = np.full((max(n, 1), max(max_shards, 1)), -1, np.int32)
+        nbad = C.c_int(0)
+        _check(self._L.rs_scrub_set_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, S, max_shards,
+                                              int(bool(repair)), count.ctypes.data, shards.ctypes.data, C.byref(nbad),
+                                              _stream_handle(stream)))
+        return count[:n], shards[:n]
 
 
 class EncodeTicket:

@@ -370,6 +370,13 @@ struct rs_codec {
     // their pinned readback (the passes' recomputed parity rows are scrub_rows)
     DevBuf<uint8_t> scrub_list_dev;
     PinnedBuf scrub_list_host;
+    // rs_locate_set_dev_batch: the weights and locators of the per-symbol
+    // decoder (built on the first use, like the ratio map), and the picked
+    // symbols and confirm results of a pass with their pinned readback
+    bool locate_set_built = false;
+    LocateSet locate_set;
+    DevBuf<uint8_t> scrub_set_dev;
+    PinnedBuf scrub_set_host;
 
     // error-locator cache keyed by erasure pattern (bounded LRU)
     Lru<std::vector<uint8_t>, std::vector<uint32_t>, 64> el_cache;
@@ -428,9 +435,10 @@ struct rs_codec {
         pset_cache.items.clear();
         rset_cache.items.clear();
         fixplan_cache.items.clear();
-        scrub_rows.release(); scrub_dev.release(); scrub_list_dev.release();
+        scrub_rows.release(); scrub_dev.release(); scrub_list_dev.release(); scrub_set_dev.release();
         scrub_host.release();
         scrub_list_host.release();
+        scrub_set_host.release();
         for (int i = 0; i < kRing; i++)
             if (ring_ev[i]) {
                 (void)hipEventSynchronize(ring_ev[i]);
@@ -2379,6 +2387,402 @@ int locate_batch_call(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t 
     return RS_OK;
 }
 
+// ---- The locate of up to four corrupt shards per stripe (rs_locate_set_dev_batch)
+// Passes, confirm rounds and host waits of the set locate so far (rs_debug_locate_set_stats).
+std::atomic<uint64_t> g_set_passes{0}, g_set_rounds{0}, g_set_waits{0};
+
+static_assert(kLocateSetMax == RS_LOCATE_SET_MAX && kScrubSetMax == RS_LOCATE_SET_MAX, "one set size in all layers");
+// cap of a call: min(max_shards, p / 2) but at least 1, and 1 where the
+// geometry leaves no shift point (LocateSet::cap).
+int locate_set_cap(rs_codec *c, int max_shards) {
+    if (!c->locate_set_built) {
+        make_locate_set(*c->F, c->k, c->p, c->locate_set);
+        c->locate_set_built = true;
+    }
+    return std::max(1, std::min(max_shards, c->locate_set.cap));
+}
+
+// A candidate set of a listed stripe: nj shards J, ascending.
+struct SetCand {
+    uint32_t e = 0;  // entry of the pass (its scratch slot)
+    int nj = 0;
+    int J[kLocateSetMax] = {};
+    uint64_t pos = 0;  // where the next decode reads its symbols
+    int nd(int k) const {  // the data shards among them (they come first)
+        int n = 0;
+        while (n < nj && J[n] < k) n++;
+        return n;
+    }
+};
+
+// count[e] and shards[e * stride ..] for stripes[0..nlist), cap >= 2, on the
+// caller's stream s inside the caller's scratch_acquire / scratch_release;
+// locate_list_device's passes.  Per pass: the recompute and the list scan with
+// one readback (host wait 1); entries with at most cap (and fewer than p) bad
+// parity rows become the candidate of those parity shards, the others are
+// decoded at their first differing position; then rounds of a confirm over all
+// candidates (one readback) and, for those that fail with room left, a pick of
+// the p symbols at the first failing position (one readback) and a decode that
+// must add a shard: at most cap rounds, 1 + 2 cap host waits.  The repairs of
+// the confirmed sets are queued and left to the caller's final wait.
+int locate_set_list_device(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride,
+                           const uint32_t *stripes, size_t nlist, uint64_t S, int cap, int stride, bool repair,
+                           hipStream_t s, int32_t *count, int32_t *shards) {
+    const int k = c->k, p = c->p;
+    const LocateSet &ls = c->locate_set;
+    for (size_t e = 0; e < nlist; e++) count[e] = RS_SCRUB_UNLOCATED;
+    std::fill(shards, shards + nlist * (size_t)stride, -1);
+    if (!nlist) return RS_OK;
+    uint64_t qs = S;  // locate_list_device's scratch rule
+    const uint64_t ds = k > 1 ? row_stride : 0;
+    if (c->bs_ok && ds >= S && ds <= 2 * S && encode_bs_fits(k, p, ds, S)) qs = ds;
+    const size_t slot_bytes = align256((size_t)p * qs);
+    size_t chunk = std::min<size_t>(nlist, (size_t)kScrubMaxList);
+    chunk = std::min(chunk, std::max<size_t>(1, kScrubListScratch / slot_bytes));
+    if (const int knob = g_path_scrub_chunk.load(std::memory_order_relaxed)) chunk = std::min(chunk, (size_t)knob);
+    if (int e = scratch_ensure(c, c->scrub_rows, chunk * slot_bytes)) return e;
+    // scan results of a pass: [first, 8 bytes per entry][rowbad, p ints]
+    const size_t o_rowbad = align256(8 * chunk), scan_bytes = o_rowbad + align256(4 * chunk * p);
+    if (int e = scratch_ensure(c, c->scrub_list_dev, scan_bytes)) return e;
+    if (scan_bytes > c->scrub_list_host.n) {
+        if (int e = scratch_host_wait(c)) return e;
+        HIP_TRY(c->scrub_list_host.ensure(scan_bytes));
+    }
+    // confirm and pick results: [bad, 1 int per candidate][used, 8 ints][fail, 8 bytes][symbols, p per pick]
+    const size_t o_used = align256(4 * chunk), o_fail = o_used + align256(32 * chunk);
+    const size_t o_sym = o_fail + align256(8 * chunk), set_bytes = o_sym + align256(4 * chunk * p);
+    if (int e = scratch_ensure(c, c->scrub_set_dev, set_bytes)) return e;
+    if (set_bytes > c->scrub_set_host.n) {
+        if (int e = scratch_host_wait(c)) return e;
+        HIP_TRY(c->scrub_set_host.ensure(set_bytes));
+    }
+    uint8_t *q = c->scrub_rows.p, *dev = c->scrub_list_dev.p, *sdev = c->scrub_set_dev.p;
+    uint8_t *host = c->scrub_list_host.p, *shost = c->scrub_set_host.p;
+    ScrubListArgs a{};
+    a.base = base;
+    a.row_stride = row_stride;
+    a.stripe_stride = stripe_stride;
+    a.fresh = q;
+    a.fresh_stride = qs;
+    a.fresh_slot_stride = slot_bytes;
+    a.S = S;
+    a.k = k;
+    a.p = p;
+    a.first = (unsigned long long *)dev;
+    a.rowbad = (int *)(dev + o_rowbad);
+    ScrubSetArgs b{};
+    b.base = base;
+    b.row_stride = row_stride;
+    b.stripe_stride = stripe_stride;
+    b.fresh = q;
+    b.fresh_stride = qs;
+    b.fresh_slot_stride = slot_bytes;
+    b.S = S;
+    b.k = k;
+    b.p = p;
+    b.sym = (uint32_t *)(sdev + o_sym);
+    b.bad = (int *)sdev;
+    b.used = (int *)(sdev + o_used);
+    b.fail = (unsigned long long *)(sdev + o_fail);
+    const size_t twb = (size_t)c->twd * 4, db = 4 * (size_t)kScrubSetDescDwords;
+    const int piece = upd_piece(c);
+    std::vector<SetCand> conf, pick, good;
+    std::vector<int> cols;
+    std::vector<uint32_t> gcol, sym((size_t)p);
+    std::vector<std::vector<uint32_t>> G;  // generator columns of the data shards of a piece
+
+    // Descriptors and A^-1 tables of cand[n0..n1) (one column set `us`) into
+    // the slot image h: descriptor i at h + db * i, tables from h + o_tw.
+    // wr: the fix's write bits, one word per candidate (nullptr: the confirm).
+    auto describe = [&](const std::vector<SetCand> &cand, size_t n0, size_t n1, const UpdColSet *us, const uint32_t *zs,
+                        uint8_t *h, size_t o_tw, size_t &ntab, const uint32_t *wr) -> bool {
+        G.assign(cols.size(), {});
+        for (size_t i = n0; i < n1; i++) {
+            const SetCand &cd = cand[i];
+            uint32_t *d = (uint32_t *)(h + db * i);
+            std::fill(d, d + kScrubSetDescDwords, 0u);
+            const int sd = cd.nd(k);
+            d[0] = zs[cd.e];
+            d[1] = cd.e;
+            d[2] = (uint32_t)i;
+            d[3] = (uint32_t)sd;
+            for (int x = 0; x < kScrubSetMax; x++) d[12 + x] = 0xffffffffu;
+            for (int x = sd; x < cd.nj; x++) d[12 + x - sd] = (uint32_t)(cd.J[x] - k);
+            // R: the first sd parity rows not in J_p
+            int R[kLocateSetMax] = {}, nr = 0;
+            for (int r = 0; r < p && nr < sd; r++) {
+                bool ex = false;
+                for (int x = sd; x < cd.nj; x++) ex |= cd.J[x] - k == r;
+                if (!ex) R[nr++] = r;
+            }
+            if (nr < sd) return false;
+            uint32_t A[kLocateSetMax * kLocateSetMax], inv[kLocateSetMax * kLocateSetMax];
+            for (int j = 0; j < sd; j++) {
+                const size_t slot = (size_t)(std::lower_bound(cols.begin(), cols.end(), cd.J[j]) - cols.begin());
+                if (G[slot].empty())
+                    generator_column_from(*c->F, k, p, cd.J[j], c->enc_ifft_logs, c->enc_fft_logs, G[slot]);
+                d[4 + j] = (uint32_t)(std::lower_bound(us->cols.begin(), us->cols.end(), cd.J[j]) - us->cols.begin());
+                d[8 + j] = (uint32_t)R[j];
+                d[17 + j] = (uint32_t)cd.J[j];
+                for (int r = 0; r < sd; r++) A[r * sd + j] = G[slot][R[r]];
+            }
+            if (!invert_matrix(*c->F, sd, A, inv)) return false;
+            d[16] = (uint32_t)ntab;
+            for (int x = 0; x < sd * sd; x++, ntab++)
+                make_twiddle(*c->F, inv[x] ? c->F->log[inv[x]] : c->F->mod, (uint32_t *)(h + o_tw + ntab * twb), true);
+            d[21] = wr ? wr[i] : 0;
+        }
+        return true;
+    };
+    // Cuts cand (sorted by its sets) into pieces of at most `piece` distinct
+    // data columns and runs `launch` over each with the piece's column set.
+    auto for_pieces = [&](std::vector<SetCand> &cand, const uint32_t *zs, const uint32_t *wr, bool fix) -> int {
+        const size_t nc = cand.size();
+        size_t ntot = 0;  // A^-1 tables: sd * sd per candidate
+        for (const SetCand &cd : cand) ntot += (size_t)cd.nd(k) * cd.nd(k);
+        const size_t o_tw = align256(db * nc), slot_need = o_tw + std::max<size_t>(1, ntot) * twb;
+        int slot = 0;
+        uint8_t *h = nullptr, *g = nullptr;
+        if (int e = ring_acquire(c, slot_need, slot, h, g)) return e;
+        size_t ntab = 0;
+        b.inv_tw = (const uint32_t *)(g + o_tw);
+        for (size_t n0 = 0, n1 = 0; n0 < nc; n0 = n1) {
+            cols.clear();
+            for (n1 = n0; n1 < nc; n1++) {
+                std::vector<int> add;
+                for (int x = 0; x < cand[n1].nj && cand[n1].J[x] < k; x++)
+                    if (!std::binary_search(cols.begin(), cols.end(), cand[n1].J[x])) add.push_back(cand[n1].J[x]);
+                if (n1 > n0 && (int)(cols.size() + add.size()) > piece) break;
+                cols.insert(cols.end(), add.begin(), add.end());
+                std::sort(cols.begin(), cols.end());
+            }
+            UpdColSet *us = nullptr;
+            if (!cols.empty())
+                if (int e = upd_col_set(c, cols, &us)) return e;
+            const size_t t0 = ntab;
+            // (an MDS generator has no singular minor, and |J| <= p / 2 leaves the rows R)
+            if (!describe(cand, n0, n1, us, zs, h, o_tw, ntab, wr)) return RS_ERR_DEVICE;
+            HIP_TRY(hipMemcpyAsync(g + db * n0, h + db * n0, db * (n1 - n0), hipMemcpyHostToDevice, s));
+            if (ntab > t0)
+                HIP_TRY(hipMemcpyAsync(g + o_tw + t0 * twb, h + o_tw + t0 * twb, (ntab - t0) * twb, hipMemcpyHostToDevice, s));
+            b.list = (const uint32_t *)(g + db * n0);
+            b.nlist = (int)(n1 - n0);
+            b.col_tw = us ? us->tw : b.inv_tw;  // no data shard in the piece: never read
+            if (fix) HIP_TRY(launch_syndrome_fix_set(c->bits, b, s));
+            else HIP_TRY(launch_syndrome_confirm_set(c->bits, b, s));
+            if (us) HIP_TRY(us->mark_used(s));
+        }
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+        return RS_OK;
+    };
+    auto by_set = [](const SetCand &x, const SetCand &y) {
+        return std::lexicographical_compare(x.J, x.J + x.nj, y.J, y.J + y.nj);
+    };
+
+    for (size_t c0 = 0; c0 < nlist; c0 += chunk) {
+        const size_t n = std::min(chunk, nlist - c0);
+        const uint32_t *zs = stripes + c0;
+        int32_t *cnt = count + c0, *sh = shards + c0 * (size_t)stride;
+        int slot = 0;
+        uint8_t *h = nullptr, *g = nullptr;
+        if (int e = ring_acquire(c, 4 * n, slot, h, g)) return e;
+        std::memcpy(h, zs, 4 * n);
+        HIP_TRY(hipMemcpyAsync(g, h, 4 * n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(dev, 0xff, 8 * n, s));
+        HIP_TRY(hipMemsetAsync(dev + o_rowbad, 0, scan_bytes - o_rowbad, s));
+        for (size_t e = 0; e < n; e++) {
+            const RowSet data{nullptr, base + (size_t)zs[e] * stripe_stride, ds};
+            const RowSet par{nullptr, q + e * slot_bytes, p > 1 ? qs : 0};
+            if (int err = encode_device(c, data, par, S, 0, 1, nullptr, s)) return err;
+        }
+        a.list = (const uint32_t *)g;
+        a.nlist = (int)n;
+        HIP_TRY(launch_syndrome_scan_list(c->bits, a, s));
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+        HIP_TRY(hipMemcpyAsync((void *)host, dev, scan_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        g_set_passes++, g_set_waits++;
+        conf.clear(), pick.clear(), good.clear();
+        const volatile uint64_t *first = (const volatile uint64_t *)host;
+        for (size_t e = 0; e < n; e++) {
+            const volatile int *rowbad = (const volatile int *)(host + o_rowbad) + e * p;
+            SetCand cd;
+            cd.e = (uint32_t)e;
+            int nb = 0;
+            for (int i = 0; i < p; i++)
+                if (rowbad[i]) {
+                    if (nb < cap) cd.J[nb] = k + i;
+                    nb++;
+                }
+            if (!nb) {
+                cnt[e] = 0;
+            } else if (nb <= cap && nb < p) {  // still confirmed
+                cd.nj = nb;
+                conf.push_back(cd);
+            } else if (first[e] < S) {
+                cd.pos = first[e];
+                pick.push_back(cd);
+            }
+        }
+        std::vector<uint32_t> wr;
+        while (true) {
+            if (!pick.empty()) {
+                // all p syndrome symbols at each candidate's position, decoded on the host
+                const size_t np = pick.size();
+                if (int e = ring_acquire(c, 4 * kScrubPickDescDwords * np, slot, h, g)) return e;
+                uint32_t *d = (uint32_t *)h;
+                for (size_t i = 0; i < np; i++, d += kScrubPickDescDwords)
+                    d[0] = zs[pick[i].e], d[1] = pick[i].e, d[2] = (uint32_t)pick[i].pos, d[3] = (uint32_t)(pick[i].pos >> 32);
+                HIP_TRY(hipMemcpyAsync(g, h, 4 * kScrubPickDescDwords * np, hipMemcpyHostToDevice, s));
+                b.list = (const uint32_t *)g;
+                b.nlist = (int)np;
+                HIP_TRY(launch_syndrome_pick_rows(c->bits, b, s));
+                HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+                c->ring_used[slot] = true;
+                HIP_TRY(hipMemcpyAsync((void *)(shost + o_sym), sdev + o_sym, 4 * np * p, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                g_set_waits++;
+                const volatile uint32_t *hs = (const volatile uint32_t *)(shost + o_sym);
+                for (size_t i = 0; i < np; i++) {
+                    SetCand cd = pick[i];
+                    for (int r = 0; r < p; r++) sym[r] = hs[i * p + r];
+                    int32_t found[kLocateSetMax];
+                    const int nf = locate_set_decode(*c->F, ls, sym.data(), cap, found);
+                    if (nf <= 0) continue;  // unlocated
+                    int merged[2 * kLocateSetMax];
+                    const int nm = (int)(std::set_union(cd.J, cd.J + cd.nj, found, found + nf, merged) - merged);
+                    if (nm == cd.nj || nm > cap) continue;  // a decode must add a shard, within cap
+                    std::copy(merged, merged + nm, cd.J);
+                    cd.nj = nm;
+                    conf.push_back(cd);
+                }
+                pick.clear();
+            }
+            if (conf.empty()) break;
+            std::stable_sort(conf.begin(), conf.end(), by_set);
+            const size_t nc = conf.size();
+            HIP_TRY(hipMemsetAsync(sdev, 0, o_fail, s));
+            HIP_TRY(hipMemsetAsync(sdev + o_fail, 0xff, 8 * nc, s));
+            if (int e = for_pieces(conf, zs, nullptr, false)) return e;
+            HIP_TRY(hipMemcpyAsync((void *)shost, sdev, o_fail + 8 * nc, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            g_set_rounds++, g_set_waits++;
+            const volatile int *bad = (const volatile int *)shost;
+            const volatile int *used = (const volatile int *)(shost + o_used);
+            const volatile uint64_t *fail = (const volatile uint64_t *)(shost + o_fail);
+            for (size_t i = 0; i < nc; i++) {
+                SetCand cd = conf[i];
+                if (!bad[i]) {
+                    // located: the shards that really change, and their write bits for the fix
+                    const int sd = cd.nd(k);
+                    uint32_t w = 0;
+                    int c1 = 0;
+                    int32_t *out = sh + (size_t)cd.e * stride;
+                    for (int x = 0; x < cd.nj; x++) {
+                        const int word = x < sd ? x : 4 + (x - sd);
+                        if (!used[8 * i + word]) continue;
+                        w |= 1u << word;
+                        out[c1++] = cd.J[x];
+                    }
+                    if (!c1) continue;  // (the scan said bad: cannot happen)
+                    cnt[cd.e] = c1;
+                    good.push_back(cd);
+                    wr.push_back(w);
+                } else if (cd.nj < cap && fail[i] < S) {
+                    cd.pos = fail[i];
+                    pick.push_back(cd);
+                }
+            }
+            conf.clear();
+            if (pick.empty()) break;
+        }
+        if (repair && !good.empty()) {
+            // (good is in confirm order round by round; the fix sorts it again with its write bits)
+            std::vector<size_t> idx(good.size());
+            for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
+            std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return by_set(good[x], good[y]); });
+            std::vector<SetCand> gs;
+            std::vector<uint32_t> ws;
+            for (size_t i : idx) gs.push_back(good[i]), ws.push_back(wr[i]);
+            if (int e = for_pieces(gs, zs, ws.data(), true)) return e;
+        }
+    }
+    return RS_OK;
+}
+
+// The set locate of a list on stream s inside the caller's scratch_acquire /
+// scratch_release: cap == 1 is the one-shard route unchanged.
+int locate_set_device(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, const uint32_t *stripes,
+                      size_t nlist, uint64_t S, int max_shards, int repair, hipStream_t s, int32_t *count,
+                      int32_t *shards) {
+    const int cap = locate_set_cap(c, max_shards);
+    int err = RS_OK;
+    if (cap == 1) {
+        // the one-shard route unchanged, its verdicts re-encoded
+        std::vector<int32_t> v(nlist);
+        err = locate_list_device(c, base, row_stride, stripe_stride, stripes, nlist, S, repair != 0, s, v.data());
+        for (size_t e = 0; e < nlist && !err; e++) {
+            std::fill(shards + e * (size_t)max_shards, shards + (e + 1) * (size_t)max_shards, -1);
+            count[e] = v[e] == RS_SCRUB_CLEAN ? 0 : v[e] >= 0 ? 1 : RS_SCRUB_UNLOCATED;
+            if (v[e] >= 0) shards[e * (size_t)max_shards] = v[e];
+        }
+    } else {
+        err = locate_set_list_device(c, base, row_stride, stripe_stride, stripes, nlist, S, cap, max_shards, repair != 0, s,
+                                     count, shards);
+    }
+    return err;
+}
+
+// rs_locate_set_dev_batch after its argument checks.  Complete on return.
+int locate_set_call(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, const uint32_t *stripes,
+                    size_t nlist, uint64_t S, int max_shards, int repair, int32_t *count, int32_t *shards, void *stream) {
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    if (int e = scratch_acquire(c, s)) return e;
+    const int err = locate_set_device(c, base, row_stride, stripe_stride, stripes, nlist, S, max_shards, repair, s, count, shards);
+    if (int e = scratch_release(c, s)) return err ? err : e;
+    if (err) return err;
+    HIP_TRY(hipStreamSynchronize(s));  // the queued repairs
+    return RS_OK;
+}
+
+// rs_scrub_set_dev_batch after its argument checks: the map, then the set
+// locate over the bad stripes.  Complete on return.
+int scrub_set_call(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, int nstripes, uint64_t S,
+                   int max_shards, int repair, int32_t *count, int32_t *shards, int *nbad, void *stream) {
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    if (int e = scratch_acquire(c, s)) return e;
+    std::vector<uint32_t> zs;
+    std::vector<int32_t> cn, sh;
+    const int *flags = nullptr;
+    int err = verify_map_device(c, base, row_stride, stripe_stride, nstripes, S, s, &flags);
+    for (int z = 0; z < nstripes && !err; z++)
+        if (((const volatile int *)flags)[z] != 0) zs.push_back((uint32_t)z);
+    if (!err && !zs.empty()) {
+        cn.resize(zs.size()), sh.resize(zs.size() * (size_t)max_shards);
+        err = locate_set_device(c, base, row_stride, stripe_stride, zs.data(), zs.size(), S, max_shards, repair, s, cn.data(),
+                                sh.data());
+    }
+    if (int e = scratch_release(c, s)) return err ? err : e;
+    if (err) return err;
+    HIP_TRY(hipStreamSynchronize(s));  // the queued repairs
+    std::fill(count, count + nstripes, 0);
+    std::fill(shards, shards + (size_t)nstripes * max_shards, -1);
+    for (size_t t = 0; t < zs.size(); t++) {
+        // (the map said bad; a clean scan cannot follow on unchanged rows)
+        count[zs[t]] = cn[t] == 0 ? RS_SCRUB_UNLOCATED : cn[t];
+        if (cn[t] > 0)
+            std::copy(sh.begin() + t * max_shards, sh.begin() + (t + 1) * max_shards, shards + (size_t)zs[t] * max_shards);
+    }
+    if (nbad) *nbad = (int)zs.size();
+    return RS_OK;
+}
+
 // The three scrub calls after their argument checks.  d != nullptr: one stripe
 // by row pointers (verdict[0]); else the slab at `base`: the map (bad != nullptr:
 // one byte per stripe), then, with verdict != nullptr, the locate of each bad
@@ -3381,6 +3785,89 @@ int rs_locate_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t st
     if (!c->enc_ok) return RS_ERR_PANIC;
     if (nlist == 0) return RS_OK;
     return locate_batch_call(c, base, row_stride, stripe_stride, stripes, nlist, S, repair, verdict, stream);
+}
+
+int rs_locate_set_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
+                            const uint32_t *stripes, size_t nlist, size_t S, int max_shards, int repair, int32_t *count,
+                            int32_t *shards, void *stream) {
+    if (!c || !base || !stripes || !count || !shards || max_shards < 1 || max_shards > RS_LOCATE_SET_MAX)
+        return RS_ERR_INVALID_ARG;
+    if (nstripes > (size_t)INT32_MAX || nlist > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    {
+        std::vector<uint32_t> sorted(stripes, stripes + nlist);
+        std::sort(sorted.begin(), sorted.end());
+        if (nlist && sorted.back() >= nstripes) return RS_ERR_INVALID_ARG;
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return RS_ERR_INVALID_ARG;
+    }
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (row_stride < S) return RS_ERR_INVALID_ARG;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    if (nlist == 0) return RS_OK;
+    return locate_set_call(c, base, row_stride, stripe_stride, stripes, nlist, S, max_shards, repair, count, shards, stream);
+}
+
+int rs_scrub_set_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, int nstripes, size_t S,
+                           int max_shards, int repair, int32_t *count, int32_t *shards, int *nbad, void *stream) {
+    if (!c || !base || !count || !shards || nstripes <= 0 || max_shards < 1 || max_shards > RS_LOCATE_SET_MAX)
+        return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    if (nbad) *nbad = 0;
+    if (S == 0) return RS_ERR_SHARD_NO_DATA;
+    if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    if (row_stride < S) return RS_ERR_INVALID_ARG;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    return scrub_set_call(c, base, row_stride, stripe_stride, nstripes, S, max_shards, repair, count, shards, nbad, stream);
+}
+
+int rs_debug_locate_set(int bits, int k, int p, const uint32_t *e, int max_shards, int *count, int32_t *shards) {
+    if ((bits != 8 && bits != 16) || !e || !count || !shards || k <= 0 || p <= 0 || max_shards < 1 ||
+        max_shards > RS_LOCATE_SET_MAX)
+        return RS_ERR_INVALID_ARG;
+    *count = -1;
+    std::fill(shards, shards + max_shards, -1);
+    // the last geometry's tables are kept: a test asks many syndromes of one geometry
+    static std::mutex mu;
+    static int kb = 0, kk = 0, kp = 0;
+    static bool ok = false;
+    static LocateSet ls;
+    static LocateMap map;
+    std::lock_guard<std::mutex> lk(mu);
+    if (kb != bits || kk != k || kp != p) {
+        ok = make_locate_set(field(bits), k, p, ls) && make_locate_map(field(bits), k, p, map);
+        kb = bits, kk = k, kp = p;
+    }
+    if (!ok) return RS_ERR_PANIC;
+    const int cap = std::max(1, std::min(max_shards, ls.cap));
+    if (cap > 1) {
+        int32_t found[kLocateSetMax];
+        const int n = locate_set_decode(field(bits), ls, e, cap, found);
+        *count = n;
+        for (int i = 0; i < n; i++) shards[i] = found[i];
+        return RS_OK;
+    }
+    // the one-shard route's classification (locate_stripe)
+    int nb = 0, bi = -1;
+    for (int i = 0; i < p; i++)
+        if (e[i]) nb++, bi = i;
+    if (!nb) {
+        *count = 0;
+    } else if (p == 1) {
+    } else if (nb == 1) {
+        *count = 1, shards[0] = k + bi;
+    } else if (nb == p) {
+        const int j = locate_shard(field(bits), map, e[0], e[1], nullptr);
+        if (j >= 0) *count = 1, shards[0] = j;
+    }
+    return RS_OK;
+}
+
+int rs_debug_locate_set_stats(uint64_t *out, int reset) {
+    if (!out) return RS_ERR_INVALID_ARG;
+    out[0] = g_set_passes.load(), out[1] = g_set_rounds.load(), out[2] = g_set_waits.load();
+    if (reset) g_set_passes = 0, g_set_rounds = 0, g_set_waits = 0;
+    return RS_OK;
 }
 
 int rs_debug_locate(int bits, int k, int p, uint32_t e0, uint32_t e1, int *shard, uint32_t *scale) {

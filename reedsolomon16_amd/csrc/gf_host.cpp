@@ -742,4 +742,114 @@ void make_repair_tables(const Field &F, uint32_t scale, uint32_t *out) {
     make_twiddle(F, scale ? F.log[scale] : F.mod, out + 2 * twd, true);
 }
 
+namespace {
+inline uint32_t gmul(const Field &F, uint32_t a, uint32_t b) { return a && b ? F.exp[F.add_mod(F.log[a], F.log[b])] : 0; }
+inline uint32_t ginv(const Field &F, uint32_t a) { return F.exp[F.sub_mod(0, F.log[a])]; }
+}  // namespace
+
+bool make_locate_set(const Field &F, int k, int p, LocateSet &ls) {
+    ls = LocateSet{};
+    if (k <= 0 || p <= 0) return false;
+    std::vector<uint32_t> il, fl;
+    int nchunks = 0;
+    if (!encode_schedule(F, k, p, il, fl, nchunks)) return false;
+    const int m = ceil_pow2(p);
+    ls.k = k, ls.p = p, ls.m = m;
+    if ((uint64_t)m + (uint64_t)k > F.order) return true;
+    const bool shift = p < m || (uint32_t)(m + k) < F.order;
+    ls.cap = shift ? std::max(1, std::min(kLocateSetMax, p / 2)) : 1;
+    if (ls.cap == 1) return true;
+    ls.a = p < m ? (uint32_t)p : (uint32_t)(m + k);
+    const int nl = 2 * ls.cap;
+    ls.w.assign((size_t)nl * p, 0);
+    for (int i = 0; i < p; i++) {
+        uint32_t lu = 0;  // log u_i: i ^ y != 0 for i < p <= y
+        for (int y = p; y < m; y++) lu = F.add_mod(lu, F.log[(uint32_t)i ^ (uint32_t)y]);
+        uint32_t v = F.exp[lu];
+        const uint32_t X = (uint32_t)i ^ ls.a;
+        for (int l = 0; l < nl; l++, v = gmul(F, v, X)) ls.w[(size_t)l * p + i] = v;
+    }
+    ls.X.resize((size_t)k + p);
+    for (int j = 0; j < k; j++) ls.X[j] = (uint32_t)(m + j) ^ ls.a;
+    for (int i = 0; i < p; i++) ls.X[(size_t)k + i] = (uint32_t)i ^ ls.a;
+    return true;
+}
+
+int locate_set_decode(const Field &F, const LocateSet &ls, const uint32_t *e, int cap, int32_t *shards) {
+    cap = std::min(cap, ls.cap);
+    const int p = ls.p, N = 2 * cap;
+    bool any = false;
+    for (int i = 0; i < p; i++) any |= e[i] != 0;
+    if (!any) return 0;
+    if (cap < 2 || ls.w.empty()) return -1;
+    uint32_t S[2 * kLocateSetMax] = {};
+    for (int i = 0; i < p; i++) {
+        if (!e[i] || e[i] >= F.order) continue;
+        for (int l = 0; l < N; l++) S[l] ^= gmul(F, ls.w[(size_t)l * p + i], e[i]);
+    }
+    // Berlekamp-Massey: the shortest C with sum_i C[i] * S[n - i] = 0
+    uint32_t C[2 * kLocateSetMax + 2] = {1}, B[2 * kLocateSetMax + 2] = {1}, T[2 * kLocateSetMax + 2];
+    int L = 0, sh = 1;
+    uint32_t b = 1;
+    for (int n = 0; n < N; n++) {
+        uint32_t d = S[n];
+        for (int i = 1; i <= L; i++) d ^= gmul(F, C[i], S[n - i]);
+        if (!d) {
+            sh++;
+            continue;
+        }
+        const uint32_t f = gmul(F, d, ginv(F, b));
+        std::copy(C, C + N + 2, T);
+        for (int i = 0; i + sh < N + 2; i++) C[i + sh] ^= gmul(F, f, B[i]);
+        if (2 * L <= n) {
+            L = n + 1 - L;
+            std::copy(T, T + N + 2, B);
+            b = d;
+            sh = 1;
+        } else {
+            sh++;
+        }
+    }
+    if (L < 1 || L > cap || !C[L]) return -1;
+    // the roots of sigma(X) = sum_i C[i] * X^(L - i) among the locators
+    int n = 0;
+    const size_t total = (size_t)ls.k + p;
+    for (size_t x = 0; x < total; x++) {
+        const uint32_t X = ls.X[x];
+        uint32_t v = 1;
+        for (int i = 1; i <= L; i++) v = gmul(F, v, X) ^ C[i];
+        if (v) continue;
+        if (n == L) return -1;
+        shards[n++] = (int32_t)x;
+    }
+    if (n != L) return -1;
+    for (int i = n; i < cap; i++) shards[i] = -1;
+    return n;
+}
+
+bool invert_matrix(const Field &F, int s, const uint32_t *A, uint32_t *inv) {
+    if (s < 0 || s > kLocateSetMax) return false;
+    uint32_t M[kLocateSetMax][2 * kLocateSetMax] = {};
+    for (int r = 0; r < s; r++) {
+        for (int c = 0; c < s; c++) M[r][c] = A[r * s + c];
+        M[r][s + r] = 1;
+    }
+    for (int c = 0; c < s; c++) {
+        int piv = c;
+        while (piv < s && !M[piv][c]) piv++;
+        if (piv == s) return false;
+        if (piv != c) std::swap_ranges(M[piv], M[piv] + 2 * s, M[c]);
+        const uint32_t iv = ginv(F, M[c][c]);
+        for (int x = 0; x < 2 * s; x++) M[c][x] = gmul(F, M[c][x], iv);
+        for (int r = 0; r < s; r++) {
+            if (r == c || !M[r][c]) continue;
+            const uint32_t f = M[r][c];
+            for (int x = 0; x < 2 * s; x++) M[r][x] ^= gmul(F, f, M[c][x]);
+        }
+    }
+    for (int r = 0; r < s; r++)
+        for (int c = 0; c < s; c++) inv[r * s + c] = M[r][s + c];
+    return true;
+}
+
 }  // namespace rs

@@ -265,4 +265,35 @@ int locate_shard(const Field &F, const LocateMap &map, uint32_t e0, uint32_t e1,
 // three rows in that order.
 void make_repair_tables(const Field &F, uint32_t scale, uint32_t *out);
 
+// ---- Scrub: which set of up to kLocateSetMax shards explains a syndrome
+// (rs_locate_set_dev_batch).  The encode's code is a
+// generalised Reed-Solomon code: with m = ceil_pow2(p), parity shard i at
+// position x = i and data shard j at x = m + j (field symbols, the engine's
+// own labels), and u_x = the product of (x ^ y) over y in [p, m), every
+// codeword c has  sum_x u_x * c_x * (x ^ a)^l = 0  for l < p and any constant
+// a.  With a no shard's position every locator X_x = x ^ a is non-zero: a = p
+// when p < m, else m + k when that is below the field order, else there is no
+// shift point (cap 1).  From the syndrome rows e_i = P_i ^ P'_i at one symbol,
+//   S_l = sum_{i<p} u_i * (i ^ a)^l * e_i
+// are the power sums of that symbol's error: an error D in shard x adds
+// u_x * D * X_x^l.
+constexpr int kLocateSetMax = 4;  // rs_mi355x.h RS_LOCATE_SET_MAX
+struct LocateSet {
+    int k = 0, p = 0, m = 0;
+    int cap = 1;                  // min(kLocateSetMax, p / 2), at least 1; 1 without a shift point
+    uint32_t a = 0;               // the shift
+    std::vector<uint32_t> w;      // 2 * cap rows of p weights: w[l * p + i] = u_i * (i ^ a)^l
+    std::vector<uint32_t> X;      // k + p locators by shard number (data shards first)
+};
+// False where the encode's schedule does not exist.  cap == 1 leaves w and X empty.
+bool make_locate_set(const Field &F, int k, int p, LocateSet &ls);
+// The shards in error at one symbol, from its p syndrome symbols e: Berlekamp-
+// Massey on the 2 * cap power sums (cap = min(cap, ls.cap) >= 2), then the
+// locator's roots among the k + p locators.  Returns their number with the
+// shard numbers ascending in shards[0..cap), 0 when e is all zero, -1 when no
+// locator of degree <= cap with all its roots among the shards fits.
+int locate_set_decode(const Field &F, const LocateSet &ls, const uint32_t *e, int cap, int32_t *shards);
+// inv = A^-1 for the s x s matrix A (row-major, s <= kLocateSetMax); false when singular.
+bool invert_matrix(const Field &F, int s, const uint32_t *A, uint32_t *inv);
+
 }  // namespace rs

@@ -2918,4 +2918,240 @@ hipError_t launch_syndrome_fix(int bits, const ScrubListArgs &a, hipStream_t s) 
 }
 #undef RS_SCRUB_LIST_LAUNCH
 
+// ---------------------------------------------------------------- locate of a set of shards (scrub)
+// rs_locate_set_dev_batch (kernels.hpp ScrubSetArgs): all p syndrome symbols
+// of a stripe at one position for the host's decoder, the confirm of a set of
+// up to four shards on the 2 p parity rows, and its repair.  Beside the four
+// kernels above, whose instantiations stay as they are.  Descriptors and
+// tables are wave-uniform and read-only for the launch (scalar loads); all row
+// addresses are 64-bit (row pointer + offset); no LDS.
+namespace {
+
+static_assert(kScrubSetMax == 4 && kScrubSetDescDwords >= 22, "the descriptor's fields");
+
+// Descriptor blockIdx.y, lanes stride over the parity rows.
+template <bool SYM16>
+__global__ void __launch_bounds__(256) k_syndrome_pick_rows(ScrubSetArgs a) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= (uint32_t)a.p) return;
+    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubPickDescDwords;
+    const uint64_t pos = (uint64_t)d[2] | (uint64_t)d[3] << 32;
+    uint32_t e = 0;
+    if (pos < a.S) {
+        const uint8_t *stored = a.base + (uint64_t)d[0] * a.stripe_stride + ((uint64_t)a.k + i) * a.row_stride;
+        const uint8_t *fresh = a.fresh + (uint64_t)d[1] * a.fresh_slot_stride + (uint64_t)i * a.fresh_stride;
+        auto symbol = [&](const uint8_t *row) -> uint32_t {
+            if constexpr (SYM16) {
+                // low bytes in [0, 32) of the 64-byte block, high bytes in [32, 64)
+                const uint64_t lo = (pos & ~(uint64_t)63) + (pos & 31);
+                return (uint32_t)row[lo] | (uint32_t)row[lo + 32] << 8;
+            } else {
+                return row[pos];
+            }
+        };
+        e = symbol(stored) ^ symbol(fresh);
+    }
+    a.sym[(uint64_t)blockIdx.y * (uint64_t)a.p + i] = e;
+}
+
+// D = A^-1 * e_R for this lane's unit; D[j] is zero for j >= s.
+template <class F>
+__device__ __forceinline__ void set_diffs(const ScrubSetArgs &a, cu32_t *d, const uint8_t *stored, const uint8_t *fresh,
+                                          uint64_t u, int s, typename F::Vec (&D)[kScrubSetMax]) {
+    typedef typename F::Vec V;
+    V eR[kScrubSetMax];
+#pragma unroll
+    for (int r = 0; r < kScrubSetMax; r++) {
+        eR[r] = F::zero();
+        if (r < s) {
+            const uint64_t i = d[8 + r];
+            eR[r] = F::load(stored + i * a.row_stride, u);
+            F::xor_into(eR[r], F::load(fresh + i * a.fresh_stride, u));
+        }
+    }
+    const uint32_t *itw = a.inv_tw + (uint64_t)d[16] * F::TWD;
+#pragma unroll
+    for (int j = 0; j < kScrubSetMax; j++) {
+        D[j] = F::zero();
+        if (j < s) {
+#pragma unroll
+            for (int r = 0; r < kScrubSetMax; r++) {
+                if (r < s) {
+                    const Tab<F> tb = load_tab<F>(itw + (uint64_t)(s * j + r) * F::TWD);
+                    F::mul_add(D[j], eR[r], tb.v);
+                }
+            }
+        }
+    }
+}
+
+// Candidate blockIdx.y: the masks of the s differences are prepared once and
+// shared by the p rows; row i outside J_p must satisfy e_i == sum_j G[i][J_d[j]] * D_j.
+// A row of J_p is not part of the test; whether it differs from its right
+// content goes into `used`, as whether D_j is non-zero does.
+template <class F>
+__global__ void __launch_bounds__(256, 2) k_syndrome_confirm_set(ScrubSetArgs a) {
+    typedef typename F::Vec V;
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubSetDescDwords;
+    const uint8_t *stored = a.base + (uint64_t)d[0] * a.stripe_stride + (uint64_t)a.k * a.row_stride;
+    const uint8_t *fresh = a.fresh + (uint64_t)d[1] * a.fresh_slot_stride;
+    const uint32_t n = d[2];
+    const int s = (int)d[3];
+    const uint32_t x0 = d[12], x1 = d[13], x2 = d[14], x3 = d[15];
+    int *used = a.used + (uint64_t)n * 8;
+    UpdMasks<F> mk[kScrubSetMax];
+    const uint32_t *ctw[kScrubSetMax];
+    {
+        V D[kScrubSetMax];
+        set_diffs<F>(a, d, stored, fresh, u, s, D);
+#pragma unroll
+        for (int j = 0; j < kScrubSetMax; j++) {
+            mk[j].prepare(D[j]);
+            ctw[j] = a.col_tw + (uint64_t)d[4 + j] * (uint64_t)a.p * F::TWD;  // table (slot, i) at ctw + i * TWD
+            if (j < s) flag_mismatch(used + j, F::diff(D[j], F::zero()) != 0);
+        }
+    }
+    V any = F::zero();
+    auto row = [&](V &x, int i) {  // x = e_i on entry
+#pragma unroll
+        for (int j = 0; j < kScrubSetMax; j++) {
+            if (j < s) {
+                const Tab<F> tb = load_tab<F>(ctw[j] + (uint64_t)i * F::TWD);
+                mk[j].mul_add(x, tb.v);
+            }
+        }
+        const uint32_t ui = (uint32_t)i;
+        if (ui == x0 || ui == x1 || ui == x2 || ui == x3) {
+            const int q = ui == x0 ? 0 : ui == x1 ? 1 : ui == x2 ? 2 : 3;
+            flag_mismatch(used + 4 + q, F::diff(x, F::zero()) != 0);
+        } else {
+            or_into<F>(any, x);
+        }
+    };
+    int i = 0;
+    for (; i + kConfRows <= a.p; i += kConfRows) {
+        V x[kConfRows], y[kConfRows];
+#pragma unroll
+        for (int q = 0; q < kConfRows; q++) {
+            x[q] = F::load(stored + (uint64_t)(i + q) * a.row_stride, u);
+            y[q] = F::load(fresh + (uint64_t)(i + q) * a.fresh_stride, u);
+        }
+#pragma unroll
+        for (int q = 0; q < kConfRows; q++) {
+            F::xor_into(x[q], y[q]);
+            row(x[q], i + q);
+        }
+    }
+    for (; i < a.p; i++) {
+        V x = F::load(stored + (uint64_t)i * a.row_stride, u);
+        F::xor_into(x, F::load(fresh + (uint64_t)i * a.fresh_stride, u));
+        row(x, i);
+    }
+    // lanes own ascending units: the first lane that saw a failure holds the wave's minimum
+    const uint64_t m = __ballot(F::diff(any, F::zero()) != 0);
+    if (m && __lane_id() == (unsigned)(__ffsll((unsigned long long)m) - 1)) {
+        // flag_mismatch's body on the ballot the atomic minimum needs anyway (set stays set)
+        if (__hip_atomic_load(a.bad + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
+            __hip_atomic_store(a.bad + n, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_min(a.fail + n, (unsigned long long)(F::off(u) + first_symbol<F>(any)), __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// The confirmed candidate blockIdx.y: D again, then the data rows of J_d and
+// the parity rows of J_p in place.  R and J_p are disjoint and R holds parity
+// rows only, so no row that D is formed from is written.
+template <class F>
+__global__ void __launch_bounds__(256, 2) k_syndrome_fix_set(ScrubSetArgs a) {
+    typedef typename F::Vec V;
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubSetDescDwords;
+    uint8_t *sb = a.base + (uint64_t)d[0] * a.stripe_stride;
+    uint8_t *stored = sb + (uint64_t)a.k * a.row_stride;
+    const uint8_t *fresh = a.fresh + (uint64_t)d[1] * a.fresh_slot_stride;
+    const int s = (int)d[3];
+    const uint32_t wr = d[21];
+    V D[kScrubSetMax];
+    set_diffs<F>(a, d, stored, fresh, u, s, D);
+#pragma unroll
+    for (int j = 0; j < kScrubSetMax; j++) {
+        if (j < s && (wr >> j & 1)) {
+            uint8_t *r = sb + (uint64_t)d[17 + j] * a.row_stride;
+            V x = F::load(r, u);
+            F::xor_into(x, D[j]);
+            F::store(r, u, x);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kScrubSetMax; q++) {
+        const uint32_t i = d[12 + q];
+        if (i < (uint32_t)a.p && (wr >> (4 + q) & 1)) {
+            V x = F::load(fresh + (uint64_t)i * a.fresh_stride, u);
+#pragma unroll
+            for (int j = 0; j < kScrubSetMax; j++) {
+                if (j < s) {
+                    const uint32_t *ctw = a.col_tw + ((uint64_t)d[4 + j] * (uint64_t)a.p + i) * F::TWD;
+                    const Tab<F> tb = load_tab<F>(ctw);
+                    F::mul_add(x, D[j], tb.v);
+                }
+            }
+            F::store(stored + (uint64_t)i * a.row_stride, u, x);
+        }
+    }
+}
+
+bool scrub_set_ok(const ScrubSetArgs &a) {
+    return a.p > 0 && a.k > 0 && a.nlist > 0 && a.nlist <= kScrubMaxList && a.S != 0 && a.S % 64 == 0 && a.base &&
+           a.fresh && a.list && a.row_stride >= a.S && a.fresh_stride >= a.S;
+}
+// Unit widths by scrub_list_narrow's rule over the descriptors.
+bool scrub_set_narrow(int bits, const ScrubSetArgs &a) {
+    ScrubListArgs l{};
+    l.S = a.S;
+    l.nlist = a.nlist;
+    return scrub_list_narrow(bits, l);
+}
+template <class F>
+dim3 scrub_set_grid(const ScrubSetArgs &a) {
+    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
+    return dim3(grid_x(units).x, (unsigned)a.nlist);
+}
+
+}  // namespace
+
+#define RS_SCRUB_SET_LAUNCH(kernel)                                                                                 \
+    do {                                                                                                            \
+        const bool narrow = scrub_set_narrow(bits, a);                                                              \
+        if (bits == 16) {                                                                                           \
+            if (narrow) hipLaunchKernelGGL(kernel<F16<2>>, scrub_set_grid<F16<2>>(a), dim3(256), 0, s, a);          \
+            else hipLaunchKernelGGL(kernel<F16<4>>, scrub_set_grid<F16<4>>(a), dim3(256), 0, s, a);                 \
+        } else {                                                                                                    \
+            if (narrow) hipLaunchKernelGGL(kernel<F8<2>>, scrub_set_grid<F8<2>>(a), dim3(256), 0, s, a);            \
+            else hipLaunchKernelGGL(kernel<F8<4>>, scrub_set_grid<F8<4>>(a), dim3(256), 0, s, a);                   \
+        }                                                                                                           \
+        return hipGetLastError();                                                                                   \
+    } while (0)
+
+hipError_t launch_syndrome_pick_rows(int bits, const ScrubSetArgs &a, hipStream_t s) {
+    if (!scrub_set_ok(a) || !a.sym) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.p + 255) / 256), (unsigned)a.nlist);
+    if (bits == 16) hipLaunchKernelGGL(k_syndrome_pick_rows<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_syndrome_pick_rows<false>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_syndrome_confirm_set(int bits, const ScrubSetArgs &a, hipStream_t s) {
+    if (!scrub_set_ok(a) || !a.col_tw || !a.inv_tw || !a.bad || !a.used || !a.fail) return hipErrorInvalidValue;
+    RS_SCRUB_SET_LAUNCH(k_syndrome_confirm_set);
+}
+
+hipError_t launch_syndrome_fix_set(int bits, const ScrubSetArgs &a, hipStream_t s) {
+    if (!scrub_set_ok(a) || !a.col_tw || !a.inv_tw) return hipErrorInvalidValue;
+    RS_SCRUB_SET_LAUNCH(k_syndrome_fix_set);
+}
+#undef RS_SCRUB_SET_LAUNCH
+
 }  // namespace rs

@@ -391,4 +391,46 @@ hipError_t launch_syndrome_confirm(int bits, const ScrubListArgs &a, hipStream_t
 // rows, writes one, each lane its own unit.
 hipError_t launch_syndrome_fix(int bits, const ScrubListArgs &a, hipStream_t s);
 
+// ---- The locate of up to kScrubSetMax corrupt shards per stripe
+// (rs_locate_set_dev_batch): three kernels beside the four above, over the
+// same scratch slots.  A candidate is a set J of shards: s data shards J_d
+// (ascending) and up to kScrubSetMax - s parity rows J_p; R = the first s
+// parity rows not in J_p; A = G[R][J_d].  With e_i = P_i ^ P'_i the data
+// shards' differences are D = A^-1 * e_R, and J explains the stripe iff
+// e_i == sum_j G[i][J_d[j]] * D_j in every parity row i outside J_p.
+constexpr int kScrubSetMax = 4;
+// A confirm / fix descriptor (dwords): [0] stripe, [1] slot, [2] candidate
+// number n, [3] s, [4..7] column-table slots of J_d, [8..11] the rows R,
+// [12..15] the rows J_p (unused: 0xffffffff), [16] first A^-1 table (table
+// (j, r) = multiply by A^-1[j][r] at inv_tw + ([16] + s j + r) * tw_dwords),
+// [17..20] the data shards J_d, [21] fix: bit j set = write data shard
+// J_d[j], bit 4 + q = write parity row J_p[q]; [22..23] unused.
+constexpr int kScrubSetDescDwords = 24;
+constexpr int kScrubPickDescDwords = 4;  // pick-rows: stripe, slot, byte position (low, high dword)
+struct ScrubSetArgs {
+    uint8_t *base;  // as ScrubListArgs
+    uint64_t row_stride, stripe_stride;
+    const uint8_t *fresh;
+    uint64_t fresh_stride, fresh_slot_stride;
+    uint64_t S;
+    int k, p, nlist;
+    const uint32_t *list;      // nlist descriptors
+    uint32_t *sym;             // pick-rows: p symbols per descriptor
+    const uint32_t *col_tw;    // column tables (make_update_columns)
+    const uint32_t *inv_tw;    // A^-1 tables (make_twiddle)
+    int *bad;                  // confirm: word n set when candidate n does not explain its stripe
+    int *used;                 // confirm: word 8 n + j set when D_j != 0 anywhere, word 8 n + 4 + q when
+                               // parity row J_p[q] differs from its right content anywhere
+    unsigned long long *fail;  // confirm: fail[n] = min(fail[n], byte offset of the first failing symbol)
+};
+// sym[q * p + i] = stored ^ fresh symbol of parity row i at the descriptor's
+// byte position (GF(2^16): the low byte there, the high byte 32 above).
+hipError_t launch_syndrome_pick_rows(int bits, const ScrubSetArgs &a, hipStream_t s);
+// Reads 2 p rows, writes only bad, used and fail.
+hipError_t launch_syndrome_confirm_set(int bits, const ScrubSetArgs &a, hipStream_t s);
+// data row J_d[j] ^= D_j; parity row i of J_p = P'_i ^ sum_j G[i][J_d[j]] * D_j
+// (P' was computed from the damaged data).  Rows of R are never written, each
+// lane owns its own unit.
+hipError_t launch_syndrome_fix_set(int bits, const ScrubSetArgs &a, hipStream_t s);
+
 }  // namespace rs

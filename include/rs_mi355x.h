@@ -702,6 +702,70 @@ int rs_scrub_set_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, 
                            size_t shard_size, int max_shards, int repair, int32_t *count /* nstripes, host */,
                            int32_t *shards /* nstripes * max_shards, host */, int *nbad, void *stream);
 
+/* Checked rebuild: rs_reconstruct_dev_batch_patterns with recover_all = 1 (its
+ * slab, table and stream rules) that also says, per stripe, whether the
+ * survivors it rebuilt from were consistent, and where they were not names the
+ * corrupt survivors and repairs them.  A row marked missing is output only: its
+ * content on entry influences no result.  count: host, nstripes int32; shards:
+ * host, nstripes * max(max_shards, 1) int32; *nbad (may be NULL) = the number
+ * of stripes with count != 0.  For a stripe with e missing rows,
+ * cap_z = min(max_shards, (p - e) / 2), which may be 0:
+ *   count[z] == 0: the survivors are consistent; every missing row holds what
+ *     rs_reconstruct_dev_batch_patterns writes.  With e == p no redundancy is
+ *     left to check and the count is always 0;
+ *   count[z] == c in 1..cap_z: exactly the c survivors shards[z * stride ..]
+ *     (ascending, unused entries -1) are corrupt, and each of them really
+ *     changes.  repair != 0: those survivors and all missing rows end bit for
+ *     bit as the codeword has them.  repair == 0: no survivor is written and
+ *     the missing rows hold what rs_reconstruct_dev_batch_patterns writes from
+ *     the survivors as they are;
+ *   count[z] == RS_SCRUB_UNLOCATED: the survivors are inconsistent and no set
+ *     of at most cap_z of them explains it; no survivor is written and the
+ *     missing rows are as under repair == 0.
+ * No survivor is written before its set is confirmed on every parity row at
+ * every symbol; nothing outside the listed survivors and the missing rows is
+ * written.  A stripe with nothing missing gets exactly rs_scrub_set_dev_batch's
+ * count, shards and repair (max_shards == 0: clean or RS_SCRUB_UNLOCATED).
+ * How: the patterns reconstruct and rs_verify_dev_batch_map's
+ * launches, unchanged; a rebuilt stripe verifies exactly when its survivors
+ * are consistent.  For a stripe that does not, the syndromes of the filled
+ * stripe are power sums over the corrupt survivors and the missing rows; the
+ * erasure locator of the missing rows folds them into p - e modified
+ * syndromes, Berlekamp-Massey on the host names up to cap_z survivors, one
+ * launch confirms the set against the check matrix of the pattern, and one
+ * launch repairs the survivors and the e rebuilt rows in place.  At most cap_z
+ * rounds and 1 + 2 * cap_z host waits per pass.
+ * Limits.  e == p is unchecked.  cap_z shrinks with e.  Where the geometry has
+ * no shift point for the locators (GF(2^8) 128+128, see rs_locate_set_dev_batch)
+ * an inconsistent stripe with e >= 1 is RS_SCRUB_UNLOCATED.  A located set is
+ * the true set whenever (truly corrupt survivors) + count <= p - e; beyond that
+ * a Reed-Solomon decoder can mis-correct.  Single-device codecs only.
+ * Errors, all decided before any device call: rs_reconstruct_dev_batch_patterns's
+ * table in its order, with NULL count / shards among the NULL checks; then
+ * max_shards outside [0, RS_LOCATE_SET_MAX] -> RS_ERR_INVALID_ARG.
+ * Measured on one MI355X at 128+32 x 1 MiB, 256 stripes, the shard order
+ * rotated per stripe, one device lost (profiles/checked_rebuild_c4.txt,
+ * DESIGN.md 4.18), ms per call.  Clean slab: 31.20 against 31.19 for the
+ * parent's rs_reconstruct_dev_batch_patterns followed by rs_verify_dev_batch_map
+ * (+0.01, inside their spread; +0.05 with 32 devices lost).  One corrupt
+ * survivor in 1 / 8 / 64 / 256 stripes, repair = 1: 31.36 / 31.92 / 35.84 /
+ * 49.64, that is 159 / 90 / 73 / 72 us per bad stripe, against 115 / 93 / 91 /
+ * 91 us for a second rs_reconstruct_dev_batch_patterns of a stripe whose bad
+ * shard is known from elsewhere; the repair launch itself is 2 us of that.
+ * Two survivors in disjoint places (two rounds): 97 us per bad stripe at 256.
+ * 1024+256 x 256 KiB, 8 stripes, two survivors each: 9.18 ms over a 5.00 ms
+ * clean call.  The first call that meets an erasure pattern builds its
+ * coefficient rows on the host, about 0.14 ms per pattern, kept in the codec.
+ * Not measured: GF(2^8) codecs, the split of a pass between launches and
+ * waits, the repair kernel alone under a trace. */
+int rs_reconstruct_checked_dev_batch_patterns(rs_codec *codec, uint8_t *d_base, size_t row_stride, size_t stripe_stride,
+                                              size_t nstripes, const uint8_t *present /* npatterns x (k+p) */,
+                                              size_t npatterns, const uint32_t *pattern_of /* nstripes, host */,
+                                              size_t shard_size, int max_shards /* 0 .. RS_LOCATE_SET_MAX */, int repair,
+                                              int32_t *count /* nstripes, host */,
+                                              int32_t *shards /* nstripes * max(max_shards, 1), host */,
+                                              int *nbad /* may be NULL */, void *stream);
+
 /* ---------------- Host-only diagnostics (no device calls; used by CPU tests) ---------------- */
 /* Field tables as built by the engine (initLUTs/initFFTSkew, leopard16.go:940-1031). */
 int rs_debug_field_tables(int field_bits, uint16_t *log_out, uint16_t *exp_out, uint16_t *skew_out,
@@ -771,6 +835,25 @@ int rs_debug_locate_set(int field_bits, int data_shards, int parity_shards, cons
  * tests/test_gpu_scrub_set.py asserts with them.  reset != 0 clears them
  * after the read.  RS_ERR_INVALID_ARG for a NULL out. */
 int rs_debug_locate_set_stats(uint64_t *out /* 3 */, int reset);
+/* The checked rebuild's check matrix: out[i] = H[i][shard],
+ * the change of syndrome row i of the filled stripe per unit difference in
+ * survivor `shard` when the rows with present[i] == 0 were filled from all
+ * survivors.  RS_ERR_INVALID_ARG for bad arguments or a missing `shard`,
+ * RS_ERR_PANIC where the reference panics or fewer than k rows are present. */
+int rs_debug_check_column(int field_bits, int data_shards, int parity_shards, const uint8_t *present /* k+p */,
+                          int shard, uint32_t *out /* p symbols */);
+/* The checked rebuild's host decoder on the p syndrome symbols e of a filled
+ * stripe at one position: *count = the number of corrupt survivors there,
+ * ascending in shards[0 .. max(cap, 1)) (unused entries -1); 0 when e is all
+ * zero; -1 when nothing of size <= min(cap, (p - e) / 2) fits or no shift
+ * point exists.  Nothing missing: rs_debug_locate_set's answer (cap 0: 0 or
+ * -1).  cap in 0..RS_LOCATE_SET_MAX. */
+int rs_debug_locate_set_present(int field_bits, int data_shards, int parity_shards, const uint8_t *present /* k+p */,
+                                const uint32_t *e /* p symbols */, int cap, int *count, int32_t *shards);
+/* rs_debug_locate_set_stats for the checked rebuild's route over stripes with
+ * missing rows: passes, confirm rounds, host waits (without the map's and the
+ * call's final one). */
+int rs_debug_checked_stats(uint64_t *out /* 3 */, int reset);
 
 /* Checks the half-wave split schedules of the GF(2^16) encode kernel
  * (logm 2..5) against the plain butterfly order on random symbols and

@@ -73,6 +73,11 @@ def lib() -> C.CDLL:
     L.rs_debug_locate.argtypes = [i32, i32, i32, C.c_uint32, C.c_uint32, P(i32), P(C.c_uint32)]
     L.rs_debug_locate_set.argtypes = [i32, i32, i32, vp, i32, P(i32), vp]
     L.rs_debug_locate_set_stats.argtypes = [P(C.c_uint64), i32]
+    L.rs_reconstruct_checked_dev_batch_patterns.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint8), sz, P(C.c_uint32), sz,
+                                                            i32, i32, vp, vp, P(i32), vp]
+    L.rs_debug_check_column.argtypes = [i32, i32, i32, P(C.c_uint8), i32, vp]
+    L.rs_debug_locate_set_present.argtypes = [i32, i32, i32, P(C.c_uint8), vp, i32, P(i32), vp]
+    L.rs_debug_checked_stats.argtypes = [P(C.c_uint64), i32]
     L.rs_debug_generator.argtypes = [i32, i32, i32, i32, vp]
     L.rs_set_host_segment.argtypes = [vp, sz]
     L.rs_set_reference_inversion_cache.argtypes = [vp, i32]

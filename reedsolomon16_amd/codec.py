@@ -766,6 +766,37 @@ class ReedSolomon:
             self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, table.ctypes.data_as(C.POINTER(C.c_uint8)),
             table.shape[0], of.ctypes.data_as(C.POINTER(C.c_uint32)), S, int(recover_all), _stream_handle(stream)))
 
+    def reconstruct_checked_dev_batch_patterns(self, slab, patterns, pattern_of: Sequence[int],
+                                               max_shards: int = LOCATE_SET_MAX, repair: bool = False, stream=None):
+        """reconstruct_dev_batch_patterns (all missing rows) that also checks
+        the survivors it rebuilt from (rs_reconstruct_checked_dev_batch_patterns):
+        (count, shards), int32 arrays of shape [nstripes] and
+        [nstripes, max(max_shards, 1)].  count 0: the survivors were
+        consistent; c > 0: the c survivors listed (ascending, padded with -1)
+        are corrupt; SCRUB_UNLOCATED: inconsistent, and no set of
+        min(max_shards, (p - missing) // 2) survivors explains it.  repair: the
+        listed survivors and the missing rows end as the codeword has them;
+        otherwise no survivor is written."""
+        n, S = self._slab(slab)
+        table = np.ascontiguousarray(np.asarray(patterns, dtype=bool).astype(np.uint8))
+        if table.ndim != 2 or table.shape[1] != self.total_shards():
+            raise ErrTooFewShards("patterns must have %d flags per row" % self.total_shards())
+        of = np.ascontiguousarray(np.asarray(pattern_of, dtype=np.int64))
+        if of.shape != (n,):
+            raise TypeError("pattern_of must name one pattern per stripe")
+        if of.size and (of.min() < 0 or of.max() >= 1 << 32):
+            raise ErrInvalidArg("pattern_of entries must be pattern numbers")
+        of = of.astype(np.uint32)
+        max_shards = int(max_shards)
+        count = np.full(max(n, 1), SCRUB_UNLOCATED, np.int32)
+        shards = np.full((max(n, 1), max(max_shards, 1)), -1, np.int32)
+        nbad = C.c_int(0)
+        _check(self._L.rs_reconstruct_checked_dev_batch_patterns(
+            self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, table.ctypes.data_as(C.POINTER(C.c_uint8)),
+            table.shape[0], of.ctypes.data_as(C.POINTER(C.c_uint32)), S, max_shards, int(bool(repair)), count.ctypes.data,
+            shards.ctypes.data, C.byref(nbad), _stream_handle(stream)))
+        return count[:n], shards[:n]
+
     def _flags(self, flags: Sequence[bool], what: str):
         if len(flags) != self.total_shards():
             raise ErrTooFewShards("need %d %s flags, got %d" % (self.total_shards(), what, len(flags)))

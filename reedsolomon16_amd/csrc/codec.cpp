@@ -377,6 +377,14 @@ struct rs_codec {
     LocateSet locate_set;
     DevBuf<uint8_t> scrub_set_dev;
     PinnedBuf scrub_set_host;
+    // rs_reconstruct_checked_dev_batch_patterns: all p weight rows and the
+    // locators of the errors-and-erasures decoder (built on the first use)
+    bool locate_present_built = false;
+    LocatePresent locate_present;
+    // ... and the coefficient rows of the erasure patterns it has met (host
+    // data only), dropped as a whole past kChkCacheBytes
+    std::map<std::vector<uint8_t>, std::shared_ptr<const PresentPattern>> chk_cache;
+    size_t chk_cache_bytes = 0;
 
     // error-locator cache keyed by erasure pattern (bounded LRU)
     Lru<std::vector<uint8_t>, std::vector<uint32_t>, 64> el_cache;
@@ -3175,6 +3183,444 @@ int reconstruct_patterns_call(rs_codec *c, uint8_t *base, size_t row_stride, siz
     return dc.finish(RS_OK);
 }
 
+// ---- Checked rebuild (rs_reconstruct_checked_dev_batch_patterns)
+// Passes, confirm rounds and host waits of the checked locate so far (rs_debug_checked_stats).
+std::atomic<uint64_t> g_chk_passes{0}, g_chk_rounds{0}, g_chk_waits{0};
+
+// An erasure pattern of the call with a bad stripe: its coefficient rows,
+// built once per call, and the check columns asked for so far.
+constexpr size_t kChkCacheBytes = 64u << 20;
+struct ChkPattern {
+    std::vector<uint8_t> present;
+    std::shared_ptr<const PresentPattern> ppp;
+    int cap = 0;  // cap_z of its stripes
+    std::map<int, std::vector<uint32_t>> H;
+    const std::vector<uint32_t> &column(rs_codec *c, int t) {
+        auto it = H.find(t);
+        if (it == H.end()) {
+            std::vector<uint32_t> h((size_t)c->p);
+            check_column(*c->F, c->k, c->p, *ppp, t, c->enc_ifft_logs, c->enc_fft_logs, h.data());
+            it = H.emplace(t, std::move(h)).first;
+        }
+        return it->second;
+    }
+};
+
+// A candidate set of corrupt survivors of a listed stripe: nj shards J, ascending.
+struct ChkCand {
+    uint32_t e = 0;  // entry of the pass (its scratch slot)
+    int pat = 0;     // its ChkPattern
+    int nj = 0;
+    int J[kLocateSetMax] = {};
+    uint64_t pos = 0;  // where the next decode reads its symbols
+};
+
+// count[e] and shards[e * stride ..] for stripes[0..nlist), each with missing
+// rows already filled from its survivors and with cap_z >= 1, on the caller's
+// stream s inside the caller's scratch_acquire / scratch_release, with
+// locate_set_list_device's pass rules.  Per pass: the recompute and the list
+// scan with one readback (host wait 1); every bad entry is decoded at its
+// first differing position (errors and erasures); then rounds of
+// k_syndrome_confirm_set over all candidates, the check columns H[.][t] as its
+// column tables and no J_p (one readback), and for those that fail with room
+// left a pick at the first failing position (one readback) and a decode that
+// must add a survivor: at most cap rounds, 1 + 2 cap host waits.  The repairs
+// of the confirmed sets are one k_syndrome_fix_present launch, left to the
+// caller's final wait.
+int locate_present_list_device(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride,
+                               const uint32_t *stripes, const int *pat_of, size_t nlist, std::vector<ChkPattern> &pats,
+                               uint64_t S, int stride, bool repair, hipStream_t s, int32_t *count, int32_t *shards) {
+    const int k = c->k, p = c->p;
+    const LocatePresent &lp = c->locate_present;
+    for (size_t e = 0; e < nlist; e++) count[e] = RS_SCRUB_UNLOCATED;
+    std::fill(shards, shards + nlist * (size_t)stride, -1);
+    if (!nlist) return RS_OK;
+    uint64_t qs = S;  // locate_list_device's scratch rule
+    const uint64_t ds = k > 1 ? row_stride : 0;
+    if (c->bs_ok && ds >= S && ds <= 2 * S && encode_bs_fits(k, p, ds, S)) qs = ds;
+    const size_t slot_bytes = align256((size_t)p * qs);
+    const size_t twb = (size_t)c->twd * 4, db = 4 * (size_t)kScrubSetDescDwords;
+    size_t chunk = std::min<size_t>(nlist, (size_t)kScrubMaxList);
+    chunk = std::min(chunk, std::max<size_t>(1, kScrubListScratch / slot_bytes));
+    // a candidate's tables: up to four check columns of p entries, and as many fix coefficients per missing row
+    chunk = std::min(chunk, std::max<size_t>(1, (64u << 20) / (2 * kLocateSetMax * (size_t)p * twb)));
+    if (const int knob = g_path_scrub_chunk.load(std::memory_order_relaxed)) chunk = std::min(chunk, (size_t)knob);
+    if (int e = scratch_ensure(c, c->scrub_rows, chunk * slot_bytes)) return e;
+    const size_t o_rowbad = align256(8 * chunk), scan_bytes = o_rowbad + align256(4 * chunk * p);
+    if (int e = scratch_ensure(c, c->scrub_list_dev, scan_bytes)) return e;
+    if (scan_bytes > c->scrub_list_host.n) {
+        if (int e = scratch_host_wait(c)) return e;
+        HIP_TRY(c->scrub_list_host.ensure(scan_bytes));
+    }
+    // confirm and pick results, as locate_set_list_device
+    const size_t o_used = align256(4 * chunk), o_fail = o_used + align256(32 * chunk);
+    const size_t o_sym = o_fail + align256(8 * chunk), set_bytes = o_sym + align256(4 * chunk * p);
+    if (int e = scratch_ensure(c, c->scrub_set_dev, set_bytes)) return e;
+    if (set_bytes > c->scrub_set_host.n) {
+        if (int e = scratch_host_wait(c)) return e;
+        HIP_TRY(c->scrub_set_host.ensure(set_bytes));
+    }
+    uint8_t *q = c->scrub_rows.p, *dev = c->scrub_list_dev.p, *sdev = c->scrub_set_dev.p;
+    uint8_t *host = c->scrub_list_host.p, *shost = c->scrub_set_host.p;
+    ScrubListArgs a{};
+    a.base = base;
+    a.row_stride = row_stride;
+    a.stripe_stride = stripe_stride;
+    a.fresh = q;
+    a.fresh_stride = qs;
+    a.fresh_slot_stride = slot_bytes;
+    a.S = S;
+    a.k = k;
+    a.p = p;
+    a.first = (unsigned long long *)dev;
+    a.rowbad = (int *)(dev + o_rowbad);
+    ScrubSetArgs b{};
+    b.base = base;
+    b.row_stride = row_stride;
+    b.stripe_stride = stripe_stride;
+    b.fresh = q;
+    b.fresh_stride = qs;
+    b.fresh_slot_stride = slot_bytes;
+    b.S = S;
+    b.k = k;
+    b.p = p;
+    b.sym = (uint32_t *)(sdev + o_sym);
+    b.bad = (int *)sdev;
+    b.used = (int *)(sdev + o_used);
+    b.fail = (unsigned long long *)(sdev + o_fail);
+    std::vector<ChkCand> conf, pick, good;
+    std::vector<uint32_t> sym((size_t)p);
+    std::vector<int> order((size_t)p);
+    auto log_of = [&](uint32_t v) { return v ? c->F->log[v] : c->F->mod; };
+    auto same = [](const ChkCand &x, const ChkCand &y) {
+        return x.pat == y.pat && x.nj == y.nj && std::equal(x.J, x.J + x.nj, y.J);
+    };
+    auto by_set = [](const ChkCand &x, const ChkCand &y) {
+        if (x.pat != y.pat) return x.pat < y.pat;
+        return std::lexicographical_compare(x.J, x.J + x.nj, y.J, y.J + y.nj);
+    };
+
+    // One launch over cand (sorted by by_set): the confirm, or with wr (the
+    // write bits, one word per candidate) the fix.  Candidates with equal
+    // (pattern, T) share their tables.  Image of the ring slot: descriptors,
+    // A^-1 tables, then the check columns (confirm) or the missing rows' numbers
+    // and the fix coefficients (fix).
+    auto launch = [&](const std::vector<ChkCand> &cand, const uint32_t *zs, const uint32_t *wr) -> int {
+        const size_t nc = cand.size();
+        size_t ninv = 0, ncol = 0, nrow = 0, nfix = 0;
+        for (size_t i = 0; i < nc; i++) {
+            if (i && same(cand[i - 1], cand[i])) continue;
+            const size_t sj = (size_t)cand[i].nj, ne = pats[cand[i].pat].ppp->E.size();
+            ninv += sj * sj, ncol += sj, nrow += ne, nfix += ne * sj;
+        }
+        const size_t o_inv = align256(db * nc), o_col = o_inv + align256(ninv * twb);
+        const size_t o_rows = o_col, o_fix = o_rows + align256(4 * nrow);
+        const size_t need = wr ? o_fix + std::max<size_t>(1, nfix) * twb : o_col + ncol * (size_t)p * twb;
+        int slot = 0;
+        uint8_t *h = nullptr, *g = nullptr;
+        if (int e = ring_acquire(c, need, slot, h, g)) return e;
+        size_t tinv = 0, tcol = 0, trow = 0, tfix = 0;
+        for (size_t i = 0; i < nc; i++) {
+            const ChkCand &cd = cand[i];
+            uint32_t *d = (uint32_t *)(h + db * i);
+            if (i && same(cand[i - 1], cd)) {
+                std::copy(d - kScrubSetDescDwords, d, d);
+            } else {
+                ChkPattern &pt = pats[cd.pat];
+                std::fill(d, d + kScrubSetDescDwords, 0u);
+                const uint32_t *cols[kLocateSetMax] = {};
+                for (int j = 0; j < cd.nj; j++) cols[j] = pt.column(c, cd.J[j]).data();
+                // R: rows of surviving parity shards outside T first, so that a
+                // row D is formed from is written only where nothing else works
+                check_row_order(k, p, pt.present.data(), cd.J, cd.nj, order.data());
+                int R[kLocateSetMax] = {};
+                uint32_t inv[kLocateSetMax * kLocateSetMax];
+                // (|T| <= p - e: the punctured code's distance gives the columns full rank)
+                if (!pick_check_rows(*c->F, p, cd.nj, cols, order.data(), R, inv)) return RS_ERR_DEVICE;
+                d[3] = (uint32_t)cd.nj;
+                for (int x = 0; x < kScrubSetMax; x++) d[12 + x] = 0xffffffffu;  // the confirm: no J_p
+                d[16] = (uint32_t)tinv;
+                for (int x = 0; x < cd.nj * cd.nj; x++, tinv++)
+                    make_twiddle(*c->F, log_of(inv[x]), (uint32_t *)(h + o_inv + tinv * twb), true);
+                for (int j = 0; j < cd.nj; j++) {
+                    d[8 + j] = (uint32_t)R[j];
+                    d[17 + j] = (uint32_t)cd.J[j];
+                    if (!wr) {
+                        d[4 + j] = (uint32_t)tcol;
+                        for (int i2 = 0; i2 < p; i2++)
+                            make_twiddle(*c->F, log_of(cols[j][i2]), (uint32_t *)(h + o_col + (tcol * p + i2) * twb), true);
+                        tcol++;
+                    }
+                }
+                if (wr) {
+                    const size_t ne = pt.ppp->E.size();
+                    d[12] = (uint32_t)ne;
+                    d[13] = (uint32_t)trow;
+                    d[14] = (uint32_t)tfix;
+                    for (size_t x = 0; x < ne; x++) {
+                        ((uint32_t *)(h + o_rows))[trow++] = (uint32_t)pt.ppp->E[x];
+                        for (int j = 0; j < cd.nj; j++, tfix++)
+                            make_twiddle(*c->F, log_of(pt.ppp->co[x][cd.J[j]]), (uint32_t *)(h + o_fix + tfix * twb), true);
+                    }
+                }
+            }
+            d[0] = zs[cd.e];
+            d[1] = cd.e;
+            d[2] = (uint32_t)i;
+            d[21] = wr ? wr[i] : 0;
+        }
+        HIP_TRY(hipMemcpyAsync(g, h, need, hipMemcpyHostToDevice, s));
+        b.list = (const uint32_t *)g;
+        b.nlist = (int)nc;
+        b.inv_tw = (const uint32_t *)(g + o_inv);
+        if (wr) {
+            ScrubPresentArgs pa{};
+            pa.set = b;
+            pa.rows = (const uint32_t *)(g + o_rows);
+            pa.fix_tw = (const uint32_t *)(g + o_fix);
+            HIP_TRY(launch_syndrome_fix_present(c->bits, pa, s));
+        } else {
+            b.col_tw = (const uint32_t *)(g + o_col);
+            HIP_TRY(launch_syndrome_confirm_set(c->bits, b, s));
+        }
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+        return RS_OK;
+    };
+
+    for (size_t c0 = 0; c0 < nlist; c0 += chunk) {
+        const size_t n = std::min(chunk, nlist - c0);
+        const uint32_t *zs = stripes + c0;
+        int32_t *cnt = count + c0, *sh = shards + c0 * (size_t)stride;
+        int slot = 0;
+        uint8_t *h = nullptr, *g = nullptr;
+        if (int e = ring_acquire(c, 4 * n, slot, h, g)) return e;
+        std::memcpy(h, zs, 4 * n);
+        HIP_TRY(hipMemcpyAsync(g, h, 4 * n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(dev, 0xff, 8 * n, s));
+        HIP_TRY(hipMemsetAsync(dev + o_rowbad, 0, scan_bytes - o_rowbad, s));
+        for (size_t e = 0; e < n; e++) {
+            const RowSet data{nullptr, base + (size_t)zs[e] * stripe_stride, ds};
+            const RowSet par{nullptr, q + e * slot_bytes, p > 1 ? qs : 0};
+            if (int err = encode_device(c, data, par, S, 0, 1, nullptr, s)) return err;
+        }
+        a.list = (const uint32_t *)g;
+        a.nlist = (int)n;
+        HIP_TRY(launch_syndrome_scan_list(c->bits, a, s));
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+        HIP_TRY(hipMemcpyAsync((void *)host, dev, scan_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        g_chk_passes++, g_chk_waits++;
+        conf.clear(), pick.clear(), good.clear();
+        const volatile uint64_t *first = (const volatile uint64_t *)host;
+        for (size_t e = 0; e < n; e++) {
+            // a corrupt survivor reaches the parity rows through the rebuilt
+            // rows too: no shortcut from the rows that differ, every entry is decoded
+            ChkCand cd;
+            cd.e = (uint32_t)e;
+            cd.pat = pat_of[c0 + e];
+            if (first[e] >= S) {
+                cnt[e] = 0;  // (the map said bad: cannot happen)
+                continue;
+            }
+            cd.pos = first[e];
+            pick.push_back(cd);
+        }
+        std::vector<uint32_t> wr;
+        while (true) {
+            if (!pick.empty()) {
+                const size_t np = pick.size();
+                if (int e = ring_acquire(c, 4 * kScrubPickDescDwords * np, slot, h, g)) return e;
+                uint32_t *d = (uint32_t *)h;
+                for (size_t i = 0; i < np; i++, d += kScrubPickDescDwords)
+                    d[0] = zs[pick[i].e], d[1] = pick[i].e, d[2] = (uint32_t)pick[i].pos, d[3] = (uint32_t)(pick[i].pos >> 32);
+                HIP_TRY(hipMemcpyAsync(g, h, 4 * kScrubPickDescDwords * np, hipMemcpyHostToDevice, s));
+                b.list = (const uint32_t *)g;
+                b.nlist = (int)np;
+                HIP_TRY(launch_syndrome_pick_rows(c->bits, b, s));
+                HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+                c->ring_used[slot] = true;
+                HIP_TRY(hipMemcpyAsync((void *)(shost + o_sym), sdev + o_sym, 4 * np * p, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                g_chk_waits++;
+                const volatile uint32_t *hs = (const volatile uint32_t *)(shost + o_sym);
+                for (size_t i = 0; i < np; i++) {
+                    ChkCand cd = pick[i];
+                    const ChkPattern &pt = pats[cd.pat];
+                    for (int r = 0; r < p; r++) sym[r] = hs[i * p + r];
+                    int32_t found[kLocateSetMax];
+                    const int nf = locate_set_decode_present(*c->F, lp, pt.present.data(), sym.data(), pt.cap, found);
+                    if (nf <= 0) continue;  // unlocated
+                    int merged[2 * kLocateSetMax];
+                    const int nm = (int)(std::set_union(cd.J, cd.J + cd.nj, found, found + nf, merged) - merged);
+                    if (nm == cd.nj || nm > pt.cap) continue;  // a decode must add a survivor, within cap_z
+                    std::copy(merged, merged + nm, cd.J);
+                    cd.nj = nm;
+                    conf.push_back(cd);
+                }
+                pick.clear();
+            }
+            if (conf.empty()) break;
+            std::stable_sort(conf.begin(), conf.end(), by_set);
+            const size_t nc = conf.size();
+            HIP_TRY(hipMemsetAsync(sdev, 0, o_fail, s));
+            HIP_TRY(hipMemsetAsync(sdev + o_fail, 0xff, 8 * nc, s));
+            if (int e = launch(conf, zs, nullptr)) return e;
+            HIP_TRY(hipMemcpyAsync((void *)shost, sdev, o_fail + 8 * nc, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            g_chk_rounds++, g_chk_waits++;
+            const volatile int *bad = (const volatile int *)shost;
+            const volatile int *used = (const volatile int *)(shost + o_used);
+            const volatile uint64_t *fail = (const volatile uint64_t *)(shost + o_fail);
+            for (size_t i = 0; i < nc; i++) {
+                ChkCand cd = conf[i];
+                if (!bad[i]) {
+                    // located: the survivors that really change, and their write bits for the fix
+                    uint32_t w = 0;
+                    int c1 = 0;
+                    int32_t *out = sh + (size_t)cd.e * stride;
+                    for (int x = 0; x < cd.nj; x++) {
+                        if (!used[8 * i + x]) continue;
+                        w |= 1u << x;
+                        out[c1++] = cd.J[x];
+                    }
+                    if (!c1) continue;  // (the scan said bad: cannot happen)
+                    cnt[cd.e] = c1;
+                    good.push_back(cd);
+                    wr.push_back(w);
+                } else if (cd.nj < pats[cd.pat].cap && fail[i] < S) {
+                    cd.pos = fail[i];
+                    pick.push_back(cd);
+                }
+            }
+            conf.clear();
+            if (pick.empty()) break;
+        }
+        if (repair && !good.empty()) {
+            std::vector<size_t> idx(good.size());
+            for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
+            std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return by_set(good[x], good[y]); });
+            std::vector<ChkCand> gs;
+            std::vector<uint32_t> ws;
+            for (size_t i : idx) gs.push_back(good[i]), ws.push_back(wr[i]);
+            if (int e = launch(gs, zs, ws.data())) return e;
+        }
+    }
+    return RS_OK;
+}
+
+// rs_reconstruct_checked_dev_batch_patterns after its argument checks: the
+// patterns reconstruct and the per-stripe map, unchanged; then the stripes the
+// map calls bad, those with nothing missing through the set locate, the others
+// through locate_present_list_device.  Complete on return.
+int reconstruct_checked_call(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
+                             const uint8_t *present, size_t npat, const uint32_t *pattern_of, size_t S, int max_shards,
+                             int repair, int32_t *count, int32_t *shards, int *nbad, void *stream) {
+    const int total = c->total, k = c->k, p = c->p;
+    const int stride = std::max(max_shards, 1);
+    std::fill(count, count + nstripes, 0);
+    std::fill(shards, shards + nstripes * (size_t)stride, -1);
+    if (!nstripes) return RS_OK;
+    if (int e = reconstruct_patterns_call(c, base, row_stride, stripe_stride, nstripes, present, npat, pattern_of, S, true,
+                                          stream))
+        return e;
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    if (int e = scratch_acquire(c, s)) return e;
+    std::vector<uint32_t> zfull, zpres;  // bad stripes with nothing missing / with missing rows and cap_z >= 1
+    std::vector<int> pat_of;             // the ChkPattern of each entry of zpres
+    std::vector<ChkPattern> pats;
+    std::vector<int> chk_of(npat, -1);
+    std::map<std::vector<uint8_t>, int> seen;
+    std::vector<int32_t> cn, sh;
+    int bad = 0;
+    auto body = [&]() -> int {
+        const int *flags = nullptr;
+        if (int e = verify_map_device(c, base, row_stride, stripe_stride, (int)nstripes, S, s, &flags)) return e;
+        for (size_t z = 0; z < nstripes; z++) {
+            if (((const volatile int *)flags)[z] == 0) continue;
+            bad++;
+            count[z] = RS_SCRUB_UNLOCATED;
+            const size_t qn = pattern_of[z];
+            const uint8_t *pr = present + qn * total;
+            int ne = 0;
+            for (int i = 0; i < total; i++) ne += pr[i] ? 0 : 1;
+            if (!ne) {
+                if (max_shards >= 1) zfull.push_back((uint32_t)z);
+                continue;
+            }
+            const int capz = std::min(max_shards, (p - ne) / 2);
+            if (capz < 1) continue;
+            if (!c->locate_present_built) {
+                make_locate_present(*c->F, k, p, c->locate_present);
+                c->locate_present_built = true;
+            }
+            if (!c->locate_present.shift) continue;  // no shift point: nothing is located
+            if (chk_of[qn] < 0) {
+                std::vector<uint8_t> f(total);
+                for (int i = 0; i < total; i++) f[i] = pr[i] != 0;
+                auto ins = seen.emplace(f, (int)pats.size());
+                if (ins.second) {
+                    if (int e = build_decode_plan(c)) return e;
+                    if (!c->dec_ok) return RS_ERR_PANIC;
+                    pats.emplace_back();
+                    ChkPattern &pt = pats.back();
+                    pt.present = std::move(f);
+                    pt.cap = capz;
+                    auto hit = c->chk_cache.find(pt.present);
+                    if (hit == c->chk_cache.end()) {
+                        auto pp = std::make_shared<PresentPattern>();
+                        if (!make_present_pattern(*c->F, k, p, pt.present.data(), c->enc_ifft_logs, c->enc_fft_logs,
+                                                  c->dec_ifft_logs, c->dec_fft_logs, *pp))
+                            return RS_ERR_PANIC;
+                        const size_t bytes = total + (size_t)ne * 4 * ((size_t)total + p);
+                        if (c->chk_cache_bytes + bytes > kChkCacheBytes) c->chk_cache.clear(), c->chk_cache_bytes = 0;
+                        c->chk_cache_bytes += bytes;
+                        hit = c->chk_cache.emplace(pt.present, std::move(pp)).first;
+                    }
+                    pt.ppp = hit->second;
+                }
+                chk_of[qn] = ins.first->second;
+            }
+            zpres.push_back((uint32_t)z);
+            pat_of.push_back(chk_of[qn]);
+        }
+        if (!zfull.empty()) {
+            cn.assign(zfull.size(), 0), sh.assign(zfull.size() * (size_t)max_shards, -1);
+            if (int e = locate_set_device(c, base, row_stride, stripe_stride, zfull.data(), zfull.size(), S, max_shards, repair,
+                                          s, cn.data(), sh.data()))
+                return e;
+            for (size_t t = 0; t < zfull.size(); t++) {
+                // (the map said bad; a clean scan cannot follow on unchanged rows)
+                count[zfull[t]] = cn[t] == 0 ? RS_SCRUB_UNLOCATED : cn[t];
+                if (cn[t] > 0)
+                    std::copy(sh.begin() + t * max_shards, sh.begin() + (t + 1) * max_shards,
+                              shards + (size_t)zfull[t] * stride);
+            }
+        }
+        if (!zpres.empty()) {
+            cn.assign(zpres.size(), 0), sh.assign(zpres.size() * (size_t)stride, -1);
+            if (int e = locate_present_list_device(c, base, row_stride, stripe_stride, zpres.data(), pat_of.data(), zpres.size(),
+                                                   pats, S, stride, repair != 0, s, cn.data(), sh.data()))
+                return e;
+            for (size_t t = 0; t < zpres.size(); t++) {
+                count[zpres[t]] = cn[t] == 0 ? RS_SCRUB_UNLOCATED : cn[t];
+                if (cn[t] > 0)
+                    std::copy(sh.begin() + t * stride, sh.begin() + (t + 1) * stride, shards + (size_t)zpres[t] * stride);
+            }
+        }
+        return RS_OK;
+    };
+    const int err = body();
+    if (int e = scratch_release(c, s)) return err ? err : e;
+    if (err) return err;
+    HIP_TRY(hipStreamSynchronize(s));  // the queued repairs
+    if (nbad) *nbad = bad;
+    return RS_OK;
+}
+
 // ---- A (present, required) pair per stripe (rs_reconstruct_rows_dev_batch_patterns)
 static_assert(sizeof(RowsSetDesc) == sizeof(RowsPattern) && offsetof(RowsSetDesc, tw) == offsetof(RowsPattern, tw) &&
                   offsetof(RowsSetDesc, src_idx) == offsetof(RowsPattern, src_idx) &&
@@ -3905,6 +4351,104 @@ int rs_reconstruct_dev_batch_patterns(rs_codec *c, uint8_t *base, size_t row_str
     if (npatterns == 0 || npatterns > 65536) return RS_ERR_INVALID_ARG;
     return reconstruct_patterns_call(c, base, row_stride, stripe_stride, nstripes, present, npatterns, pattern_of, S,
                                      recover_all != 0, stream);
+}
+
+int rs_reconstruct_checked_dev_batch_patterns(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride,
+                                              size_t nstripes, const uint8_t *present, size_t npatterns,
+                                              const uint32_t *pattern_of, size_t S, int max_shards, int repair,
+                                              int32_t *count, int32_t *shards, int *nbad, void *stream) {
+    if (!c || !base || !present || !pattern_of || !count || !shards || nstripes > (size_t)INT32_MAX)
+        return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    if (npatterns == 0 || npatterns > 65536) return RS_ERR_INVALID_ARG;
+    if (nbad) *nbad = 0;
+    {
+        // reconstruct_patterns_call's table, in its order (recover_all = 1)
+        const int total = c->total;
+        for (size_t z = 0; z < nstripes; z++)
+            if (pattern_of[z] >= npatterns) return RS_ERR_INVALID_ARG;
+        if (S == 0) return RS_ERR_SHARD_NO_DATA;
+        bool too_few = false;
+        for (size_t q = 0; q < npatterns; q++) {
+            int np = 0;
+            for (int i = 0; i < total; i++) np += present[q * total + i] ? 1 : 0;
+            if (np == 0) return RS_ERR_SHARD_NO_DATA;
+            too_few = too_few || np < c->k;
+        }
+        if (too_few) return RS_ERR_TOO_FEW_SHARDS;
+        if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
+        if (row_stride < S || (nstripes > 1 && stripe_stride < (size_t)total * row_stride)) return RS_ERR_INVALID_ARG;
+        if ((long)c->m + c->k > (long)c->F->order) return RS_ERR_PANIC;
+    }
+    if (max_shards < 0 || max_shards > RS_LOCATE_SET_MAX) return RS_ERR_INVALID_ARG;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    return reconstruct_checked_call(c, base, row_stride, stripe_stride, nstripes, present, npatterns, pattern_of, S,
+                                    max_shards, repair, count, shards, nbad, stream);
+}
+
+int rs_debug_checked_stats(uint64_t *out, int reset) {
+    if (!out) return RS_ERR_INVALID_ARG;
+    out[0] = g_chk_passes.load(), out[1] = g_chk_rounds.load(), out[2] = g_chk_waits.load();
+    if (reset) g_chk_passes = 0, g_chk_rounds = 0, g_chk_waits = 0;
+    return RS_OK;
+}
+
+int rs_debug_check_column(int bits, int k, int p, const uint8_t *present, int shard, uint32_t *out) {
+    if ((bits != 8 && bits != 16) || !present || !out || k <= 0 || p <= 0 || shard < 0 || shard >= k + p)
+        return RS_ERR_INVALID_ARG;
+    if (!present[shard]) return RS_ERR_INVALID_ARG;
+    // the last pattern's coefficient rows are kept: a test asks many columns of one pattern
+    static std::mutex mu;
+    static int kb = 0, kk = 0, kp = 0;
+    static std::vector<uint8_t> kpr;
+    static bool ok = false;
+    static std::vector<uint32_t> ei, ef, di, df;
+    static PresentPattern pp;
+    std::lock_guard<std::mutex> lk(mu);
+    const std::vector<uint8_t> pr(present, present + k + p);
+    if (kb != bits || kk != k || kp != p || kpr != pr) {
+        int nchunks = 0;
+        ok = encode_schedule(field(bits), k, p, ei, ef, nchunks) && decode_schedule(field(bits), k, p, di, df) &&
+             make_present_pattern(field(bits), k, p, present, ei, ef, di, df, pp);
+        kb = bits, kk = k, kp = p, kpr = pr;
+    }
+    if (!ok) return RS_ERR_PANIC;
+    check_column(field(bits), k, p, pp, shard, ei, ef, out);
+    return RS_OK;
+}
+
+int rs_debug_locate_set_present(int bits, int k, int p, const uint8_t *present, const uint32_t *e, int cap, int *count,
+                                int32_t *shards) {
+    if ((bits != 8 && bits != 16) || !present || !e || !count || !shards || k <= 0 || p <= 0 || cap < 0 ||
+        cap > RS_LOCATE_SET_MAX)
+        return RS_ERR_INVALID_ARG;
+    *count = -1;
+    std::fill(shards, shards + std::max(cap, 1), -1);
+    bool missing = false;
+    for (int i = 0; i < k + p; i++) missing |= !present[i];
+    if (!missing) {
+        // nothing missing: the set locate's answer (cap 0: clean or not)
+        if (cap >= 1) return rs_debug_locate_set(bits, k, p, e, cap, count, shards);
+        bool any = false;
+        for (int i = 0; i < p; i++) any |= e[i] != 0;
+        *count = any ? -1 : 0;
+        return RS_OK;
+    }
+    static std::mutex mu;
+    static int kb = 0, kk = 0, kp = 0;
+    static bool ok = false;
+    static LocatePresent lp;
+    std::lock_guard<std::mutex> lk(mu);
+    if (kb != bits || kk != k || kp != p) {
+        ok = make_locate_present(field(bits), k, p, lp);
+        kb = bits, kk = k, kp = p;
+    }
+    if (!ok) return RS_ERR_PANIC;
+    int32_t found[kLocateSetMax + 1];
+    const int n = locate_set_decode_present(field(bits), lp, present, e, cap, found);
+    *count = n;
+    for (int i = 0; i < n; i++) shards[i] = found[i];
+    return RS_OK;
 }
 
 int rs_reconstruct_rows_dev_batch_patterns(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride,

@@ -852,4 +852,185 @@ bool invert_matrix(const Field &F, int s, const uint32_t *A, uint32_t *inv) {
     return true;
 }
 
+bool make_locate_present(const Field &F, int k, int p, LocatePresent &lp) {
+    lp = LocatePresent{};
+    if (k <= 0 || p <= 0) return false;
+    std::vector<uint32_t> il, fl;
+    int nchunks = 0;
+    if (!encode_schedule(F, k, p, il, fl, nchunks)) return false;
+    const int m = ceil_pow2(p);
+    lp.k = k, lp.p = p, lp.m = m;
+    if ((uint64_t)m + (uint64_t)k > F.order) return true;
+    lp.shift = p < m || (uint32_t)(m + k) < F.order;
+    if (!lp.shift) return true;
+    lp.a = p < m ? (uint32_t)p : (uint32_t)(m + k);
+    lp.w.assign((size_t)p * p, 0);
+    for (int i = 0; i < p; i++) {
+        uint32_t lu = 0;  // log u_i, as make_locate_set
+        for (int y = p; y < m; y++) lu = F.add_mod(lu, F.log[(uint32_t)i ^ (uint32_t)y]);
+        uint32_t v = F.exp[lu];
+        const uint32_t X = (uint32_t)i ^ lp.a;
+        for (int l = 0; l < p; l++, v = gmul(F, v, X)) lp.w[(size_t)l * p + i] = v;
+    }
+    lp.X.resize((size_t)k + p);
+    for (int j = 0; j < k; j++) lp.X[j] = (uint32_t)(m + j) ^ lp.a;
+    for (int i = 0; i < p; i++) lp.X[(size_t)k + i] = (uint32_t)i ^ lp.a;
+    return true;
+}
+
+int locate_set_decode_present(const Field &F, const LocatePresent &lp, const uint8_t *present, const uint32_t *e, int cap,
+                              int32_t *shards) {
+    const int p = lp.p, total = lp.k + lp.p;
+    for (int i = 0; i < cap; i++) shards[i] = -1;
+    bool any = false;
+    for (int i = 0; i < p; i++) any |= e[i] != 0;
+    if (!any) return 0;
+    int ne = 0;
+    for (int i = 0; i < total; i++) ne += present[i] ? 0 : 1;
+    if (ne > p || !lp.shift) return -1;
+    const int capz = std::min(std::min(cap, kLocateSetMax), (p - ne) / 2);
+    if (capz < 1) return -1;
+    // All p - e modified syndromes, not only the first 2 * cap_z: the shortest
+    // recurrence through all of them is longer than cap_z whenever more than
+    // cap_z survivors are wrong and the distance still tells (2 (cap_z + 1) <= p - e).
+    const int N = p - ne, ns = p;
+    std::vector<uint32_t> S((size_t)ns, 0), gam((size_t)ne + 1, 0), M((size_t)N, 0);
+    for (int i = 0; i < p; i++) {
+        if (!e[i] || e[i] >= F.order) continue;
+        for (int l = 0; l < ns; l++) S[l] ^= gmul(F, lp.w[(size_t)l * p + i], e[i]);
+    }
+    // Gamma(z) = prod over the missing rows of (1 ^ X z)
+    gam[0] = 1;
+    for (int i = 0, d = 0; i < total; i++) {
+        if (present[i]) continue;
+        d++;
+        for (int j = d; j >= 1; j--) gam[j] ^= gmul(F, gam[j - 1], lp.X[i]);
+    }
+    for (int l = 0; l < N; l++)
+        for (int j = 0; j <= ne; j++) M[l] ^= gmul(F, gam[j], S[l + ne - j]);
+    // Berlekamp-Massey on the modified syndromes, as locate_set_decode
+    std::vector<uint32_t> C((size_t)N + 2, 0), B((size_t)N + 2, 0), T;
+    C[0] = B[0] = 1;
+    int L = 0, sh = 1;
+    uint32_t b = 1;
+    for (int n = 0; n < N; n++) {
+        uint32_t d = M[n];
+        for (int i = 1; i <= L; i++) d ^= gmul(F, C[i], M[n - i]);
+        if (!d) {
+            sh++;
+            continue;
+        }
+        const uint32_t f = gmul(F, d, ginv(F, b));
+        T = C;
+        for (int i = 0; i + sh < N + 2; i++) C[i + sh] ^= gmul(F, f, B[i]);
+        if (2 * L <= n) {
+            L = n + 1 - L;
+            B = T;
+            b = d;
+            sh = 1;
+        } else {
+            sh++;
+        }
+    }
+    if (L < 1 || L > capz || !C[L]) return -1;
+    // the roots of sigma(X) = sum_i C[i] * X^(L - i) among the survivors' locators
+    int n = 0;
+    for (int x = 0; x < total; x++) {
+        if (!present[x]) continue;
+        const uint32_t X = lp.X[x];
+        uint32_t v = 1;
+        for (int i = 1; i <= L; i++) v = gmul(F, v, X) ^ C[i];
+        if (v) continue;
+        if (n == L) return -1;
+        shards[n++] = (int32_t)x;
+    }
+    if (n != L) {
+        for (int i = 0; i < cap; i++) shards[i] = -1;
+        return -1;
+    }
+    return n;
+}
+
+bool make_present_pattern(const Field &F, int k, int p, const uint8_t *present, const std::vector<uint32_t> &enc_ifft,
+                          const std::vector<uint32_t> &enc_fft, const std::vector<uint32_t> &dec_ifft,
+                          const std::vector<uint32_t> &dec_fft, PresentPattern &pp) {
+    pp = PresentPattern{};
+    const int total = k + p;
+    std::vector<uint8_t> erased((size_t)total);
+    for (int i = 0; i < total; i++) {
+        erased[i] = present[i] ? 0 : 1;
+        if (erased[i]) pp.E.push_back(i);
+    }
+    if ((int)pp.E.size() > p) return false;
+    std::vector<uint32_t> el;
+    if (!error_locators(F, k, p, erased.data(), el)) return false;
+    pp.co.resize(pp.E.size());
+    pp.GE.resize(pp.E.size());
+    for (size_t x = 0; x < pp.E.size(); x++) {
+        pp.co[x].assign((size_t)total, 0);
+        decode_coefficients_from(F, k, p, erased.data(), el, dec_ifft, dec_fft, pp.E[x], pp.co[x].data());
+        if (pp.E[x] < k) generator_column_from(F, k, p, pp.E[x], enc_ifft, enc_fft, pp.GE[x]);
+    }
+    return true;
+}
+
+void check_column(const Field &F, int k, int p, const PresentPattern &pp, int t, const std::vector<uint32_t> &enc_ifft,
+                  const std::vector<uint32_t> &enc_fft, uint32_t *H) {
+    std::fill(H, H + p, 0u);
+    if (t < k) {
+        std::vector<uint32_t> g;
+        generator_column_from(F, k, p, t, enc_ifft, enc_fft, g);
+        std::copy(g.begin(), g.end(), H);
+    } else {
+        H[t - k] = 1;
+    }
+    for (size_t x = 0; x < pp.E.size(); x++) {
+        const uint32_t c = pp.co[x][t];
+        if (!c) continue;
+        if (pp.E[x] >= k) {
+            H[pp.E[x] - k] ^= c;
+        } else {
+            for (int i = 0; i < p; i++) H[i] ^= gmul(F, pp.GE[x][i], c);
+        }
+    }
+}
+
+void check_row_order(int k, int p, const uint8_t *present, const int *T, int s, int *order) {
+    int no = 0;
+    for (int pass = 0; pass < 2; pass++)
+        for (int r = 0; r < p; r++) {
+            const bool plain = present[k + r] && !std::binary_search(T, T + s, k + r);
+            if (plain == (pass == 0)) order[no++] = r;
+        }
+}
+
+bool pick_check_rows(const Field &F, int p, int s, const uint32_t *const *cols, const int *order, int *R, uint32_t *inv) {
+    if (s < 1 || s > kLocateSetMax) return false;
+    // basis[q]: an accepted row reduced by the ones before it, with its pivot column
+    uint32_t basis[kLocateSetMax][kLocateSetMax];
+    int piv[kLocateSetMax], nr = 0;
+    for (int o = 0; o < p && nr < s; o++) {
+        const int r = order[o];
+        uint32_t v[kLocateSetMax];
+        for (int j = 0; j < s; j++) v[j] = cols[j][r];
+        for (int q = 0; q < nr; q++) {
+            const uint32_t f = v[piv[q]];
+            if (!f) continue;
+            for (int j = 0; j < s; j++) v[j] ^= gmul(F, f, basis[q][j]);
+        }
+        int pc = 0;
+        while (pc < s && !v[pc]) pc++;
+        if (pc == s) continue;
+        const uint32_t iv = ginv(F, v[pc]);
+        for (int j = 0; j < s; j++) basis[nr][j] = gmul(F, v[j], iv);
+        piv[nr] = pc;
+        R[nr++] = r;
+    }
+    if (nr < s) return false;
+    uint32_t A[kLocateSetMax * kLocateSetMax];
+    for (int r = 0; r < s; r++)
+        for (int j = 0; j < s; j++) A[r * s + j] = cols[j][R[r]];
+    return invert_matrix(F, s, A, inv);
+}
+
 }  // namespace rs

@@ -296,4 +296,65 @@ int locate_set_decode(const Field &F, const LocateSet &ls, const uint32_t *e, in
 // inv = A^-1 for the s x s matrix A (row-major, s <= kLocateSetMax); false when singular.
 bool invert_matrix(const Field &F, int s, const uint32_t *A, uint32_t *inv);
 
+// ---- Checked rebuild: which corrupt survivors explain the syndrome of a
+// stripe whose missing rows were filled from all survivors
+// (rs_reconstruct_checked_dev_batch_patterns).  With E the
+// missing rows and T the corrupt survivors (differences D_t), the filled
+// stripe is a codeword plus d: d_t = D_t on T, d_x = sum_t c[x][t] * D_t on E
+// (c: decode_coefficients of the pattern), zero elsewhere.  Its syndromes are
+// the power sums of d over T and E; E is known, so the erasure locator
+// Gamma(z) = prod_{x in E} (1 ^ X_x z) folds them into p - e modified
+// syndromes  T_l = sum_j Gamma_j * S_{l + e - j} = sum_{t in T} Y_t * X_t^l.
+struct LocatePresent {
+    int k = 0, p = 0, m = 0;
+    bool shift = false;       // false: no shift point (or m + k past the field), nothing is located
+    uint32_t a = 0;           // the shift, as LocateSet::a
+    std::vector<uint32_t> w;  // p rows of p weights: w[l * p + i] = u_i * (i ^ a)^l
+    std::vector<uint32_t> X;  // k + p locators by shard number (data shards first)
+};
+// False where the encode's schedule does not exist.
+bool make_locate_present(const Field &F, int k, int p, LocatePresent &lp);
+// The corrupt survivors at one symbol, from the p syndrome symbols e of the
+// filled stripe: with e missing rows (present[i] == 0), Berlekamp-Massey on
+// all p - e modified syndromes, a recurrence no longer than cap_z = min(cap,
+// kLocateSetMax, (p - e) / 2), then the locator's roots among the survivors'
+// locators; all of them must be found there.  (All the syndromes, so that
+// cap_z + 1 corrupt survivors with 2 (cap_z + 1) <= p - e are never mistaken
+// for fewer.)  Returns their number with the shard numbers
+// ascending in shards[0..cap) (padded with -1), 0 when e is all zero, -1
+// when nothing of degree <= cap_z fits, cap_z is 0 or there is no shift point.
+int locate_set_decode_present(const Field &F, const LocatePresent &lp, const uint8_t *present, const uint32_t *e, int cap,
+                              int32_t *shards);
+
+// What an erasure pattern contributes to the check matrix: the missing rows,
+// the decode coefficients of each over all shards (0 at the missing ones) and
+// the generator column of each missing data row.
+struct PresentPattern {
+    std::vector<int> E;                     // missing shards, ascending
+    std::vector<std::vector<uint32_t>> co;  // co[x][t] = c[E[x]][t], k + p entries
+    std::vector<std::vector<uint32_t>> GE;  // G[.][E[x]] (p entries) for E[x] < k, else empty
+};
+// From the logs encode_schedule and decode_schedule returned for (k, p).  False
+// where error_locators refuses the geometry or fewer than k rows are present.
+bool make_present_pattern(const Field &F, int k, int p, const uint8_t *present, const std::vector<uint32_t> &enc_ifft,
+                          const std::vector<uint32_t> &enc_fft, const std::vector<uint32_t> &dec_ifft,
+                          const std::vector<uint32_t> &dec_fft, PresentPattern &pp);
+// Column t (a survivor) of the check matrix: a difference D in survivor t
+// changes syndrome row i of the filled stripe by H[i] * D,
+//   H[i] = [t == k + i] ^ [t < k] G[i][t] ^ [k + i in E] c[k + i][t] ^ sum_{x in E, x < k} G[i][x] * c[x][t].
+void check_column(const Field &F, int k, int p, const PresentPattern &pp, int t, const std::vector<uint32_t> &enc_ifft,
+                  const std::vector<uint32_t> &enc_fft, uint32_t *H);
+// s rows R of the p x s matrix whose column j is cols[j] (p entries each) with
+// H[R][.] non-singular, and inv = its inverse (row-major).  Rows are tried in
+// the order `order` (p row numbers): the rows picked are the first that work.
+// False when the columns have rank below s.
+bool pick_check_rows(const Field &F, int p, int s, const uint32_t *const *cols, const int *order, int *R, uint32_t *inv);
+// The order the checked rebuild tries the rows in: first the rows of parity
+// shards that are present and outside T (ascending shards T[0..s)), which the
+// repair does not write, then the others.  A set of parity shards alone, with
+// only parity rows missing, has no non-zero row outside those it writes, so
+// the repair reads its rows R before it writes anything instead of relying on
+// R being disjoint from them.
+void check_row_order(int k, int p, const uint8_t *present, const int *T, int s, int *order);
+
 }  // namespace rs

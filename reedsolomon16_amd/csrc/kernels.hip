@@ -3103,6 +3103,73 @@ __global__ void __launch_bounds__(256, 2) k_syndrome_fix_set(ScrubSetArgs a) {
     }
 }
 
+// The confirmed candidate blockIdx.y of a checked rebuild: D as above, the
+// survivors T in place, then the stripe's e missing rows, kConfRows loads in
+// flight, each ^= sum_j c[x][T[j]] * D_j through masks prepared once.  D is
+// complete (every row of R loaded) before the first store and a lane owns its
+// unit in every row, so a row of R that is also written is read first.
+template <class F>
+__global__ void __launch_bounds__(256, 2) k_syndrome_fix_present(ScrubPresentArgs pa) {
+    typedef typename F::Vec V;
+    const ScrubSetArgs &a = pa.set;
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubSetDescDwords;
+    uint8_t *sb = a.base + (uint64_t)d[0] * a.stripe_stride;
+    const uint8_t *stored = sb + (uint64_t)a.k * a.row_stride;
+    const uint8_t *fresh = a.fresh + (uint64_t)d[1] * a.fresh_slot_stride;
+    const int s = (int)d[3];
+    const uint32_t wr = d[21];
+    UpdMasks<F> mk[kScrubSetMax];
+    {
+        V D[kScrubSetMax];
+        set_diffs<F>(a, d, stored, fresh, u, s, D);
+#pragma unroll
+        for (int j = 0; j < kScrubSetMax; j++) {
+            mk[j].prepare(D[j]);
+            if (j < s && (wr >> j & 1)) {
+                uint8_t *r = sb + (uint64_t)d[17 + j] * a.row_stride;
+                V x = F::load(r, u);
+                F::xor_into(x, D[j]);
+                F::store(r, u, x);
+            }
+        }
+    }
+    const int ne = (int)d[12];
+    cu32_t *rows = (cu32_t *)pa.rows + d[13];
+    const uint32_t *ftw = pa.fix_tw + (uint64_t)d[14] * F::TWD;
+    auto terms = [&](V &x, int q) {
+#pragma unroll
+        for (int j = 0; j < kScrubSetMax; j++) {
+            if (j < s) {
+                const Tab<F> tb = load_tab<F>(ftw + ((uint64_t)q * (uint64_t)s + j) * F::TWD);
+                mk[j].mul_add(x, tb.v);
+            }
+        }
+    };
+    int q = 0;
+    for (; q + kConfRows <= ne; q += kConfRows) {
+        V x[kConfRows];
+        uint8_t *r[kConfRows];
+#pragma unroll
+        for (int i = 0; i < kConfRows; i++) {
+            r[i] = sb + (uint64_t)rows[q + i] * a.row_stride;
+            x[i] = F::load(r[i], u);
+        }
+#pragma unroll
+        for (int i = 0; i < kConfRows; i++) {
+            terms(x[i], q + i);
+            F::store(r[i], u, x[i]);
+        }
+    }
+    for (; q < ne; q++) {
+        uint8_t *r = sb + (uint64_t)rows[q] * a.row_stride;
+        V x = F::load(r, u);
+        terms(x, q);
+        F::store(r, u, x);
+    }
+}
+
 bool scrub_set_ok(const ScrubSetArgs &a) {
     return a.p > 0 && a.k > 0 && a.nlist > 0 && a.nlist <= kScrubMaxList && a.S != 0 && a.S % 64 == 0 && a.base &&
            a.fresh && a.list && a.row_stride >= a.S && a.fresh_stride >= a.S;
@@ -3153,5 +3220,19 @@ hipError_t launch_syndrome_fix_set(int bits, const ScrubSetArgs &a, hipStream_t 
     RS_SCRUB_SET_LAUNCH(k_syndrome_fix_set);
 }
 #undef RS_SCRUB_SET_LAUNCH
+
+hipError_t launch_syndrome_fix_present(int bits, const ScrubPresentArgs &pa, hipStream_t s) {
+    const ScrubSetArgs &a = pa.set;
+    if (!scrub_set_ok(a) || !a.inv_tw || !pa.rows || !pa.fix_tw) return hipErrorInvalidValue;
+    const bool narrow = scrub_set_narrow(bits, a);
+    if (bits == 16) {
+        if (narrow) hipLaunchKernelGGL(k_syndrome_fix_present<F16<2>>, scrub_set_grid<F16<2>>(a), dim3(256), 0, s, pa);
+        else hipLaunchKernelGGL(k_syndrome_fix_present<F16<4>>, scrub_set_grid<F16<4>>(a), dim3(256), 0, s, pa);
+    } else {
+        if (narrow) hipLaunchKernelGGL(k_syndrome_fix_present<F8<2>>, scrub_set_grid<F8<2>>(a), dim3(256), 0, s, pa);
+        else hipLaunchKernelGGL(k_syndrome_fix_present<F8<4>>, scrub_set_grid<F8<4>>(a), dim3(256), 0, s, pa);
+    }
+    return hipGetLastError();
+}
 
 }  // namespace rs

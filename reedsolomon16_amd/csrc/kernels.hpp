@@ -433,4 +433,26 @@ hipError_t launch_syndrome_confirm_set(int bits, const ScrubSetArgs &a, hipStrea
 // lane owns its own unit.
 hipError_t launch_syndrome_fix_set(int bits, const ScrubSetArgs &a, hipStream_t s);
 
+// ---- The repair of a checked rebuild (rs_reconstruct_checked_dev_batch_patterns):
+// a confirmed set T of s corrupt survivors (data or parity shards) of a stripe
+// whose e missing rows were filled from all survivors.  The confirm is
+// k_syndrome_confirm_set with the check matrix's columns H[.][t] as its
+// column tables and no J_p; the fix below is its own kernel.  Descriptor
+// (kScrubSetDescDwords dwords): [0] stripe, [1] slot, [3] s, [8..11] the rows
+// R, [16] first A^-1 table, [17..20] the shards T (numbers in [0, k + p)),
+// [21] bit j set = write shard T[j], as ScrubSetArgs; [12] e, [13] the first
+// of the stripe's e missing shard numbers in `rows`, [14] the first of its
+// e x s tables in fix_tw: table (x, j) = multiply by c[rows[x]][T[j]] at
+// fix_tw + ([14] + x s + j) * tw_dwords.
+struct ScrubPresentArgs {
+    ScrubSetArgs set;        // base, strides, fresh rows, S, k, p, nlist, list, inv_tw
+    const uint32_t *rows;    // missing shard numbers
+    const uint32_t *fix_tw;  // make_twiddle images
+};
+// D = A^-1 * e_R per unit; shard T[j] ^= D_j in place, then missing row x ^=
+// sum_j c[x][T[j]] * D_j.  A lane loads its unit of the rows R before it writes
+// anything and owns that unit in every row, so a row of R may be written too.
+// Reads 2 s + s + e rows, writes s + e.
+hipError_t launch_syndrome_fix_present(int bits, const ScrubPresentArgs &a, hipStream_t s);
+
 }  // namespace rs

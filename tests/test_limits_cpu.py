@@ -128,3 +128,33 @@ def test_batch_calls_reject_row_stride_below_shard_size(bits, k, p):
         ok.value = 7
     pr = (C.c_uint8 * (k + p))(*([0] + [1] * (k + p - 1)))
     assert L.rs_reconstruct_dev_batch(c._h, base, S - 64, (k + p) * S, 2, pr, S, 1, None) == RS_ERR_INVALID_ARG
+
+
+# ---- the layouts of tests/test_gpu_limits.py
+from tests import limits_cases as lc  # noqa: E402
+
+
+def test_gpu_limit_cases_are_what_they_claim():
+    """tests/test_gpu_limits.py takes its shapes and layouts from
+    limits_cases.py: every layout must fit the one 6 GiB buffer, the far
+    geometries must be far, and each encode case must name the kernel its codec
+    takes (the bit-sliced one only while its row predicate holds)."""
+    assert lc.S_EDGE == S_EDGE
+    shapes = set(lc.REC_SHAPES + lc.ROWS_SHAPES + lc.UPDATE_SHAPES + lc.SCRUB_SHAPES + [lc.CHECKED_SHAPE] +
+                 [c[:3] for c in lc.FAR_STRIPE_ENCODES])
+    assert {c[:3] for c in lc.REC_CASES} == set(lc.REC_SHAPES)
+    for bits, k, p in shapes:
+        n = k + p
+        base, rstride, sstride = lc.geometry("far_rows", n)
+        assert rstride % 64 == 0 and base + (n - 1) * rstride + 4 * lc.MIB + S_EDGE + lc.GUARD <= lc.BUF_BYTES
+        assert (n - 1) * rstride + S_EDGE >= 1 << 32  # the stripe's rows span 4 GiB
+        # and so do its data rows alone, wherever k of k + p rows in 6 GiB can
+        assert (k - 1) * rstride + S_EDGE >= 1 << 32 or (k - 1) * lc.BUF_BYTES < (n - 1) << 32, (bits, k, p)
+        base, rstride, sstride = lc.geometry("far_stripes", n)
+        assert rstride == lc.NEAR_ROW and sstride >= 1 << 32
+        assert base + sstride + 16 * lc.MIB + n * rstride + lc.GUARD <= lc.BUF_BYTES
+    for bits, k, p, path in lc.FAR_STRIPE_ENCODES + lc.GRID_ENCODES:
+        assert rs.ReedSolomon(k, p, bits).encode_path == path, (bits, k, p)
+    assert rs.lib().rs_debug_encode_bs_fits(128, 32, lc.NEAR_ROW, S_EDGE) == 1
+    assert [c[3].split("-")[0].rstrip("168") for c in lc.GRID_ENCODES] == ["reg", "split", "lds"]  # the unsliced launchers
+    assert lc.GRID_STRIPES > 65_535 and (1 << 32) + lc.GUARD + lc.GRID_STRIPES * 37 * lc.GRID_S + lc.GUARD <= lc.BUF_BYTES

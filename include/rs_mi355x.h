@@ -402,6 +402,81 @@ int rs_reconstruct_rows_dev_batch_patterns(rs_codec *codec, uint8_t *base, size_
                                            const uint8_t *required /* npatterns x (k+p), or NULL */,
                                            size_t npatterns, const uint32_t *pattern_of /* nstripes, host */,
                                            size_t shard_size, void *stream);
+/* The checked degraded read: the call above, which also verifies the rows it
+ * reads.  A stripe with s rows marked present has s - k symbols of redundancy
+ * among them; c_z = min(checks, s - k) check equations over exactly those rows
+ *  are evaluated in the pass that rebuilds the wanted rows, and
+ * verdict[z] (a HOST array of nstripes entries) says what they gave.
+ * Writes: exactly those of rs_reconstruct_rows_dev_batch_patterns for the same
+ * arguments, bit for bit, WHATEVER THE VERDICT: the rows of a RS_ROWS_CHECK_BAD
+ * stripe hold what the unchecked call writes, and what to do with them is the
+ * caller's decision (rs_reconstruct_checked_dev_batch_patterns names and
+ * repairs the corrupt survivor of such a stripe).  Rows not marked present are
+ * never read: a caller who marks only k + 2 rows present reads k + 2 rows and
+ * gets two checks.  A stripe with nothing to rebuild is still checked, and
+ * still not written.
+ * Guarantee, per stripe: the verdict is never BAD when the rows marked present
+ * are consistent (rows of one codeword); it is always BAD when, at some symbol
+ * position, between 1 and c_z of them are wrong.  Where more than c_z rows are
+ * wrong at every damaged position the stripe is missed only if all c_z check
+ * symbols vanish at each of them: for random differences 2^(-bits * c_z) per
+ * position.  RS_ROWS_CHECKS_MAX is 2 for the kernel's instantiation count; a
+ * third check would add little to that.  c_z == 0 (exactly k rows marked
+ * present, or checks == 0): RS_ROWS_CHECK_NONE.  GF(2^8) 128+128 is covered
+ * (the equations need no shift point).
+ * Tiers, per stripe, mixed within a call: where the unchecked call takes its
+ * direct tier and t <= 6 (so t + c_z <= 8, that kernel's accumulators), one
+ * fused launch per (t, c_z) group of the streaming kernel with c_z more
+ * accumulators; everywhere else (t above either threshold, n > 2048, t == 0) the unchecked call's route rebuilds the rows
+ * and one check-only launch per c_z reads the present rows of those stripes.
+ * Tables per stripe range in a device blob cached per codec (4 sets, keyed by
+ * checks and the pairs), from the exact locators of each pattern (the
+ * reference-keyed GF(2^8) inversion cache is neither read nor stored).
+ * Stream: the launches are stream-ordered; the call then waits ONCE on the
+ * host for that stream, reads the flags back and fills verdict and *nbad (the
+ * number of BAD stripes; may be NULL).  checks == 0: NONE everywhere and
+ * otherwise the unchecked call (no wait with a caller stream).
+ * Errors, all decided before any device call: those of
+ * rs_reconstruct_rows_dev_batch_patterns in its order, with a NULL verdict
+ * among the NULL checks; then checks outside [0, RS_ROWS_CHECKS_MAX]:
+ * RS_ERR_INVALID_ARG.
+ * Measured on one MI355X, us per stripe (profiles/rows_checked_c4.txt,
+ * DESIGN.md 4.19; a pass over the slab to a device synchronise, five
+ * alternating passes, medians; the slabs of the call above, one device lost,
+ * the lost row wanted): checks 0 / 1 / 2 on a clean slab / the unchecked call /
+ * the unchecked call with 2 / 3 rows wanted / the checked rebuild without
+ * repair.  128+32 x 1 MiB, 256 stripes: 29.3 / 30.9 / 39.7 / 29.0 / 30.9 /
+ * 39.3 / 129.0; 1024+256 x 256 KiB, 8 stripes: 85.5 / 162.2 / 224.8 / 83.8 /
+ * 160.7 / 222.0 / 663.8.  One check costs what a second wanted row costs.
+ * The second is dearer because the streaming kernel's step from two to three
+ * accumulators is (its own 30.9 -> 39.3), and two checks sit 0.4 us (0.9 %)
+ * at 128+32 and 2.9 us (1.3 %) at 1024+256 ABOVE the unchecked call with
+ * three wanted rows, which reads two present rows fewer (1.3 % at 128+32) and
+ * has no flag clear, read-back and host wait (12-24 us per call).
+ * One and 256 bad stripes of 256: 31.9 / 39.8 and 30.3 / 39.5 (checks 1 / 2).
+ * Check-only on the complete slab: 27.1 / 30.8 and 93.4 / 171.9.  The
+ * unchecked call's C entry point, this build against the parent commit's
+ * library in the same passes: 29.07 against 29.10, and 82.6 against 82.2
+ * (overlapping ranges).  Not measured: GF(2^8) codecs, kernel time alone
+ * under a trace, set building, more than one wanted row per stripe. */
+#define RS_ROWS_CHECKS_MAX 2
+#define RS_ROWS_CHECK_OK 0   /* every check of the stripe is zero at every symbol */
+#define RS_ROWS_CHECK_BAD 1  /* the rows marked present are not consistent */
+#define RS_ROWS_CHECK_NONE 2 /* c_z == 0: nothing was checked */
+int rs_reconstruct_rows_checked_dev_batch_patterns(rs_codec *codec, uint8_t *base, size_t row_stride,
+                                                   size_t stripe_stride, size_t nstripes,
+                                                   const uint8_t *present /* npatterns x (k+p) */,
+                                                   const uint8_t *required /* npatterns x (k+p), or NULL */,
+                                                   size_t npatterns, const uint32_t *pattern_of /* nstripes, host */,
+                                                   size_t shard_size, int checks /* 0 .. RS_ROWS_CHECKS_MAX */,
+                                                   int32_t *verdict /* nstripes, host */, int *nbad /* may be NULL */,
+                                                   void *stream);
+/* Host-only diagnostic: row l of the check weights of `present` (k+p entries,
+ * 0 at the shards not present): sum over the present shards t of out[t] *
+ * shard t is zero at every symbol of a consistent stripe.  l in [0, (number
+ * present) - k), else RS_ERR_INVALID_ARG. */
+int rs_debug_check_weights(int field_bits, int data_shards, int parity_shards, const uint8_t *present /* k+p */,
+                           int l, uint32_t *out /* k+p */);
 /* Host memory, through the host pipeline of rs_reconstruct (pinned, pageable
  * and zero-copy rows; single- and multi-device codecs, where the locators are
  * computed once and every part gets the same `required`).  lens[i] == 0 marks

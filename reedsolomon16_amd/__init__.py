@@ -28,6 +28,10 @@ from .codec import (  # noqa: F401
     SCRUB_CLEAN,
     SCRUB_UNLOCATED,
     LOCATE_SET_MAX,
+    ROWS_CHECK_OK,
+    ROWS_CHECK_BAD,
+    ROWS_CHECK_NONE,
+    ROWS_CHECKS_MAX,
 )
 from ._capi import LIB_PATH, lib  # noqa: F401
 
@@ -36,4 +40,5 @@ __all__ = [
     "ErrShardNoData", "ErrShardSize", "ErrInvalidShardSize", "ErrNotSupported", "ErrShortData",
     "ErrReconstructRequired", "ErrNilWriter", "ErrSize", "ErrPanic", "ErrDevice", "LIB_PATH", "lib", "alloc_pinned",
     "EmptyShard", "SCRUB_CLEAN", "SCRUB_UNLOCATED", "LOCATE_SET_MAX",
+    "ROWS_CHECK_OK", "ROWS_CHECK_BAD", "ROWS_CHECK_NONE", "ROWS_CHECKS_MAX",
 ]

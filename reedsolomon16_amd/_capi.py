@@ -55,6 +55,9 @@ def lib() -> C.CDLL:
     L.rs_reconstruct_rows_dev_batch.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint8), P(C.c_uint8), sz, vp]
     L.rs_reconstruct_rows_dev_batch_patterns.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint8), P(C.c_uint8), sz,
                                                          P(C.c_uint32), sz, vp]
+    L.rs_reconstruct_rows_checked_dev_batch_patterns.argtypes = [vp, vp, sz, sz, sz, P(C.c_uint8), P(C.c_uint8), sz,
+                                                                 P(C.c_uint32), sz, i32, vp, P(i32), vp]
+    L.rs_debug_check_weights.argtypes = [i32, i32, i32, P(C.c_uint8), i32, vp]
     L.rs_reconstruct_rows.argtypes =[vp, P(vp), P(sz), i32, P(C.c_uint8)]
     L.rs_debug_decode_coefficients.argtypes = [i32, i32, i32, P(C.c_uint8), i32, vp]
     L.rs_verify_dev_batch.argtypes = [vp, vp, sz, sz, i32, sz, P(i32), vp]

@@ -225,6 +225,9 @@ def _dev_rows_opt(rows, count: int):
 RS_NULL_STREAM = C.c_void_p(-1).value  # include/rs_mi355x.h: HIP's null stream, asynchronous
 SCRUB_CLEAN, SCRUB_UNLOCATED = -1, -2  # include/rs_mi355x.h RS_SCRUB_*: verdicts of locate_dev / scrub_dev_batch
 LOCATE_SET_MAX = 4  # RS_LOCATE_SET_MAX: the most shards locate_set_dev_batch names per stripe
+# RS_ROWS_CHECK_*: verdicts of reconstruct_rows_checked_dev_batch_patterns, and its most checks per stripe
+ROWS_CHECK_OK, ROWS_CHECK_BAD, ROWS_CHECK_NONE = 0, 1, 2
+ROWS_CHECKS_MAX = 2
 
 
 def _stream_handle(stream):
@@ -855,6 +858,40 @@ class ReedSolomon:
             self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, table.ctypes.data_as(C.POINTER(C.c_uint8)),
             req.ctypes.data_as(C.POINTER(C.c_uint8)) if req is not None else None, table.shape[0],
             of.ctypes.data_as(C.POINTER(C.c_uint32)), S, _stream_handle(stream)))
+
+    def reconstruct_rows_checked_dev_batch_patterns(self, slab, patterns, required, pattern_of: Sequence[int],
+                                                    checks: int = ROWS_CHECKS_MAX, stream=None) -> np.ndarray:
+        """reconstruct_rows_dev_batch_patterns that also checks the rows it
+        reads (rs_reconstruct_rows_checked_dev_batch_patterns): the same
+        writes whatever the verdict, and an int32 verdict per stripe:
+        ROWS_CHECK_OK, ROWS_CHECK_BAD (the rows marked present are not
+        consistent; the rebuilt rows hold what the unchecked call writes) or
+        ROWS_CHECK_NONE (exactly k rows marked present, or checks == 0).  A
+        stripe with s rows marked present gets min(checks, s - k) checks.  The
+        call waits for its launches."""
+        n, S = self._slab(slab)
+        table = np.ascontiguousarray(np.asarray(patterns, dtype=bool).astype(np.uint8))
+        if table.ndim != 2 or table.shape[1] != self.total_shards():
+            raise ErrTooFewShards("patterns must have %d flags per row" % self.total_shards())
+        req = None
+        if required is not None:
+            req = np.ascontiguousarray(np.asarray(required, dtype=bool).astype(np.uint8))
+            if req.shape != table.shape:
+                raise ErrTooFewShards("required must have the shape of patterns")
+        of = np.ascontiguousarray(np.asarray(pattern_of, dtype=np.int64))
+        if of.shape != (n,):
+            raise TypeError("pattern_of must name one pattern per stripe")
+        if of.size and (of.min() < 0 or of.max() >= 1 << 32):
+            raise ErrInvalidArg("pattern_of entries must be pattern numbers")
+        of = of.astype(np.uint32)
+        verdict = np.full(max(n, 1), ROWS_CHECK_NONE, np.int32)
+        nbad = C.c_int(0)
+        _check(self._L.rs_reconstruct_rows_checked_dev_batch_patterns(
+            self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, table.ctypes.data_as(C.POINTER(C.c_uint8)),
+            req.ctypes.data_as(C.POINTER(C.c_uint8)) if req is not None else None, table.shape[0],
+            of.ctypes.data_as(C.POINTER(C.c_uint32)), S, int(checks), verdict.ctypes.data, C.byref(nbad),
+            _stream_handle(stream)))
+        return verdict[:n]
 
     def encode_dev_batch(self, slab, stream=None) -> None:
         """Encode a [nstripes, k+p, S] uint8 CUDA tensor in one launch.  Any

@@ -245,6 +245,18 @@ struct RowsSet : StreamUses {
     }
 };
 
+// The same with each pair's check tables behind its decode tables
+// (rs_reconstruct_rows_checked_dev_batch_patterns; gf_host.hpp
+// make_rows_chk_set): one descriptor per pair.
+struct RowsChkSet : StreamUses {
+    DevBuf<uint8_t> blob;
+    const RowsChkPattern *desc = nullptr;  // device array
+    ~RowsChkSet() {
+        drain();
+        blob.release();
+    }
+};
+
 // A small bounded LRU, most recent first.  find() moves a hit to the front;
 // put() inserts at the front and evicts past the cache's capacity, which runs
 // the evicted value's destructor (a DevPlan / UpdPlan waits there for its last
@@ -355,6 +367,13 @@ struct rs_codec {
     // rows sets keyed by their (present, rows rebuilt) pairs in order of first
     // use: the direct tier's counterpart of pset_cache
     Lru<std::vector<uint8_t>, std::unique_ptr<RowsSet>, 4> rset_cache;
+    // checked rows sets keyed by the check count and their (present, rows
+    // rebuilt) pairs, and the per-stripe flags of a checked call with their
+    // pinned readback (the call waits for its launches before it returns, under
+    // the codec mutex: no other call sees the two buffers in use)
+    Lru<std::vector<uint8_t>, std::unique_ptr<RowsChkSet>, 4> rchk_cache;
+    DevBuf<int> rchk_bad;
+    PinnedBuf rchk_host;
     // scrub (rs_verify_dev_batch_map / rs_locate_dev / rs_scrub_dev_batch): the
     // ratio map of the data shards (built on the first locate), the device
     // tables of a repaired row keyed by its data shard (UpdPlan::tw: the three
@@ -442,6 +461,9 @@ struct rs_codec {
         rowsplan_cache.items.clear();
         pset_cache.items.clear();
         rset_cache.items.clear();
+        rchk_cache.items.clear();
+        rchk_bad.release();
+        rchk_host.release();
         fixplan_cache.items.clear();
         scrub_rows.release(); scrub_dev.release(); scrub_list_dev.release(); scrub_set_dev.release();
         scrub_host.release();
@@ -3679,18 +3701,25 @@ int rows_set(rs_codec *c, const std::vector<RowsSetPair> &pairs, RowsSet **out) 
     return RS_OK;
 }
 
-// rs_reconstruct_rows_dev_batch_patterns after its NULL checks.
-int reconstruct_rows_patterns_call(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride,
-                                   size_t nstripes, const uint8_t *present, const uint8_t *required, size_t npat,
-                                   const uint32_t *pattern_of, size_t S, void *stream) {
+// Per table row: normalized present flags, the rows the call rebuilds (missing
+// and required; required == NULL: every missing row), their counts.
+struct RowsPatTables {
+    std::vector<uint8_t> pres, want;
+    std::vector<int> todo, npres;
+};
+
+// The error table of rs_reconstruct_rows_dev_batch_patterns after its NULL
+// checks, in its order; fills the tables.
+int rows_pat_tables(const rs_codec *c, size_t row_stride, size_t stripe_stride, size_t nstripes, const uint8_t *present,
+                    const uint8_t *required, size_t npat, const uint32_t *pattern_of, size_t S, RowsPatTables &tb) {
     const int total = c->total, k = c->k;
     for (size_t z = 0; z < nstripes; z++)
         if (pattern_of[z] >= npat) return RS_ERR_INVALID_ARG;
     if (S == 0) return RS_ERR_SHARD_NO_DATA;
-    // per table row: normalized present flags, the rows the call rebuilds
-    // (missing and required; required == NULL: every missing row), their counts
-    std::vector<uint8_t> pres(npat * total), want(npat * total);
-    std::vector<int> todo(npat, 0), npres(npat, 0);
+    std::vector<uint8_t> &pres = tb.pres, &want = tb.want;
+    std::vector<int> &todo = tb.todo, &npres = tb.npres;
+    pres.assign(npat * total, 0), want.assign(npat * total, 0);
+    todo.assign(npat, 0), npres.assign(npat, 0);
     bool too_few = false;
     for (size_t q = 0; q < npat; q++) {
         for (int i = 0; i < total; i++) {
@@ -3707,15 +3736,16 @@ int reconstruct_rows_patterns_call(rs_codec *c, uint8_t *base, size_t row_stride
     if (S % 64) return RS_ERR_INVALID_SHARD_SIZE;
     if (row_stride < S || (nstripes > 1 && stripe_stride < (size_t)total * row_stride)) return RS_ERR_INVALID_ARG;
     if ((long)c->m + k > (long)c->F->order) return RS_ERR_PANIC;  // error_locators / decode_schedule: the reference panics
-    bool any = false;
-    for (size_t z = 0; z < nstripes && !any; z++) any = todo[pattern_of[z]] > 0;
-    if (!any) return RS_OK;
+    return RS_OK;
+}
 
-    DevCall dc(c, stream);
-    if (dc.err) return dc.err;
-    const hipStream_t s = dc.s;
-    if (int e = build_decode_plan(c)) return e;
-    if (!c->dec_ok) return RS_ERR_PANIC;
+// The launches of rs_reconstruct_rows_dev_batch_patterns on s, for a call that
+// holds the codec (DevCall) and has built the decode plan.
+int rows_patterns_launch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
+                         const RowsPatTables &tb, size_t npat, const uint32_t *pattern_of, size_t S, hipStream_t s) {
+    const int total = c->total;
+    const std::vector<uint8_t> &pres = tb.pres, &want = tb.want;
+    const std::vector<int> &todo = tb.todo, &npres = tb.npres;
     if (!rec_lds_ok(c)) {
         // multi-pass codecs (n > 2048: never the direct tier): stripe by stripe
         std::vector<uint8_t *> rows(total);
@@ -3870,7 +3900,198 @@ int reconstruct_rows_patterns_call(rs_codec *c, uint8_t *base, size_t row_stride
         }
         z0 = z1;
     }
-    return dc.finish(RS_OK);
+    return RS_OK;
+}
+
+// rs_reconstruct_rows_dev_batch_patterns after its NULL checks.
+int reconstruct_rows_patterns_call(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride,
+                                   size_t nstripes, const uint8_t *present, const uint8_t *required, size_t npat,
+                                   const uint32_t *pattern_of, size_t S, void *stream) {
+    RowsPatTables tb;
+    if (int e = rows_pat_tables(c, row_stride, stripe_stride, nstripes, present, required, npat, pattern_of, S, tb)) return e;
+    bool any = false;
+    for (size_t z = 0; z < nstripes && !any; z++) any = tb.todo[pattern_of[z]] > 0;
+    if (!any) return RS_OK;
+
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    if (int e = build_decode_plan(c)) return e;
+    if (!c->dec_ok) return RS_ERR_PANIC;
+    return dc.finish(rows_patterns_launch(c, base, row_stride, stripe_stride, nstripes, tb, npat, pattern_of, S, dc.s));
+}
+
+// ---- The same with check equations over the rows marked present
+// (rs_reconstruct_rows_checked_dev_batch_patterns)
+
+// The cached device set of `pairs` (all different) for `checks`, as rows_set.
+int rows_chk_set(rs_codec *c, const std::vector<RowsChkPair> &pairs, int checks, RowsChkSet **out) {
+    const int total = c->total;
+    std::vector<uint8_t> key;
+    key.reserve(1 + pairs.size() * total * 2);
+    key.push_back((uint8_t)checks);
+    for (const RowsChkPair &p : pairs) {
+        for (int i = 0; i < total; i++) key.push_back(p.present[i] != 0);
+        for (int i = 0; i < total; i++) key.push_back(p.wanted && p.wanted[i] && !p.present[i]);
+    }
+    if (auto *hit = c->rchk_cache.find(key)) {
+        *out = hit->get();
+        return RS_OK;
+    }
+    auto rs = std::make_unique<RowsChkSet>();
+    std::vector<uint8_t> h;
+    if (!make_rows_chk_set(*c->F, c->k, c->p, c->dec_ifft_logs, c->dec_fft_logs, pairs, kDecGroup, 0, h)) return RS_ERR_PANIC;
+    HIP_TRY(rs->blob.ensure(h.size()));
+    const uint64_t g = (uint64_t)(uintptr_t)rs->blob.p;  // the image holds offsets: make them addresses of the blob
+    RowsChkDesc *d = (RowsChkDesc *)h.data();
+    for (size_t i = 0; i < pairs.size(); i++) d[i].tw += g, d[i].src_idx += g, d[i].dst_idx += g;
+    HIP_TRY(hipMemcpy(rs->blob.p, h.data(), h.size(), hipMemcpyHostToDevice));
+    rs->desc = (const RowsChkPattern *)rs->blob.p;
+    *out = c->rchk_cache.put(std::move(key), std::move(rs))->get();  // an eviction waits for that set's last launch
+    return RS_OK;
+}
+
+static_assert(sizeof(RowsChkDesc) == sizeof(RowsChkPattern) && offsetof(RowsChkDesc, tw) == offsetof(RowsChkPattern, tw) &&
+                  offsetof(RowsChkDesc, src_idx) == offsetof(RowsChkPattern, src_idx) &&
+                  offsetof(RowsChkDesc, dst_idx) == offsetof(RowsChkPattern, dst_idx) &&
+                  offsetof(RowsChkDesc, np) == offsetof(RowsChkPattern, np) &&
+                  offsetof(RowsChkDesc, t) == offsetof(RowsChkPattern, t) && offsetof(RowsChkDesc, c) == offsetof(RowsChkPattern, c),
+              "make_rows_chk_set writes the kernel's descriptors");
+static_assert(RS_ROWS_CHECKS_MAX == kDecChecksMax, "the header's check count is the kernel's");
+
+// rs_reconstruct_rows_checked_dev_batch_patterns after its NULL checks.
+int reconstruct_rows_checked_call(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
+                                  const uint8_t *present, const uint8_t *required, size_t npat, const uint32_t *pattern_of,
+                                  size_t S, int checks, int32_t *verdict, int *nbad, void *stream) {
+    RowsPatTables tb;
+    if (int e = rows_pat_tables(c, row_stride, stripe_stride, nstripes, present, required, npat, pattern_of, S, tb)) return e;
+    if (checks < 0 || checks > RS_ROWS_CHECKS_MAX) return RS_ERR_INVALID_ARG;
+    if (checks > 0 && !c->enc_ok) return RS_ERR_PANIC;  // make_check_weights: no encode schedule
+    const int total = c->total, k = c->k;
+    // checks per table row: c_z = min(checks, s - k) with s rows marked present
+    std::vector<int> cz(npat);
+    bool any_chk = false;
+    for (size_t q = 0; q < npat; q++) cz[q] = std::min(checks, tb.npres[q] - k);
+    for (size_t z = 0; z < nstripes; z++) {
+        verdict[z] = cz[pattern_of[z]] ? RS_ROWS_CHECK_OK : RS_ROWS_CHECK_NONE;
+        any_chk = any_chk || cz[pattern_of[z]];
+    }
+    if (!any_chk)  // nothing to check anywhere: the parent
+        return reconstruct_rows_patterns_call(c, base, row_stride, stripe_stride, nstripes, present, required, npat, pattern_of,
+                                              S, stream);
+
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    if (int e = build_decode_plan(c)) return e;
+    if (!c->dec_ok) return RS_ERR_PANIC;
+    // Per table row: fused (the direct tier's stripes whose rows and checks fit
+    // one launch's accumulators) or the parent's route plus a check-only entry.
+    // The parent's route sees the fused stripes as table row npat, which has
+    // every shard present: nothing to rebuild.
+    std::vector<uint8_t> fused(npat, 0);
+    for (size_t q = 0; q < npat; q++)
+        fused[q] = rec_lds_ok(c) && cz[q] > 0 && tb.todo[q] > 0 && rows_pat_direct(c, tb.todo[q]) &&
+                   tb.todo[q] <= kDecGroup - kDecChecksMax;  // the kernel's instantiations: t + c_z <= kDecGroup
+    {
+        std::vector<uint32_t> rest_of(nstripes);
+        bool rest = false;
+        for (size_t z = 0; z < nstripes; z++) {
+            const uint32_t q = pattern_of[z];
+            rest_of[z] = fused[q] ? (uint32_t)npat : q;
+            rest = rest || (!fused[q] && tb.todo[q] > 0);
+        }
+        if (rest) {
+            tb.pres.resize((npat + 1) * total, 1), tb.want.resize((npat + 1) * total, 0);
+            tb.todo.push_back(0), tb.npres.push_back(total);
+            if (int e = rows_patterns_launch(c, base, row_stride, stripe_stride, nstripes, tb, npat + 1, rest_of.data(), S, s))
+                return e;
+        }
+    }
+    HIP_TRY(c->rchk_bad.ensure(nstripes));
+    HIP_TRY(c->rchk_host.ensure(nstripes * sizeof(int)));
+    HIP_TRY(hipMemsetAsync(c->rchk_bad.p, 0, nstripes * sizeof(int), s));
+    // Equal (present, rows the fused kernel rebuilds) pairs share a descriptor.
+    std::vector<int> canon(npat, -1), id_of(npat, -1);
+    std::map<std::vector<uint8_t>, int> seen;
+    auto canon_of = [&](size_t q) {
+        if (canon[q] < 0) {
+            std::vector<uint8_t> f(tb.pres.begin() + q * total, tb.pres.begin() + (q + 1) * total);
+            if (fused[q]) f.insert(f.end(), tb.want.begin() + q * total, tb.want.begin() + (q + 1) * total);
+            canon[q] = seen.emplace(std::move(f), (int)q).first->second;
+        }
+        return canon[q];
+    };
+    // Stripe ranges as in rows_patterns_launch; per range one checked rows set
+    // and one launch per (rows, checks) count, rows == 0: check-only.
+    constexpr int kMaxT = kDecGroup - kDecChecksMax;
+    for (size_t z0 = 0; z0 < nstripes;) {
+        std::vector<RowsChkPair> pairs;
+        std::vector<int> members;
+        std::vector<RecStripe> lists[kMaxT + 1][kDecChecksMax + 1];
+        size_t bytes = 0, z1 = z0;
+        for (; z1 < nstripes && z1 - z0 < kPatMaxStripes; z1++) {
+            const size_t q = pattern_of[z1];
+            if (!cz[q]) continue;
+            const int cq = canon_of(q), t = fused[q] ? tb.todo[q] : 0;
+            if (id_of[cq] < 0) {
+                const size_t need = rows_chk_pair_bytes(c->bits, tb.npres[cq], t, cz[cq]);
+                if (!members.empty() && bytes + need > kPatSetBudget) break;
+                bytes += need;
+                id_of[cq] = (int)pairs.size();
+                pairs.push_back(RowsChkPair{tb.pres.data() + (size_t)cq * total,
+                                            t ? tb.want.data() + (size_t)cq * total : nullptr, cz[cq]});
+                members.push_back(cq);
+            }
+            lists[t][cz[cq]].push_back(RecStripe{(int)(z1 - z0), id_of[cq]});
+        }
+        for (int cq : members) id_of[cq] = -1;
+        if (!members.empty()) {
+            RowsChkSet *rs = nullptr;
+            if (int e = rows_chk_set(c, pairs, checks, &rs)) return e;
+            size_t off[kMaxT + 1][kDecChecksMax + 1] = {}, ib = 0;
+            for (int t = 0; t <= kMaxT; t++)
+                for (int nc = 1; nc <= kDecChecksMax; nc++) {
+                    off[t][nc] = ib;
+                    ib += align256(lists[t][nc].size() * sizeof(RecStripe));
+                }
+            int slot = 0;
+            uint8_t *h = nullptr, *g = nullptr;
+            if (int e = ring_acquire(c, ib, slot, h, g)) return e;
+            for (int t = 0; t <= kMaxT; t++)
+                for (int nc = 1; nc <= kDecChecksMax; nc++)
+                    if (!lists[t][nc].empty())
+                        std::memcpy(h + off[t][nc], lists[t][nc].data(), lists[t][nc].size() * sizeof(RecStripe));
+            HIP_TRY(hipMemcpyAsync(g, h, ib, hipMemcpyHostToDevice, s));
+            for (int t = 0; t <= kMaxT; t++)
+                for (int nc = 1; nc <= kDecChecksMax; nc++) {
+                    if (lists[t][nc].empty()) continue;
+                    DecodeRowsChkArgs da{};
+                    da.base = base + z0 * stripe_stride;
+                    da.row_stride = row_stride;
+                    da.stripe_stride = stripe_stride;
+                    da.pat = rs->desc;
+                    da.list = (const RecStripe *)(g + off[t][nc]);
+                    da.bad = c->rchk_bad.p + z0;
+                    da.S = S;
+                    da.nlist = (int)lists[t][nc].size();
+                    da.nt = t;
+                    da.nc = nc;
+                    HIP_TRY(launch_decode_rows_checked(c->bits, da, s));
+                }
+            HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+            c->ring_used[slot] = true;
+            HIP_TRY(rs->mark_used(s));
+        }
+        z0 = z1;
+    }
+    HIP_TRY(hipMemcpyAsync(c->rchk_host.p, c->rchk_bad.p, nstripes * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));  // the call's one host wait
+    const int *flag = (const int *)c->rchk_host.p;
+    int bad = 0;
+    for (size_t z = 0; z < nstripes; z++)
+        if (cz[pattern_of[z]] && flag[z]) verdict[z] = RS_ROWS_CHECK_BAD, bad++;
+    if (nbad) *nbad = bad;
+    return RS_OK;
 }
 
 }  // namespace
@@ -4459,6 +4680,29 @@ int rs_reconstruct_rows_dev_batch_patterns(rs_codec *c, uint8_t *base, size_t ro
     if (npatterns == 0 || npatterns > 65536) return RS_ERR_INVALID_ARG;
     return reconstruct_rows_patterns_call(c, base, row_stride, stripe_stride, nstripes, present, required, npatterns,
                                           pattern_of, S, stream);
+}
+
+int rs_reconstruct_rows_checked_dev_batch_patterns(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride,
+                                                   size_t nstripes, const uint8_t *present, const uint8_t *required,
+                                                   size_t npatterns, const uint32_t *pattern_of, size_t S, int checks,
+                                                   int32_t *verdict, int *nbad, void *stream) {
+    if (!c || !base || !present || !pattern_of || !verdict || nstripes > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
+    if (c->multi) return RS_ERR_INVALID_ARG;  // device rows live on one device: use rs_device_part
+    if (npatterns == 0 || npatterns > 65536) return RS_ERR_INVALID_ARG;
+    if (nbad) *nbad = 0;
+    return reconstruct_rows_checked_call(c, base, row_stride, stripe_stride, nstripes, present, required, npatterns,
+                                         pattern_of, S, checks, verdict, nbad, stream);
+}
+
+int rs_debug_check_weights(int bits, int k, int p, const uint8_t *present, int l, uint32_t *out) {
+    if ((bits != 8 && bits != 16) || !present || !out || k <= 0 || p <= 0 || l < 0) return RS_ERR_INVALID_ARG;
+    int np = 0;
+    for (int i = 0; i < k + p; i++) np += present[i] ? 1 : 0;
+    if (l >= np - k) return RS_ERR_INVALID_ARG;  // checks exist for l < (number present) - k
+    std::vector<uint32_t> w((size_t)(l + 1) * (k + p));
+    if (!make_check_weights(field(bits), k, p, present, l + 1, w.data())) return RS_ERR_PANIC;
+    std::copy(w.end() - (k + p), w.end(), out);
+    return RS_OK;
 }
 
 int rs_reconstruct_rows_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,

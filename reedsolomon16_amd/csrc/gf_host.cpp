@@ -1033,4 +1033,89 @@ bool pick_check_rows(const Field &F, int p, int s, const uint32_t *const *cols, 
     return invert_matrix(F, s, A, inv);
 }
 
+bool make_check_weights(const Field &F, int k, int p, const uint8_t *present, int c, uint32_t *out) {
+    if (k <= 0 || p <= 0 || c < 0) return false;
+    std::vector<uint32_t> il, fl;
+    int nchunks = 0;
+    if (!encode_schedule(F, k, p, il, fl, nchunks)) return false;
+    const int m = ceil_pow2(p), total = k + p;
+    if ((uint64_t)m + (uint64_t)k > F.order) return false;
+    auto pos = [&](int t) { return (uint32_t)(t < k ? m + t : t - k); };
+    std::vector<uint32_t> absent;
+    for (int t = 0; t < total; t++)
+        if (!present[t]) absent.push_back(pos(t));
+    if (c > total - (int)absent.size() - k) return false;
+    std::fill(out, out + (size_t)c * total, 0u);
+    for (int t = 0; t < total && c > 0; t++) {
+        if (!present[t]) continue;
+        const uint32_t x = pos(t);
+        uint32_t lh = 0;  // log of u_t * Gamma(x_t): every factor is non-zero (distinct positions)
+        for (int y = p; y < m; y++) lh = F.add_mod(lh, F.log[x ^ (uint32_t)y]);
+        for (uint32_t a : absent) lh = F.add_mod(lh, F.log[x ^ a]);
+        uint32_t v = F.exp[lh];
+        for (int l = 0; l < c; l++, v = gmul(F, v, x)) out[(size_t)l * total + t] = v;
+    }
+    return true;
+}
+
+void make_check_tables(const Field &F, int k, int p, const uint8_t *present, int c, const uint32_t *w, uint32_t *out) {
+    const int twd = tw_dwords(F.bits), total = k + p;
+    for (int l = 0; l < c; l++)
+        for (int t = 0; t < total; t++)
+            if (present[t]) {
+                const uint32_t h = w[(size_t)l * total + t];
+                make_twiddle(F, h ? F.log[h] : F.mod, out, true);
+                out += twd;
+            }
+}
+
+size_t rows_chk_pair_bytes(int bits, int np, int t, int c) {
+    return rows_set_align((size_t)(t + c) * np * tw_dwords(bits) * 4) + rows_set_align((size_t)np * 4) +
+           rows_set_align((size_t)std::max(t, 1) * 4) + sizeof(RowsChkDesc);
+}
+
+bool make_rows_chk_set(const Field &F, int k, int p, const std::vector<uint32_t> &ifft, const std::vector<uint32_t> &fft,
+                       const std::vector<RowsChkPair> &pairs, int group, uint64_t base, std::vector<uint8_t> &image) {
+    const int total = k + p, twd = tw_dwords(F.bits);
+    const size_t npairs = pairs.size();
+    std::vector<std::vector<int>> src(npairs), dst(npairs);
+    std::vector<size_t> off(npairs);
+    size_t bytes = rows_set_align(npairs * sizeof(RowsChkDesc));
+    for (size_t q = 0; q < npairs; q++) {
+        for (int i = 0; i < total; i++) {
+            if (pairs[q].present[i]) src[q].push_back(i);
+            else if (pairs[q].wanted && pairs[q].wanted[i]) dst[q].push_back(i);
+        }
+        if (src[q].empty() || pairs[q].c < 1 || (int)dst[q].size() + pairs[q].c > group) return false;
+        off[q] = bytes;
+        bytes += rows_chk_pair_bytes(F.bits, (int)src[q].size(), (int)dst[q].size(), pairs[q].c) - sizeof(RowsChkDesc);
+    }
+    image.assign(bytes, 0);
+    std::vector<uint8_t> erased(total), pres(total);
+    std::vector<uint32_t> el, w;
+    for (size_t q = 0; q < npairs; q++) {
+        const int np = (int)src[q].size(), t = (int)dst[q].size(), c = pairs[q].c;
+        for (int i = 0; i < total; i++) pres[i] = pairs[q].present[i] != 0, erased[i] = !pres[i];
+        const size_t o_tw = off[q], o_si = o_tw + rows_set_align((size_t)(t + c) * np * twd * 4);
+        const size_t o_di = o_si + rows_set_align((size_t)np * 4);
+        uint32_t *tw = (uint32_t *)(image.data() + o_tw);
+        if (t) {
+            if (!error_locators(F, k, p, erased.data(), el)) return false;
+            make_decode_tables(F, k, p, erased.data(), el, ifft, fft, dst[q].data(), t, tw);
+        }
+        w.assign((size_t)c * total, 0);
+        if (!make_check_weights(F, k, p, pres.data(), c, w.data())) return false;
+        make_check_tables(F, k, p, pres.data(), c, w.data(), tw + (size_t)t * np * twd);
+        std::memcpy(image.data() + o_si, src[q].data(), (size_t)np * 4);
+        if (t) std::memcpy(image.data() + o_di, dst[q].data(), (size_t)t * 4);
+        RowsChkDesc d{};
+        d.tw = base + o_tw;
+        d.src_idx = base + o_si;
+        d.dst_idx = base + o_di;
+        d.np = np, d.t = t, d.c = c;
+        std::memcpy(image.data() + q * sizeof(RowsChkDesc), &d, sizeof(d));
+    }
+    return true;
+}
+
 }  // namespace rs

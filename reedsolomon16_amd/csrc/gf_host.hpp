@@ -357,4 +357,45 @@ bool pick_check_rows(const Field &F, int p, int s, const uint32_t *const *cols, 
 // R being disjoint from them.
 void check_row_order(int k, int p, const uint8_t *present, const int *T, int s, int *order);
 
+// ---- Checked degraded read: check equations over the rows marked present
+// (rs_reconstruct_rows_checked_dev_batch_patterns).  With the
+// positions x and the column multipliers u_x of LocateSet above (no shift
+// point: a position of 0 is harmless), A the shards not marked present and
+// Gamma(X) = the product of (X ^ x_a) over a in A, Gamma vanishes on A and
+// deg(Gamma * X^l) < p for l < p - |A|, so over the present rows alone
+//   h_l[t] = u_t * Gamma(x_t) * x_t^l,   sum_{t present} h_l[t] * row_t = 0.
+// h_0[t] != 0 at every present t and h_l[t] = h_0[t] * x_t^l: any c of these
+// rows have every c columns independent (distinct positions), so up to c
+// wrong rows at a symbol never leave all c check symbols zero.
+// out: c rows of k + p weights, 0 at the shards not present.  False where
+// encode_schedule returns false, where m + k exceeds the field order, or for
+// c outside [0, (number present) - k].
+bool make_check_weights(const Field &F, int k, int p, const uint8_t *present, int c, uint32_t *out);
+// The weights as c x (number present) images of "multiply by h_l[t]" at out +
+// (l * npresent + i) * tw_dwords, i counting the present shards in ascending
+// order (make_decode_tables' layout, so a pair's check tables follow its decode
+// tables as further rows); a zero weight is the all-zero table.  w:
+// make_check_weights' output for the same present and c.
+void make_check_tables(const Field &F, int k, int p, const uint8_t *present, int c, const uint32_t *w, uint32_t *out);
+
+// ---- Checked rows set: make_rows_set's blob with the check tables of each
+// pair behind its decode tables (codec.cpp RowsChkSet, kernels.hpp
+// RowsChkPattern).  A pair rebuilds t >= 0 rows (wanted == nullptr or nothing
+// wanted and missing: the check-only form) with c >= 1 checks, t + c <= group:
+// one descriptor per pair, tables (t + c) x np.
+struct RowsChkDesc {  // kernels.hpp RowsChkPattern with addresses as integers
+    uint64_t tw, src_idx, dst_idx;
+    int32_t np, t, c, pad;
+};
+struct RowsChkPair {
+    const uint8_t *present, *wanted;  // k+p flags each; wanted may be nullptr
+    int c;
+};
+size_t rows_chk_pair_bytes(int bits, int np, int t, int c);
+// As make_rows_set (descriptor q is pair q's).  False where error_locators or
+// make_check_weights refuses, or a pair has t + c > group or c < 1.
+bool make_rows_chk_set(const Field &F, int k, int p, const std::vector<uint32_t> &ifft_logs,
+                       const std::vector<uint32_t> &fft_logs, const std::vector<RowsChkPair> &pairs, int group,
+                       uint64_t base, std::vector<uint8_t> &image);
+
 }  // namespace rs

@@ -2621,6 +2621,116 @@ hipError_t launch_decode_rows_patterns(int bits, const DecodeRowsPatArgs &a, hip
     return narrow ? decode_rows_pat_f<F8<2>>(a, s) : decode_rows_pat_f<F8<4>>(a, s);
 }
 
+// ---------------------------------------------------------------- direct decode with check equations
+// k_decode_rows_pat with NC more accumulators (kernels.hpp DecodeRowsChkArgs,
+// rs_reconstruct_rows_checked_dev_batch_patterns): the descriptor's table has
+// NT + NC rows over the same np present rows, so the loop is the same with
+// NT + NC products per prepared unit; the first NT sums are the wanted rows,
+// the last NC must be zero.
+namespace {
+
+typedef __attribute__((address_space(4))) const RowsChkPattern dec_cchk_t;
+
+// Waves per SIMD the compiler must leave room for: 2 as k_decode_rows_pat, but
+// 5 up to three accumulators, where that kernel's F16<4> variants have 91-93
+// VGPRs (96 allocated: five waves) and this one's <1, 2> came out at 97 (104
+// allocated: four waves) without the bound.
+constexpr int dec_chk_waves(int na) { return na <= 3 ? 5 : 2; }
+
+// A copy of k_decode_rows_pat's body (that kernel and its descriptor keep
+// their code and registers).  NT + NC <= kDecGroup accumulators, as there.
+// NT == 0: nothing is stored but the flag.
+template <class F, int NT, int NC>
+__global__ void __launch_bounds__(256, dec_chk_waves(NT + NC)) k_decode_rows_chk(DecodeRowsChkArgs a, int y0) {
+    typedef typename F::Vec V;
+    constexpr int NA = NT + NC;
+    static_assert(NA <= kDecGroup && NC >= 1, "accumulators of k_decode_rows_pat at most");
+    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= F::units(a.S)) return;
+    dec_cstripe_t &e = ((dec_cstripe_t *)a.list)[(uint64_t)blockIdx.y + (uint64_t)y0];
+    dec_cchk_t &d = ((dec_cchk_t *)a.pat)[e.pat];
+    uint8_t *sb = a.base + (uint64_t)e.stripe * a.stripe_stride;
+    const int np = d.np;
+    const uint32_t *tw = d.tw;  // table (j, i) at tw + (j * np + i) * TWD
+    upd_cint_t *si = (upd_cint_t *)d.src_idx, *di = (upd_cint_t *)d.dst_idx;
+    auto srow = [&](int i) -> const uint8_t * { return sb + (uint64_t)si[i] * a.row_stride; };
+    V acc[NA];
+#pragma unroll
+    for (int j = 0; j < NA; j++) acc[j] = F::zero();
+    const uint64_t trow = (uint64_t)np * F::TWD;
+    int i = 0;
+    for (; i + kDecRows <= np; i += kDecRows) {
+        V x[kDecRows];
+#pragma unroll
+        for (int q = 0; q < kDecRows; q++) x[q] = F::load(srow(i + q), u);
+#pragma unroll
+        for (int q = 0; q < kDecRows; q++) {
+            UpdMasks<F> mk;
+            mk.prepare(x[q]);
+#pragma unroll
+            for (int j = 0; j < NA; j++) {
+                const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)(i + q) * F::TWD);
+                mk.mul_add(acc[j], tb.v);
+            }
+        }
+    }
+    for (; i < np; i++) {
+        UpdMasks<F> mk;
+        mk.prepare(F::load(srow(i), u));
+#pragma unroll
+        for (int j = 0; j < NA; j++) {
+            const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)i * F::TWD);
+            mk.mul_add(acc[j], tb.v);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NT; j++) F::store(sb + (uint64_t)di[j] * a.row_stride, u, acc[j]);
+    uint32_t any = 0;
+#pragma unroll
+    for (int j = NT; j < NA; j++) any |= F::diff(acc[j], F::zero());
+    flag_mismatch(a.bad + (uint64_t)e.stripe, any != 0);  // one plain store per wave with a non-zero sum
+}
+
+template <class F, int NT, int NC>
+hipError_t decode_chk_group(const DecodeRowsChkArgs &a, hipStream_t s) {
+    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
+    return for_y(a.nlist, [&](int y0, int ny) {
+        hipLaunchKernelGGL((k_decode_rows_chk<F, NT, NC>), dim3(grid_x(units).x, ny), dim3(256), 0, s, a, y0);
+    });
+}
+
+template <class F, int NC>
+hipError_t decode_rows_chk_c(const DecodeRowsChkArgs &a, hipStream_t s) {
+    static_assert(kDecGroup == 8 && kDecChecksMax == 2, "decode_rows_chk_c dispatches 0..6 rows with 1..2 checks");
+    switch (a.nt) {
+        case 0: return decode_chk_group<F, 0, NC>(a, s);
+        case 1: return decode_chk_group<F, 1, NC>(a, s);
+        case 2: return decode_chk_group<F, 2, NC>(a, s);
+        case 3: return decode_chk_group<F, 3, NC>(a, s);
+        case 4: return decode_chk_group<F, 4, NC>(a, s);
+        case 5: return decode_chk_group<F, 5, NC>(a, s);
+        default: return decode_chk_group<F, 6, NC>(a, s);
+    }
+}
+
+template <class F>
+hipError_t decode_rows_chk_f(const DecodeRowsChkArgs &a, hipStream_t s) {
+    return a.nc == 1 ? decode_rows_chk_c<F, 1>(a, s) : decode_rows_chk_c<F, 2>(a, s);
+}
+
+}  // namespace
+
+// Unit widths by launch_decode_rows_patterns's rule.
+hipError_t launch_decode_rows_checked(int bits, const DecodeRowsChkArgs &a, hipStream_t s) {
+    constexpr uint64_t kDecMinBlocks = 1024;
+    if (a.nt < 0 || a.nt > kDecGroup - kDecChecksMax || a.nc < 1 || a.nc > kDecChecksMax) return hipErrorInvalidValue;
+    if (a.nlist <= 0 || a.S == 0 || a.S % 64 || !a.base || !a.pat || !a.list || !a.bad) return hipErrorInvalidValue;
+    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * (uint64_t)a.nlist;
+    const bool narrow = pick_narrow(wide_blocks < kDecMinBlocks);
+    if (bits == 16) return narrow ? decode_rows_chk_f<F16<2>>(a, s) : decode_rows_chk_f<F16<4>>(a, s);
+    return narrow ? decode_rows_chk_f<F8<2>>(a, s) : decode_rows_chk_f<F8<4>>(a, s);
+}
+
 // ---------------------------------------------------------------- syndrome scan (scrub)
 // Stored parity rows against freshly encoded ones (kernels.hpp ScanArgs):
 // k_update's shape without a product.  A stream: every byte of the 2 p rows is

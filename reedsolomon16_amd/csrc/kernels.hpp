@@ -331,6 +331,31 @@ struct DecodeRowsPatArgs {
 };
 hipError_t launch_decode_rows_patterns(int bits, const DecodeRowsPatArgs &a, hipStream_t s);
 
+// The same with nc check equations over the present rows in the same pass
+// (rs_reconstruct_rows_checked_dev_batch_patterns; gf_host.hpp
+// make_check_weights): the descriptor's table holds the pair's t decode rows,
+// then its c check rows, all over the same np present rows; a check row's
+// weighted sum of the present rows is zero at every symbol of a consistent
+// stripe.  A lane whose check sums are not all zero sets bad[stripe] (cleared
+// by the caller; only ever set to 1).  nt == 0: the check-only form, which
+// writes nothing but bad.
+struct RowsChkPattern {
+    const uint32_t *tw;             // (t + c) x np tables, (j, i) at (j*np + i) * tw_dwords
+    const int *src_idx, *dst_idx;   // np present shard indices, t wanted ones
+    int np, t, c, pad;
+};
+constexpr int kDecChecksMax = 2;
+struct DecodeRowsChkArgs {
+    uint8_t *base;  // shard i of stripe z at base + z*stripe_stride + i*row_stride
+    uint64_t row_stride, stripe_stride;
+    const RowsChkPattern *pat;  // device array
+    const RecStripe *list;      // device array, nlist entries; every pat[list[].pat] has t == nt, c == nc
+    int *bad;                   // device array, one word per stripe of the slab at base
+    uint64_t S;
+    int nlist, nt, nc;          // 0 <= nt <= kDecGroup - kDecChecksMax, 1 <= nc <= kDecChecksMax
+};
+hipError_t launch_decode_rows_checked(int bits, const DecodeRowsChkArgs &a, hipStream_t s);
+
 
 // ---- Syndrome scan of one stripe (scrub): compares the p stored parity rows
 // with the p rows a fresh encode of the stored data gave, writes neither.

@@ -497,6 +497,72 @@ int rs_encode_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, siz
 int rs_verify_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, size_t stripe_stride, int nstripes,
                         size_t shard_size, int *ok, void *stream);
 
+/* ---------------- A list of stripes of different sizes (beyond the reference) ----------------
+ * The batch calls above take one shard_size and one base + z*stripe_stride
+ * layout for the whole slab.  These two take a host array of nstripes
+ * descriptors, one per stripe, each with a buffer and a size of its own: shard
+ * i of stripe z lies at stripes[z].base + i*row_stride, data rows 0..k-1 and
+ * parity rows k..k+p-1 as in rs_encode_dev_batch.  The small-object write path
+ * of an object store, which one call per object leaves launch-bound, goes out
+ * in shared launches: one grid over the column blocks of all stripes (DESIGN.md
+ * section 4.20).
+ *
+ * rs_encode_dev_list writes, per stripe, bit for bit what rs_encode_dev_batch
+ * writes for that stripe alone (nstripes = 1, that shard_size), and no byte
+ * outside the p parity rows' shard_size bytes.  Stream semantics are
+ * rs_encode_dev_batch's: asynchronous on a caller stream or RS_NULL_STREAM,
+ * complete on return for NULL.
+ * rs_verify_dev_list sets verdict[z] (host, nstripes entries, may be NULL) to 1
+ * when stripe z's parity matches its data and to 0 when it does not; *ok is
+ * the AND of the verdicts.  Synchronous, like rs_verify_dev_batch_map.
+ * The list is read before the call returns and may be freed then.  Stripes
+ * that overlap in memory are the caller's error and are not checked.
+ * nstripes == 0 returns RS_OK with nothing launched (*ok = 1), once rules 1
+ * and 6 below have passed.
+ *
+ * Errors, decided before any device call, in this order:
+ *   1. NULL codec or list (NULL ok for verify), a multi-device codec, more
+ *      than INT32_MAX stripes, or a stripe with a NULL base: RS_ERR_INVALID_ARG;
+ *   2. any shard_size == 0: RS_ERR_SHARD_NO_DATA;
+ *   3. any shard_size not a multiple of 64: RS_ERR_INVALID_SHARD_SIZE;
+ *   4. any row_stride < shard_size: RS_ERR_INVALID_ARG;
+ *   5. any stripe whose data rows span 2^32 bytes or more,
+ *      (k-1)*row_stride + shard_size >= 2^32: RS_ERR_INVALID_ARG (the list
+ *      kernel addresses a stripe's data rows through a 32-bit buffer
+ *      descriptor; this call refuses what the descriptor cannot hold);
+ *   6. RS_ERR_PANIC where the reference's encode of the geometry panics.
+ * Each rule is applied to the whole list before the next.
+ *
+ * Routing.  Geometries with m = ceilPow2(p) <= 32 use the list kernel, the
+ * others (LDS and multi-pass encodes) loop over the stripes, one launch
+ * sequence each: right, not fast.  Where a stripe alone would take the
+ * bit-sliced or the split kernel (GF(2^16), m = 4..32), a stripe of more than
+ * RS_ENCODE_LIST_MAX_BS32 / _BS16 / _SPLIT bytes per shard goes to one
+ * launch of that kernel on the same stream and the rest share the list
+ * launch (rs_debug_set_path "enc_list").  GF(2^8) and GF(2^16) with m <= 2
+ * always take the list kernel. */
+typedef struct {
+    uint8_t *base;      /* device: shard i at base + i*row_stride */
+    size_t row_stride;  /* >= shard_size */
+    size_t shard_size;  /* > 0, a multiple of 64 */
+} rs_stripe;
+/* Largest shard_size at which the list kernel measured faster than one launch
+ * of the stripe's own kernel per stripe, over 64 stripes of one size in
+ * {4, 16, 64, 256, 1024} KiB (profiles/encode_list_c2.txt), by the kernel a
+ * stripe alone takes (rs_encode_path):
+ *   bit-sliced, m = 32 (128+32): 256 KiB; at 1 MiB its own kernel wins, 2727
+ *     against 2998 us;
+ *   bit-sliced, m = 16 (37+9): 1 MiB, the largest size measured (933 against
+ *     994 us there): no crossover found;
+ *   split (64+8, m = 8, and 193+16, m = 16): 1 MiB, the largest size measured
+ *     (964 against 1291 and 3462 against 3905 us there): no crossover found. */
+#define RS_ENCODE_LIST_MAX_BS32 ((size_t)256 << 10)
+#define RS_ENCODE_LIST_MAX_BS16 ((size_t)1024 << 10)
+#define RS_ENCODE_LIST_MAX_SPLIT ((size_t)1024 << 10)
+int rs_encode_dev_list(rs_codec *codec, const rs_stripe *stripes /* HOST, nstripes */, size_t nstripes, void *stream);
+int rs_verify_dev_list(rs_codec *codec, const rs_stripe *stripes /* HOST, nstripes */, size_t nstripes,
+                       int8_t *verdict /* HOST, nstripes, may be NULL */, int *ok, void *stream);
+
 /* Name of the kernel path the codec uses for encode ("reg-m32", "lds", "multipass", ...). */
 const char *rs_encode_path(const rs_codec *codec);
 
@@ -958,6 +1024,31 @@ int rs_debug_zc_rows(uint8_t *const *rows, int nrows, size_t S);
  * host's own check before that kernel is launched.  Host only. */
 int rs_debug_encode_bs_fits(int data_shards, int parity_shards, size_t row_stride, size_t shard_size);
 
+/* 1 when the data rows of a stripe fit the list kernel's 32-bit buffer
+ * descriptor, (k-1)*row_stride + shard_size < 2^32 without wrapping, 0
+ * otherwise: rule 5 of rs_encode_dev_list.  Host only. */
+int rs_debug_encode_list_fits(int data_shards, size_t row_stride, size_t shard_size);
+
+/* 1 when rs_encode_dev_list gives a stripe of shard_size bytes per shard a
+ * launch of its own kernel under the current "enc_list" knob, 0 when the
+ * stripe joins the list launch; -1 for a NULL, multi-device or panicking
+ * codec.  Host only: the codec's device is not touched. */
+int rs_debug_encode_list_own(const rs_codec *codec, size_t shard_size);
+
+/* The launch plan of rs_encode_dev_list for stripes of sizes[0..nstripes)
+ * that all go through the list kernel of a geometry with this field and
+ * parity count (m = ceilPow2(p) <= 32), under unit_width -1 / 0 / 1 as the
+ * "unit_width" knob below.  The list is cut, in order, into launches of at
+ * most max_stripes stripes (0: the library's ring-slot limit) and fewer than
+ * 2^31 workgroups.  *nlaunches = their number; launches (may be NULL) gets
+ * four values per launch: first stripe, one past the last, bytes of a row per
+ * workgroup, workgroups; first_wg (may be NULL) gets per launch its prefix of
+ * (stripes + 1) entries, nstripes + *nlaunches in all: entry i = workgroups of
+ * the launch's stripes before its i-th.  RS_ERR_INVALID_ARG for a size that is
+ * 0, no multiple of 64 or >= 2^32.  Host only, no memory behind the sizes. */
+int rs_debug_encode_list_plan(int field_bits, int parity_shards, int unit_width, const size_t *sizes, size_t nstripes,
+                              size_t max_stripes, int *nlaunches, uint64_t *launches, uint32_t *first_wg);
+
 /* Test-only kernel-path overrides (process-wide), so the parity tests can run
  * the variants other geometries select on the same small inputs:
  *   "bs" 0/1          bit-sliced GF(2^16) encode off / on (default 1; read by rs_new),
@@ -988,7 +1079,10 @@ int rs_debug_encode_bs_fits(int data_shards, int parity_shards, size_t row_strid
  *   "scrub_batch" -1/0/1  rs_scrub_dev_batch locates its bad stripes through rs_locate_dev_batch's
  *                     shared launches by the measured threshold (-1, default), never (0: one
  *                     stripe at a time), or always (1),
- *   "scrub_chunk" >= 0  listed stripes per pass of rs_locate_dev_batch, 0 = automatic (default 0).
+ *   "scrub_chunk" >= 0  listed stripes per pass of rs_locate_dev_batch, 0 = automatic (default 0),
+ *   "enc_list" -1/0/1  rs_encode_dev_list / rs_verify_dev_list: the list kernel by the measured
+ *                     size thresholds (-1, default), never (0: one launch sequence per stripe),
+ *                     or always where m <= 32 admits it (1).
  * Returns RS_ERR_INVALID_ARG for an unknown knob or value.  Host only. */
 int rs_debug_set_path(const char *knob, int value);
 

@@ -15,6 +15,12 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rs_mi355x.h")
 _lib = None
 
 
+class Stripe(C.Structure):
+    """rs_stripe: one entry of rs_encode_dev_list's / rs_verify_dev_list's list."""
+
+    _fields_ = [("base", C.c_void_p), ("row_stride", C.c_size_t), ("shard_size", C.c_size_t)]
+
+
 def lib() -> C.CDLL:
     """Load the engine library (raises OSError if it has not been built)."""
     global _lib
@@ -110,11 +116,16 @@ def lib() -> C.CDLL:
     L.rs_debug_set_path.argtypes = [C.c_char_p, i32]
     L.rs_debug_zc_rows.argtypes = [P(vp), i32, sz]
     L.rs_debug_encode_bs_fits.argtypes = [i32, i32, sz, sz]
+    L.rs_encode_dev_list.argtypes = [vp, P(Stripe), sz, vp]
+    L.rs_verify_dev_list.argtypes = [vp, P(Stripe), sz, vp, P(i32), vp]
+    L.rs_debug_encode_list_fits.argtypes = [i32, sz, sz]
+    L.rs_debug_encode_list_own.argtypes = [vp, sz]
+    L.rs_debug_encode_list_plan.argtypes = [i32, i32, i32, P(sz), sz, sz, P(i32), vp, vp]
     _lib = L
     return L
 
 
-_PATH_DEFAULTS = {"bs": 1, "sub": 1, "prune": 1, "unit_width": -1, "hp_tiles": 0, "hp_step": 0, "zc": 3, "hp_tune": 1, "rec_half": 0, "dec_lab": 0, "lds_big": 1, "rows_direct": -1, "pat_tier": 0, "bsdec_grid": 0, "scrub_batch": -1, "scrub_chunk": 0}
+_PATH_DEFAULTS = {"bs": 1, "sub": 1, "prune": 1, "unit_width": -1, "hp_tiles": 0, "hp_step": 0, "zc": 3, "hp_tune": 1, "rec_half": 0, "dec_lab": 0, "lds_big": 1, "rows_direct": -1, "pat_tier": 0, "bsdec_grid": 0, "scrub_batch": -1, "scrub_chunk": 0, "enc_list": -1}
 
 
 def set_path(knob: str, value: int) -> None:

@@ -906,6 +906,37 @@ class ReedSolomon:
         _check(self._L.rs_encode_dev_batch(self._h, slab.data_ptr(), slab.stride(1), slab.stride(0), n, S,
                                            _stream_handle(stream)))
 
+    def _stripe_list(self, stripes):
+        """rs_stripe descriptors of a sequence of 2-D (k+p, S) uint8 CUDA
+        tensors; a padded strided view is allowed (the row stride comes from
+        the tensor)."""
+        arr = (_capi.Stripe * max(len(stripes), 1))()
+        for z, t in enumerate(stripes):
+            if t.dim() != 2 or t.shape[0] != self.total_shards():
+                raise TypeError("stripe %d must be a [k+p, S] uint8 CUDA tensor" % z)
+            if not t.is_cuda or str(t.dtype) != "torch.uint8" or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise TypeError("stripe %d: rows must be contiguous uint8 on a CUDA device" % z)
+            if t.device.index != self.device:
+                raise TypeError("stripe %d is on device %s, the codec on device %d" % (z, t.device.index, self.device))
+            arr[z] = _capi.Stripe(t.data_ptr(), t.stride(0), t.shape[1])
+        return arr
+
+    def encode_dev_list(self, stripes, stream=None) -> None:
+        """Encode a list of stripes of different sizes, each a (k+p, S_z) uint8
+        CUDA tensor of its own, in shared launches (rs_encode_dev_list)."""
+        arr = self._stripe_list(stripes)
+        _check(self._L.rs_encode_dev_list(self._h, arr, len(stripes), _stream_handle(stream)))
+
+    def verify_dev_list(self, stripes, stream=None) -> np.ndarray:
+        """Verify such a list (rs_verify_dev_list): a bool array, True where a
+        stripe's parity matches its data."""
+        arr = self._stripe_list(stripes)
+        verdict = np.zeros(max(len(stripes), 1), np.int8)
+        ok = C.c_int(0)
+        _check(self._L.rs_verify_dev_list(self._h, arr, len(stripes), verdict.ctypes.data, C.byref(ok),
+                                          _stream_handle(stream)))
+        return verdict[:len(stripes)].astype(bool)
+
     # ---------------- incremental update of device rows (beyond the reference:
     # its Leopard codecs reject Update / EncodeIdx; the encode is GF-linear, so
     # a changed data row moves each parity row by one constant times the change)

@@ -556,7 +556,7 @@ int upload_split(rs_codec *c) {
 // the reconstruct FFT unpruned, the narrow / wide LDS units) on the same small
 // inputs.  Process-wide; read when a codec is created (bs) or at each launch.
 std::atomic<int> g_path_bs{1}, g_path_sub{1}, g_path_prune{1}, g_path_unit_width{-1}, g_path_hp_tiles{0}, g_path_hp_step{0},
-    g_path_zc{3}, g_path_hp_tune{1}, g_path_rec_half{0}, g_path_dec_lab{0}, g_path_lds_big{1}, g_path_rows_direct{-1}, g_path_pat_tier{0}, g_path_bsdec_grid{0}, g_path_scrub_batch{-1}, g_path_scrub_chunk{0};
+    g_path_zc{3}, g_path_hp_tune{1}, g_path_rec_half{0}, g_path_dec_lab{0}, g_path_lds_big{1}, g_path_rows_direct{-1}, g_path_pat_tier{0}, g_path_bsdec_grid{0}, g_path_scrub_batch{-1}, g_path_scrub_chunk{0}, g_path_enc_list{-1};
 bool bs_enabled() { return g_path_bs.load(std::memory_order_relaxed) != 0; }
 bool sub_enabled() { return g_path_sub.load(std::memory_order_relaxed) != 0; }
 bool prune_enabled() { return g_path_prune.load(std::memory_order_relaxed) != 0; }
@@ -2062,6 +2062,122 @@ int verify_map_device(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t 
     HIP_TRY(hipMemcpyAsync(hflags, dflags, 4 * (size_t)nstripes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     *flags = hflags;
+    return RS_OK;
+}
+
+// ---- A list of stripes of different sizes (rs_encode_dev_list / rs_verify_dev_list; rs_mi355x.h)
+static_assert(sizeof(EncListStripe) == 24 && sizeof(rs_stripe) == 24 && offsetof(rs_stripe, row_stride) == 8 &&
+                  offsetof(rs_stripe, shard_size) == 16,
+              "a host descriptor is the kernel's descriptor");
+// Descriptors and prefix of one launch travel through one ring slot.
+constexpr size_t kEncListSlotBytes = 4u << 20;
+constexpr size_t kEncListMaxStripes = (kEncListSlotBytes - 256 - 4) / (sizeof(EncListStripe) + 4);
+// pick_narrow's rule for the GF(2^8) register units (kernels.hip launch_encode_reg), over a launch's workgroups
+constexpr uint64_t kEncListNarrowBelow = 1024;
+
+// The launches of the list kernel over stripes[order[0..n)], in order; stripe
+// order[i]'s mismatch word is mismatch[i] (verify).  Nothing waits for a kernel.
+int encode_list_launches(rs_codec *c, const rs_stripe *stripes, const std::vector<uint32_t> &order, int *mismatch,
+                         hipStream_t s) {
+    const size_t n = order.size();
+    if (!n) return RS_OK;
+    std::vector<uint64_t> sizes(n);
+    for (size_t i = 0; i < n; i++) sizes[i] = stripes[order[i]].shard_size;
+    std::vector<EncListLaunch> plan;
+    if (!make_encode_list_plan(sizes.data(), n, encode_list_wg_bytes(c->bits, c->logm, false),
+                               encode_list_wg_bytes(c->bits, c->logm, true), unit_width_override(), kEncListNarrowBelow,
+                               kEncListMaxStripes, kEncListMaxWg, plan))
+        return RS_ERR_INVALID_ARG;
+    for (const EncListLaunch &l : plan) {
+        const size_t nl = l.z1 - l.z0, o_pre = align256(nl * sizeof(EncListStripe));
+        int slot = 0;
+        uint8_t *h = nullptr, *g = nullptr;
+        if (int e = ring_acquire(c, o_pre + 4 * (nl + 1), slot, h, g)) return e;
+        EncListStripe *hd = (EncListStripe *)h;
+        for (size_t i = 0; i < nl; i++) {
+            const rs_stripe &st = stripes[order[l.z0 + i]];
+            hd[i] = EncListStripe{st.base, st.row_stride, st.shard_size};
+        }
+        write_encode_list_prefix(sizes.data(), l, (uint32_t *)(h + o_pre));
+        HIP_TRY(hipMemcpyAsync(g, h, o_pre + 4 * (nl + 1), hipMemcpyHostToDevice, s));
+        EncodeListArgs a{};
+        a.stripes = (const EncListStripe *)g;
+        a.first_wg = (const uint32_t *)(g + o_pre);
+        a.nstripes = (uint32_t)nl;
+        a.nwg = (uint32_t)l.nwg;
+        a.wg_bytes = l.wg_bytes;
+        a.k = c->k;
+        a.p = c->p;
+        a.nchunks = c->nchunks;
+        a.tw_ifft = c->tw_ifft.p;
+        a.tw_fft = c->tw_fft.p;
+        a.mismatch = mismatch ? mismatch + l.z0 : nullptr;
+        HIP_TRY(launch_encode_reg_list(c->bits, c->logm, mismatch != nullptr, a, s));
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+    }
+    return RS_OK;
+}
+
+// Largest shard size the automatic routing hands to the list kernel where a
+// stripe alone takes the bit-sliced (m = 32, m = 16) or the split kernel: the
+// largest measured size at which the list kernel was faster
+// (profiles/encode_list_c2.txt).  UINT64_MAX: the geometry
+// has the register kernel only (GF(2^8), GF(2^16) m <= 2).  Host only: the
+// split kernel serves every GF(2^16) codec with m = 4..32 (plan_encode_host).
+uint64_t encode_list_max(const rs_codec *c) {
+    if (c->bits != 16 || c->logm < 2 || c->logm > kMaxRegLogM) return UINT64_MAX;
+    if (c->bs_ok) return c->logm == 5 ? RS_ENCODE_LIST_MAX_BS32 : RS_ENCODE_LIST_MAX_BS16;
+    return RS_ENCODE_LIST_MAX_SPLIT;
+}
+// Does the automatic / forced routing give a stripe of this size a launch of its own?
+bool encode_list_own(const rs_codec *c, uint64_t shard_size) {
+    const int knob = g_path_enc_list.load(std::memory_order_relaxed);
+    if (c->logm > kMaxRegLogM || knob == 0) return true;
+    return knob < 0 && shard_size > encode_list_max(c);
+}
+
+// rs_encode_dev_list (verdict == ok == nullptr) and rs_verify_dev_list after their argument checks.
+int encode_list_call(rs_codec *c, const rs_stripe *stripes, size_t n, int8_t *verdict, int *ok, void *stream) {
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    const bool verify = ok != nullptr;
+    std::vector<uint32_t> order, own;  // through the list kernel / one encode_device each
+    for (size_t z = 0; z < n; z++) (encode_list_own(c, stripes[z].shard_size) ? own : order).push_back((uint32_t)z);
+    int *dflags = nullptr, *hflags = nullptr;
+    // the codec scratch: the verify's mismatch words, and the work rows of a
+    // multi-pass encode; the list kernel and the strided launches of the
+    // other encodes touch none (encode_uses_scratch)
+    const bool scr = verify || (!own.empty() && !enc_lds_ok(c));
+    if (scr)
+        if (int e = scratch_acquire(c, s)) return e;
+    if (verify) {
+        if (int e = scrub_buffers(c, (int)n)) return e;
+        dflags = (int *)(c->scrub_dev.p + scrub_head(c));
+        hflags = (int *)(c->scrub_host.p + scrub_head(c) + 256);
+        HIP_TRY(hipMemsetAsync(dflags, 0, 4 * n, s));
+    }
+    // mismatch words: the list's stripes in list order, then the others
+    if (int e = encode_list_launches(c, stripes, order, dflags, s)) return e;
+    for (size_t i = 0; i < own.size(); i++) {
+        const rs_stripe &st = stripes[own[i]];
+        const RowSet data{nullptr, st.base, st.row_stride}, par{nullptr, st.base + (size_t)c->k * st.row_stride, st.row_stride};
+        if (int e = encode_device(c, data, par, st.shard_size, 0, 1, verify ? dflags + order.size() + i : nullptr, s))
+            return e;
+    }
+    if (scr)
+        if (int e = scratch_release(c, s)) return e;
+    if (!verify) return dc.finish(RS_OK);
+    HIP_TRY(hipMemcpyAsync(hflags, dflags, 4 * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    int all = 1;
+    for (size_t i = 0; i < n; i++) {
+        const int good = ((volatile int *)hflags)[i] == 0;
+        if (verdict) verdict[i < order.size() ? order[i] : own[i - order.size()]] = (int8_t)good;
+        all &= good;
+    }
+    *ok = all;
     return RS_OK;
 }
 
@@ -4394,6 +4510,77 @@ int rs_verify_dev_batch(rs_codec *c, uint8_t *base, size_t row_stride, size_t st
     return encode_dev_call(c, nullptr, base, row_stride, stripe_stride, nstripes, S, ok, stream);
 }
 
+// ---- A list of stripes of different sizes (beyond the reference; rs_mi355x.h).
+// The header's error order: each rule over the whole list before the next.
+static int encode_list_check(const rs_codec *c, const rs_stripe *st, size_t n) {
+    if (!c || !st || c->multi || n > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
+    for (size_t z = 0; z < n; z++)
+        if (!st[z].base) return RS_ERR_INVALID_ARG;
+    for (size_t z = 0; z < n; z++)
+        if (st[z].shard_size == 0) return RS_ERR_SHARD_NO_DATA;
+    for (size_t z = 0; z < n; z++)
+        if (st[z].shard_size % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    for (size_t z = 0; z < n; z++)
+        if (st[z].row_stride < st[z].shard_size) return RS_ERR_INVALID_ARG;
+    for (size_t z = 0; z < n; z++)
+        if (!encode_list_fits(c->k, st[z].row_stride, st[z].shard_size)) return RS_ERR_INVALID_ARG;
+    if (!c->enc_ok) return RS_ERR_PANIC;
+    return RS_OK;
+}
+
+int rs_encode_dev_list(rs_codec *c, const rs_stripe *stripes, size_t nstripes, void *stream) {
+    if (int e = encode_list_check(c, stripes, nstripes)) return e;
+    if (nstripes == 0) return RS_OK;
+    return encode_list_call(c, stripes, nstripes, nullptr, nullptr, stream);
+}
+
+int rs_verify_dev_list(rs_codec *c, const rs_stripe *stripes, size_t nstripes, int8_t *verdict, int *ok, void *stream) {
+    if (!ok) return RS_ERR_INVALID_ARG;
+    *ok = 0;
+    if (int e = encode_list_check(c, stripes, nstripes)) return e;
+    if (nstripes == 0) {
+        *ok = 1;
+        return RS_OK;
+    }
+    return encode_list_call(c, stripes, nstripes, verdict, ok, stream);
+}
+
+int rs_debug_encode_list_fits(int k, size_t row_stride, size_t S) { return encode_list_fits(k, row_stride, S) ? 1 : 0; }
+
+int rs_debug_encode_list_own(const rs_codec *c, size_t S) {
+    if (!c || c->multi || !c->enc_ok) return -1;
+    return encode_list_own(c, S) ? 1 : 0;
+}
+
+int rs_debug_encode_list_plan(int bits, int p, int unit_width, const size_t *sizes, size_t nstripes, size_t max_stripes,
+                              int *nlaunches, uint64_t *launches, uint32_t *first_wg) {
+    if ((bits != 8 && bits != 16) || p <= 0 || p > 32 || unit_width < -1 || unit_width > 1 || !sizes || !nlaunches)
+        return RS_ERR_INVALID_ARG;
+    const int logm = ilog2(ceil_pow2(p));
+    std::vector<uint64_t> sz(sizes, sizes + nstripes);
+    for (uint64_t S : sz)
+        if (!S || S % 64 || S >= (1ull << 32)) return RS_ERR_INVALID_ARG;
+    std::vector<EncListLaunch> plan;
+    if (!make_encode_list_plan(sz.data(), nstripes, encode_list_wg_bytes(bits, logm, false),
+                               encode_list_wg_bytes(bits, logm, true), unit_width, kEncListNarrowBelow,
+                               max_stripes ? max_stripes : kEncListMaxStripes, kEncListMaxWg, plan))
+        return RS_ERR_INVALID_ARG;
+    *nlaunches = (int)plan.size();
+    for (const EncListLaunch &l : plan) {
+        if (launches) {
+            *launches++ = l.z0;
+            *launches++ = l.z1;
+            *launches++ = l.wg_bytes;
+            *launches++ = l.nwg;
+        }
+        if (first_wg) {
+            write_encode_list_prefix(sz.data(), l, first_wg);
+            first_wg += l.z1 - l.z0 + 1;
+        }
+    }
+    return RS_OK;
+}
+
 // ---- Scrub (beyond the reference; rs_mi355x.h).  Every error is decided
 // before the first device call, by rs_verify_dev's / rs_verify_dev_batch's rules.
 int rs_verify_dev_batch_map(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, int nstripes, size_t S,
@@ -5166,6 +5353,7 @@ int rs_debug_set_path(const char *knob, int value) {
     else if (k == "bsdec_grid" && value >= 0) g_path_bsdec_grid = value;
     else if (k == "scrub_batch" && value >= -1 && value <= 1) g_path_scrub_batch = value;
     else if (k == "scrub_chunk" && value >= 0) g_path_scrub_chunk = value;
+    else if (k == "enc_list" && value >= -1 && value <= 1) g_path_enc_list = value;
     else return RS_ERR_INVALID_ARG;
     return RS_OK;
 }

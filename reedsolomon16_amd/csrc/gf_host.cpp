@@ -493,6 +493,46 @@ void write_update_list_descs(const UpdListLaunch &l, size_t g0, size_t g1, const
     }
 }
 
+bool make_encode_list_plan(const uint64_t *sizes, size_t n, uint32_t wide, uint32_t narrow, int unit_width,
+                           uint64_t narrow_below, size_t max_stripes, uint64_t max_wg, std::vector<EncListLaunch> &out) {
+    out.clear();
+    if (!max_stripes || !wide) return false;
+    // the width the cuts are counted in; an automatic launch that turns narrow
+    // has fewer than narrow_below wide workgroups, so at most 4x that many
+    const uint32_t cut = unit_width == 1 && narrow ? narrow : wide;
+    auto wgs = [](uint64_t S, uint32_t w) { return (S + w - 1) / w; };
+    for (size_t z = 0; z < n;) {
+        EncListLaunch l{z, z, cut, 0};
+        while (l.z1 < n && l.z1 - l.z0 < max_stripes) {
+            const uint64_t w = wgs(sizes[l.z1], cut);
+            if (w > max_wg) return false;
+            if (l.nwg + w > max_wg) break;
+            l.nwg += w;
+            l.z1++;
+        }
+        if (unit_width < 0 && narrow && l.nwg < narrow_below) {
+            uint64_t nn = 0;
+            for (size_t i = l.z0; i < l.z1; i++) nn += wgs(sizes[i], narrow);
+            if (nn <= max_wg) {  // else the launch stays wide
+                l.wg_bytes = narrow;
+                l.nwg = nn;
+            }
+        }
+        out.push_back(l);
+        z = l.z1;
+    }
+    return true;
+}
+
+void write_encode_list_prefix(const uint64_t *sizes, const EncListLaunch &l, uint32_t *first_wg) {
+    uint64_t at = 0;
+    for (size_t i = l.z0; i < l.z1; i++) {
+        *first_wg++ = (uint32_t)at;
+        at += (sizes[i] + l.wg_bytes - 1) / l.wg_bytes;
+    }
+    *first_wg = (uint32_t)at;
+}
+
 bool decode_schedule(const Field &F, int k, int p, std::vector<uint32_t> &ifft, std::vector<uint32_t> &fft) {
     const int m = ceil_pow2(p);
     if ((long)m + k > (long)F.order) return false;  // the Go code panics (see error_locators)

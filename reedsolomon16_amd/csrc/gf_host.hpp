@@ -176,6 +176,57 @@ inline size_t upd_list_desc_dwords(int nt) { return 1 + 3 * (size_t)nt; }
 void write_update_list_descs(const UpdListLaunch &l, size_t g0, size_t g1, const int *idx_of, const int *cols, int ncols,
                              uint32_t *out);
 
+// ---- A list of stripes of different sizes in one launch (rs_encode_dev_list,
+// kernels.hip k_encode_reg_list).
+// Bytes of a row one workgroup of the register encode covers (256 lanes, one
+// unit each) for m = 2^logm <= 32: the wide unit, or the narrow one GF(2^8)
+// has at m = 4..16; 0 where there is no such kernel.
+constexpr uint32_t encode_list_wg_bytes(int bits, int logm, bool narrow) {
+    if (logm < 0 || logm > 5) return 0;
+    if (bits == 16) return narrow ? 0 : logm <= 3 ? 8192 : logm == 4 ? 4096 : 2048;
+    if (bits != 8) return 0;
+    if (narrow) return logm >= 2 && logm <= 4 ? 1024 : 0;
+    return logm <= 4 ? 4096 : 2048;
+}
+// The stripe's data rows fit the kernel's 32-bit buffer descriptor:
+// (k-1) * row_stride + shard_size < 2^32 (and the sum does not wrap).
+inline bool encode_list_fits(int k, uint64_t row_stride, uint64_t shard_size) {
+    constexpr uint64_t lim = 1ull << 32;
+    if (k < 1 || shard_size >= lim) return false;
+    if (k == 1) return true;
+    return row_stride <= (lim - 1 - shard_size) / (uint64_t)(k - 1);
+}
+constexpr uint64_t kEncListMaxWg = (1ull << 31) - 1;  // workgroups per launch (a one-dimensional grid)
+// One launch: stripes [z0, z1) of the list in workgroups of wg_bytes, nwg in all.
+struct EncListLaunch {
+    size_t z0, z1;
+    uint32_t wg_bytes;
+    uint64_t nwg;
+};
+// Cuts sizes[0..n) (each > 0, a multiple of 64, < 2^32), in order, into
+// launches of at most max_stripes stripes and at most max_wg workgroups.
+// unit_width: -1 automatic (a launch whose wide workgroups number fewer than
+// narrow_below takes the narrow unit where there is one), 0 wide, 1 narrow
+// where there is one.  wide / narrow: encode_list_wg_bytes of the geometry
+// (narrow == 0: none).  False when max_stripes == 0 or a single stripe
+// exceeds max_wg; the plan is then unspecified.
+bool make_encode_list_plan(const uint64_t *sizes, size_t n, uint32_t wide, uint32_t narrow, int unit_width,
+                           uint64_t narrow_below, size_t max_stripes, uint64_t max_wg, std::vector<EncListLaunch> &out);
+// first_wg[0 .. z1 - z0] of a launch: first_wg[i] = workgroups of the
+// launch's stripes before its i-th, first_wg[z1 - z0] = nwg.
+void write_encode_list_prefix(const uint64_t *sizes, const EncListLaunch &l, uint32_t *first_wg);
+// The kernel's search: the i in [0, n) with first_wg[i] <= wg < first_wg[i + 1]
+// (first_wg strictly ascending, wg < first_wg[n]).
+inline uint32_t encode_list_find(const uint32_t *first_wg, uint32_t n, uint32_t wg) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (first_wg[mid] <= wg) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // Decoder schedules over n = ceilPow2(m+k) rows (leopard16.go:573-657).
 bool decode_schedule(const Field &F, int k, int p, std::vector<uint32_t> &ifft_logs, std::vector<uint32_t> &fft_logs);
 

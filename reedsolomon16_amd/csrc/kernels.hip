@@ -668,6 +668,150 @@ __global__ void __launch_bounds__(256, 2) k_encode_reg(EncodeArgs a) {
     }
 }
 
+// ---------------------------------------------------------------- register encode over a list of stripes
+// k_encode_reg's strided form over stripes of different sizes, each in a
+// buffer of its own (kernels.hpp EncodeListArgs, rs_encode_dev_list).  A copy:
+// k_encode_reg and its instantiations keep their registers.  The grid is
+// one-dimensional over the column blocks of all stripes; a workgroup finds its
+// stripe by a binary search over the prefix first_wg and reads the stripe's
+// descriptor.  Prefix and descriptors are the same for the whole workgroup and
+// read-only for the launch: scalar loads through the constant address space
+// (as k_decode_rows_pat reads its list entry), SGPRs and no VGPRs.  A
+// workgroup never straddles two stripes: the waves of a stripe's last
+// workgroup past the row end are dead and still join the barriers.  The data
+// rows go through a 32-bit buffer descriptor over the stripe's data span,
+// which the host keeps below 2^32 (gf_host.hpp encode_list_fits); the parity
+// rows through 64-bit pointers.
+typedef __attribute__((address_space(4))) const EncListStripe enc_cstripe_t;
+
+template <class F, int LOGM, bool VERIFY>
+__global__ void __launch_bounds__(256, 2) k_encode_reg_list(EncodeListArgs a) {
+    constexpr int M = 1 << LOGM;
+    constexpr int ROWB = F::ROWB;          // bytes of a row covered by one wave
+    constexpr int PPR = ROWB / 16;         // 16-byte pieces per row
+    constexpr int NDMA = M * PPR / 64;     // DMA wave-instructions per chunk
+    static_assert(NDMA * 64 == M * PPR, "chunk must be whole DMA instructions");
+    constexpr int IS = ifft_slot_count(LOGM), FS = fft_slot_count(LOGM);
+    constexpr int TB = F::TWD * 4;                      // bytes per twiddle table
+    constexpr int TABB = ((IS > FS ? IS : FS) * TB + 15) / 16 * 16;  // bytes per table buffer
+    typedef typename F::Vec V;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    __shared__ __attribute__((aligned(16))) uint8_t lds[4 * M * ROWB + 2 * TABB];
+    uint8_t *ltab = lds + 4 * M * ROWB;
+
+    // the stripe z with first_wg[z] <= blockIdx.x < first_wg[z + 1] (gf_host.hpp encode_list_find)
+    cu32_t *fw = (cu32_t *)a.first_wg;
+    const uint32_t wg = blockIdx.x;
+    uint32_t z = 0, zh = a.nstripes;
+    while (zh - z > 1) {
+        const uint32_t mid = z + (zh - z) / 2;
+        if (fw[mid] <= wg) z = mid;
+        else zh = mid;
+    }
+    enc_cstripe_t &d = ((enc_cstripe_t *)a.stripes)[z];
+    uint8_t *const sbase = d.base;
+    const uint64_t stride = d.row_stride, shard_size = d.shard_size;
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform (SGPR)
+    const uint64_t units = F::units(shard_size);
+    const uint64_t u0 = (uint64_t)(wg - fw[z]) * 256 + wave * 64;
+    const bool wave_live = u0 < units;  // waves past the row end still join the barriers
+    const uint64_t u = u0 + lane;
+    const uint64_t span = F::span_off(u0);
+    uint8_t *img = lds + wave * (M * ROWB);
+
+    // Buffer descriptor over this stripe's data rows: (k-1)*stride + shard_size < 2^32 (checked by the host).
+    const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)sbase, 0, (int)(uint32_t)((uint64_t)(a.k - 1) * stride + shard_size), 0x00020000);
+    // One DMA wave-instruction (piece group j) of chunk c's rows: rows past the
+    // chunk's count and pieces past the row end are zero-filled.  The staging
+    // lambdas are always inlined: left to the inliner, F16<4> at m = 8 kept
+    // stage_one as a call, with its captures and the arguments in scratch.
+    auto stage_one = [&](int c, int j) __attribute__((always_inline)) {
+        const int row0 = c * M, cnt = a.k - row0;
+        const int P = j * 64 + lane;
+        const int r = P / PPR;
+        const uint64_t go = span + F::piece_goff(P % PPR);
+        if (wave_live && r < cnt && go < shard_size) {
+            const uint32_t voff = (uint32_t)((uint64_t)(row0 + r) * stride + go);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(drsrc, (lvoid_t *)(img + j * 1024), 16, voff, 0, 0, 0);
+        } else {
+            *(__attribute__((address_space(3))) u32x4 *)(img + j * 1024 + lane * 16) = u32x4{0, 0, 0, 0};
+        }
+    };
+    auto stage = [&](int c) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < NDMA; j++) stage_one(c, j);
+    };
+
+    // Stage `nslot` twiddle tables into table buffer b (waves split the pieces).
+    auto stage_tab = [&](const uint32_t *src, int nslot, int b) __attribute__((always_inline)) {
+        const int npieces = nslot * TB / 16;
+        const int P = wave * 64 + lane;
+        const __amdgpu_buffer_rsrc_t trsrc = __builtin_amdgcn_make_buffer_rsrc((void *)src, 0, npieces * 16, 0x00020000);
+        for (int base = 0; base < npieces; base += 256) {
+            if (base + P < npieces)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(trsrc, (lvoid_t *)(ltab + b * TABB + base * 16 + wave * 1024),
+                                                         16, (base + P) * 16, 0, 0, 0);
+        }
+    };
+
+    V acc[M];
+    stage(0);
+    stage_tab(a.tw_ifft, IS, 0);
+    for (int c = 0; c < a.nchunks; ++c) {
+        wait_vm0();  // this wave's DMAs for chunk c have landed
+        __syncthreads();  // every wave's table pieces landed; buffer (c+1)&1 is no longer read
+        V cur[M];
+#pragma unroll
+        for (int r = 0; r < M; r++) cur[r] = F::lds_load(img + r * ROWB, lane);
+        wait_lgkm0();  // reads done before the image is overwritten
+        const bool more = c + 1 < a.nchunks;
+        if (more) stage_tab(a.tw_ifft + (uint64_t)(c + 1) * IS * F::TWD, IS, (c + 1) & 1);
+        else stage_tab(a.tw_fft, FS, (c + 1) & 1);
+        // the next chunk's row DMAs spread through the IFFT, as in k_encode_reg
+        constexpr int NOPS = ifft_op_count<LOGM>();
+        constexpr int SPREAD = NOPS >= NDMA ? NOPS / NDMA : 0;
+        if (!SPREAD && more) stage(c + 1);
+        ifft_reg<F, LOGM>(cur, vgpr_lds_addr(ltab + (c & 1) * TABB), [&](int i) {
+            if (SPREAD && i % SPREAD == 0 && i / SPREAD < NDMA && more) stage_one(c + 1, i / SPREAD);
+        });
+        if (c == 0) {
+#pragma unroll
+            for (int r = 0; r < M; r++) acc[r] = cur[r];
+        } else {
+#pragma unroll
+            for (int r = 0; r < M; r++) F::xor_into(acc[r], cur[r]);
+        }
+    }
+    wait_vm0();
+    __syncthreads();
+    fft_reg<F, LOGM>(acc, vgpr_lds_addr(ltab + (a.nchunks & 1) * TABB));
+    if (!wave_live || u >= units) return;
+    uint8_t *const par = sbase + (uint64_t)a.k * stride;
+    if constexpr (VERIFY) {
+        uint32_t bad = 0;
+#pragma unroll
+        for (int r = 0; r < M; r++)
+            if (r < a.p) bad |= F::diff(acc[r], F::load(par + (uint64_t)r * stride, u));
+        flag_mismatch(a.mismatch + z, bad != 0);
+    } else {
+#pragma unroll
+        for (int r = 0; r < M; r++)
+            if (r < a.p) F::store(par + (uint64_t)r * stride, u, acc[r]);
+    }
+}
+
+template <class F, int LOGM>
+hipError_t enc_reg_list(bool verify, const EncodeListArgs &a, hipStream_t s) {
+    constexpr uint32_t kWg = 256 * (F::SYM16 ? 8 : 4) * F::W;  // bytes of a row per workgroup
+    if (a.wg_bytes != kWg) return hipErrorInvalidValue;
+    if (verify) hipLaunchKernelGGL((k_encode_reg_list<F, LOGM, true>), dim3(a.nwg), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_encode_reg_list<F, LOGM, false>), dim3(a.nwg), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- half-wave split encode (GF(2^16), 4 <= m <= 32)
 // Same algorithm as k_encode_reg, but the M rows of a column unit are split
 // over lanes L and L+32 (schedule.hpp, SplitSched): per lane M/2 rows of the
@@ -1952,6 +2096,35 @@ hipError_t launch_encode_reg(int bits, int logm, bool verify, const EncodeArgs &
             case 3: return narrow ? enc_reg<F8<1>, 3>(verify, a, s) : enc_reg<F8<4>, 3>(verify, a, s);
             case 4: return narrow ? enc_reg<F8<1>, 4>(verify, a, s) : enc_reg<F8<4>, 4>(verify, a, s);
             case 5: return enc_reg<F8<2>, 5>(verify, a, s);
+        }
+    }
+    return hipErrorInvalidValue;
+}
+
+// launch_encode_reg's (field, log2 m) table; the unit width comes with the
+// launch (gf_host.hpp make_encode_list_plan applies pick_narrow's rule to the
+// launch's total workgroup count).
+hipError_t launch_encode_reg_list(int bits, int logm, bool verify, const EncodeListArgs &a, hipStream_t s) {
+    if (!a.stripes || !a.first_wg || !a.nstripes || !a.nwg || a.nwg > 0x7fffffffu) return hipErrorInvalidValue;
+    if (verify && !a.mismatch) return hipErrorInvalidValue;
+    if (bits == 16) {
+        switch (logm) {
+            case 0: return enc_reg_list<F16<4>, 0>(verify, a, s);
+            case 1: return enc_reg_list<F16<4>, 1>(verify, a, s);
+            case 2: return enc_reg_list<F16<4>, 2>(verify, a, s);
+            case 3: return enc_reg_list<F16<4>, 3>(verify, a, s);
+            case 4: return enc_reg_list<F16<2>, 4>(verify, a, s);
+            case 5: return enc_reg_list<F16<1>, 5>(verify, a, s);
+        }
+    } else {
+        const bool narrow = a.wg_bytes == 1024;
+        switch (logm) {
+            case 0: return enc_reg_list<F8<4>, 0>(verify, a, s);
+            case 1: return enc_reg_list<F8<4>, 1>(verify, a, s);
+            case 2: return narrow ? enc_reg_list<F8<1>, 2>(verify, a, s) : enc_reg_list<F8<4>, 2>(verify, a, s);
+            case 3: return narrow ? enc_reg_list<F8<1>, 3>(verify, a, s) : enc_reg_list<F8<4>, 3>(verify, a, s);
+            case 4: return narrow ? enc_reg_list<F8<1>, 4>(verify, a, s) : enc_reg_list<F8<4>, 4>(verify, a, s);
+            case 5: return enc_reg_list<F8<2>, 5>(verify, a, s);
         }
     }
     return hipErrorInvalidValue;

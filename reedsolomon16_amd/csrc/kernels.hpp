@@ -79,6 +79,27 @@ hipError_t launch_encode_reg(int bits, int logm, bool verify, const EncodeArgs &
 // split_image_dwords(logm, true) dwords (codec.cpp lays them out from
 // schedule.hpp's EncodeSplit<logm>).
 hipError_t launch_encode_split(int logm, bool verify, const EncodeArgs &a, hipStream_t s);
+// The register encode over a list of stripes of different sizes, each in a
+// buffer of its own (rs_encode_dev_list; k_encode_reg_list): a one-dimensional
+// grid over the column blocks of all stripes.  Workgroup w serves the stripe z
+// with first_wg[z] <= w < first_wg[z + 1] (gf_host.hpp
+// write_encode_list_prefix, encode_list_find) and its block w - first_wg[z].
+struct EncListStripe {
+    uint8_t *base;        // shard i at base + i * row_stride: k data rows, then p parity rows
+    uint64_t row_stride;  // (k-1) * row_stride + shard_size < 2^32 (gf_host.hpp encode_list_fits)
+    uint64_t shard_size;  // > 0, a multiple of 64
+};
+struct EncodeListArgs {
+    const EncListStripe *stripes;  // device array, nstripes descriptors
+    const uint32_t *first_wg;      // device array, nstripes + 1 entries, strictly ascending from 0
+    uint32_t nstripes, nwg;        // nwg == first_wg[nstripes] < 2^31
+    uint32_t wg_bytes;             // gf_host.hpp encode_list_wg_bytes of the launch's unit
+    int k, p, nchunks;
+    const uint32_t *tw_ifft, *tw_fft;  // as EncodeArgs
+    int *mismatch;                 // verify: word z is set when stripe z's parity differs (cleared by the caller)
+};
+// logm in [0, 5]; hipErrorInvalidValue when wg_bytes is no unit of (bits, logm).
+hipError_t launch_encode_reg_list(int bits, int logm, bool verify, const EncodeListArgs &a, hipStream_t s);
 // Name of the register-kernel variant (for diagnostics / profiles).
 const char *encode_reg_name(int bits, int logm);
 

@@ -499,7 +499,8 @@ int rs_verify_dev_batch(rs_codec *codec, uint8_t *d_base, size_t row_stride, siz
 
 /* ---------------- A list of stripes of different sizes (beyond the reference) ----------------
  * The batch calls above take one shard_size and one base + z*stripe_stride
- * layout for the whole slab.  These two take a host array of nstripes
+ * layout for the whole slab.  These two (and rs_reconstruct_rows_dev_list
+ * below) take a host array of nstripes
  * descriptors, one per stripe, each with a buffer and a size of its own: shard
  * i of stripe z lies at stripes[z].base + i*row_stride, data rows 0..k-1 and
  * parity rows k..k+p-1 as in rs_encode_dev_batch.  The small-object write path
@@ -562,6 +563,56 @@ typedef struct {
 int rs_encode_dev_list(rs_codec *codec, const rs_stripe *stripes /* HOST, nstripes */, size_t nstripes, void *stream);
 int rs_verify_dev_list(rs_codec *codec, const rs_stripe *stripes /* HOST, nstripes */, size_t nstripes,
                        int8_t *verdict /* HOST, nstripes, may be NULL */, int *ok, void *stream);
+
+/* ---------------- Degraded read of such a list (beyond the reference) ----------------
+ * rs_reconstruct_rows_dev_batch_patterns over a list of stripes of different
+ * sizes: the read path of the store whose write path rs_encode_dev_list
+ * serves.  Stripe z is stripes[z] (shard i at base + i*row_stride, shard_size
+ * bytes a shard) and uses row pattern_of[z] of the two tables, as in
+ * rs_reconstruct_rows_dev_batch_patterns: it rebuilds exactly its rows with
+ * !present[i] && required[i] (required == NULL: every missing row).  Per
+ * stripe the result is bit for bit what rs_reconstruct_rows_dev_batch writes
+ * for that stripe alone (nstripes = 1, its base, row stride, shard_size and
+ * pair): the locators are the exact ones of the pattern, and the
+ * reference-keyed GF(2^8) inversion cache is neither read nor stored.  No
+ * byte outside the rebuilt rows' shard_size bytes is written; a stripe with
+ * nothing to rebuild is not touched.  The list and the three arrays are read
+ * before the call returns and may be freed then.  Stream semantics are those
+ * of rs_reconstruct_rows_dev_batch_patterns: asynchronous on a caller stream
+ * or RS_NULL_STREAM, complete on return for NULL.  Stripes that overlap in
+ * memory are the caller's error and are not checked.
+ *
+ * Errors, decided before any device call, in this order, each rule over the
+ * whole list and the whole table before the next:
+ *   1. NULL codec, stripes, present or pattern_of, a multi-device codec, more
+ *      than INT32_MAX stripes, npatterns == 0 or > 65536, a pattern_of[z] >=
+ *      npatterns, or a stripe with a NULL base: RS_ERR_INVALID_ARG;
+ *   2. any shard_size == 0, or a table row with no shard present:
+ *      RS_ERR_SHARD_NO_DATA;
+ *   3. a table row with fewer than k shards present, whether or not a stripe
+ *      names it: RS_ERR_TOO_FEW_SHARDS;
+ *   4. any shard_size not a multiple of 64: RS_ERR_INVALID_SHARD_SIZE;
+ *   5. any row_stride < shard_size: RS_ERR_INVALID_ARG (with it a shard_size
+ *      of 2^42 bytes or more, which no device holds and no grid covers);
+ *   6. RS_ERR_PANIC where the reference's reconstruct of the geometry panics.
+ * After these, nstripes == 0 or a list with nothing to rebuild returns RS_OK
+ * with nothing launched.  There is no counterpart of rs_encode_dev_list's
+ * rule 5: the decode kernel addresses every row with 64-bit arithmetic, so
+ * the rows of a stripe may lie 4 GiB and more apart.
+ *
+ * Routing.  The tier of a stripe is chosen as
+ * rs_reconstruct_rows_dev_batch_patterns chooses it (rs_debug_set_path
+ * "rows_direct"), but that at n = 256 the automatic choice takes up to 8
+ * wanted rows (measured: profiles/rows_list_c2.txt).  Direct stripes share
+ * launches of the list kernel, one per
+ * wanted-row count: one flat grid over the column blocks of all of them.
+ * Every other stripe (more wanted rows than the direct tier takes, n > 2048,
+ * multi-pass codecs) runs on the same stream what it would run alone, one
+ * launch sequence per stripe: right, not fast. */
+int rs_reconstruct_rows_dev_list(rs_codec *codec, const rs_stripe *stripes /* HOST, nstripes */, size_t nstripes,
+                                 const uint8_t *present /* HOST, npatterns x (k+p) */,
+                                 const uint8_t *required /* HOST, npatterns x (k+p), or NULL: every missing row */,
+                                 size_t npatterns, const uint32_t *pattern_of /* HOST, nstripes */, void *stream);
 
 /* Name of the kernel path the codec uses for encode ("reg-m32", "lds", "multipass", ...). */
 const char *rs_encode_path(const rs_codec *codec);
@@ -1049,6 +1100,26 @@ int rs_debug_encode_list_own(const rs_codec *codec, size_t shard_size);
 int rs_debug_encode_list_plan(int field_bits, int parity_shards, int unit_width, const size_t *sizes, size_t nstripes,
                               size_t max_stripes, int *nlaunches, uint64_t *launches, uint32_t *first_wg);
 
+/* The launch plan of rs_reconstruct_rows_dev_list's list kernel for nentries
+ * (stripe, descriptor) entries: sizes[i] bytes per shard and wanted[i] rows
+ * to rebuild (1..8) each, under unit_width -1 / 0 / 1 as the "unit_width" knob
+ * below.  The entries are cut, in order, into ranges of at most max_entries
+ * entries (0: the library's ring-slot limit, which *entry_limit, if not NULL,
+ * receives in every case); a range has one launch per wanted-row count that
+ * occurs in it, over its entries of that count in order, each of fewer than
+ * 2^31 workgroups.  *nlaunches = the number of launches; launches (may be
+ * NULL) gets nine values per launch: the range's first entry, one past its
+ * last, the wanted-row count, the launch's entries, bytes of a row per
+ * workgroup, workgroups, the offsets of the launch's entries and of its prefix
+ * in the range's ring slot, and the slot bytes of the range; first_wg (may be
+ * NULL) gets per launch its prefix of (entries + 1) words: word i =
+ * workgroups of the launch's entries before its i-th.  RS_ERR_INVALID_ARG for
+ * a size that is 0 or no multiple of 64, a wanted count outside 1..8, or an
+ * entry of 2^31 workgroups or more.  Host only, no memory behind the sizes. */
+int rs_debug_rows_list_plan(int field_bits, int unit_width, const size_t *sizes, const int *wanted, size_t nentries,
+                            size_t max_entries, size_t *entry_limit, int *nlaunches, uint64_t *launches,
+                            uint32_t *first_wg);
+
 /* Test-only kernel-path overrides (process-wide), so the parity tests can run
  * the variants other geometries select on the same small inputs:
  *   "bs" 0/1          bit-sliced GF(2^16) encode off / on (default 1; read by rs_new),
@@ -1082,7 +1153,9 @@ int rs_debug_encode_list_plan(int field_bits, int parity_shards, int unit_width,
  *   "scrub_chunk" >= 0  listed stripes per pass of rs_locate_dev_batch, 0 = automatic (default 0),
  *   "enc_list" -1/0/1  rs_encode_dev_list / rs_verify_dev_list: the list kernel by the measured
  *                     size thresholds (-1, default), never (0: one launch sequence per stripe),
- *                     or always where m <= 32 admits it (1).
+ *                     or always where m <= 32 admits it (1),
+ *   "rows_list" -1/0  rs_reconstruct_rows_dev_list: direct stripes through the list kernel
+ *                     (-1, default) or every stripe on its own (0).
  * Returns RS_ERR_INVALID_ARG for an unknown knob or value.  Host only. */
 int rs_debug_set_path(const char *knob, int value);
 

@@ -16,7 +16,7 @@ _lib = None
 
 
 class Stripe(C.Structure):
-    """rs_stripe: one entry of rs_encode_dev_list's / rs_verify_dev_list's list."""
+    """rs_stripe: one entry of the list of rs_encode_dev_list, rs_verify_dev_list and rs_reconstruct_rows_dev_list."""
 
     _fields_ = [("base", C.c_void_p), ("row_stride", C.c_size_t), ("shard_size", C.c_size_t)]
 
@@ -121,11 +121,13 @@ def lib() -> C.CDLL:
     L.rs_debug_encode_list_fits.argtypes = [i32, sz, sz]
     L.rs_debug_encode_list_own.argtypes = [vp, sz]
     L.rs_debug_encode_list_plan.argtypes = [i32, i32, i32, P(sz), sz, sz, P(i32), vp, vp]
+    L.rs_reconstruct_rows_dev_list.argtypes = [vp, P(Stripe), sz, P(C.c_uint8), P(C.c_uint8), sz, P(C.c_uint32), vp]
+    L.rs_debug_rows_list_plan.argtypes = [i32, i32, P(sz), P(i32), sz, sz, P(sz), P(i32), vp, vp]
     _lib = L
     return L
 
 
-_PATH_DEFAULTS = {"bs": 1, "sub": 1, "prune": 1, "unit_width": -1, "hp_tiles": 0, "hp_step": 0, "zc": 3, "hp_tune": 1, "rec_half": 0, "dec_lab": 0, "lds_big": 1, "rows_direct": -1, "pat_tier": 0, "bsdec_grid": 0, "scrub_batch": -1, "scrub_chunk": 0, "enc_list": -1}
+_PATH_DEFAULTS = {"bs": 1, "sub": 1, "prune": 1, "unit_width": -1, "hp_tiles": 0, "hp_step": 0, "zc": 3, "hp_tune": 1, "rec_half": 0, "dec_lab": 0, "lds_big": 1, "rows_direct": -1, "pat_tier": 0, "bsdec_grid": 0, "scrub_batch": -1, "scrub_chunk": 0, "enc_list": -1, "rows_list": -1}
 
 
 def set_path(knob: str, value: int) -> None:

@@ -937,6 +937,34 @@ class ReedSolomon:
                                           _stream_handle(stream)))
         return verdict[:len(stripes)].astype(bool)
 
+    def reconstruct_rows_dev_list(self, stripes, patterns, required, pattern_of: Sequence[int], stream=None) -> None:
+        """reconstruct_rows_dev_batch_patterns over a list of stripes of
+        different sizes, each a (k+p, S_z) uint8 CUDA tensor of its own, in
+        shared launches (rs_reconstruct_rows_dev_list): stripe z uses row
+        pattern_of[z] of the [npatterns, k+p] tables `patterns` and `required`
+        and rebuilds its missing and required rows.  required=None: every
+        missing row.  A stripe with nothing to rebuild is left alone."""
+        arr = self._stripe_list(stripes)
+        n = len(stripes)
+        table = np.ascontiguousarray(np.asarray(patterns, dtype=bool).astype(np.uint8))
+        if table.ndim != 2 or table.shape[1] != self.total_shards():
+            raise ErrTooFewShards("patterns must have %d flags per row" % self.total_shards())
+        req = None
+        if required is not None:
+            req = np.ascontiguousarray(np.asarray(required, dtype=bool).astype(np.uint8))
+            if req.shape != table.shape:
+                raise ErrTooFewShards("required must have the shape of patterns")
+        of = np.ascontiguousarray(np.asarray(pattern_of, dtype=np.int64))
+        if of.shape != (n,):
+            raise TypeError("pattern_of must name one pattern per stripe")
+        if of.size and (of.min() < 0 or of.max() >= 1 << 32):
+            raise ErrInvalidArg("pattern_of entries must be pattern numbers")
+        of = np.concatenate([of, [0]]).astype(np.uint32)  # never an empty (NULL) array
+        _check(self._L.rs_reconstruct_rows_dev_list(
+            self._h, arr, n, table.ctypes.data_as(C.POINTER(C.c_uint8)),
+            req.ctypes.data_as(C.POINTER(C.c_uint8)) if req is not None else None, table.shape[0],
+            of.ctypes.data_as(C.POINTER(C.c_uint32)), _stream_handle(stream)))
+
     # ---------------- incremental update of device rows (beyond the reference:
     # its Leopard codecs reject Update / EncodeIdx; the encode is GF-linear, so
     # a changed data row moves each parity row by one constant times the change)

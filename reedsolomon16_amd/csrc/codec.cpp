@@ -556,7 +556,7 @@ int upload_split(rs_codec *c) {
 // the reconstruct FFT unpruned, the narrow / wide LDS units) on the same small
 // inputs.  Process-wide; read when a codec is created (bs) or at each launch.
 std::atomic<int> g_path_bs{1}, g_path_sub{1}, g_path_prune{1}, g_path_unit_width{-1}, g_path_hp_tiles{0}, g_path_hp_step{0},
-    g_path_zc{3}, g_path_hp_tune{1}, g_path_rec_half{0}, g_path_dec_lab{0}, g_path_lds_big{1}, g_path_rows_direct{-1}, g_path_pat_tier{0}, g_path_bsdec_grid{0}, g_path_scrub_batch{-1}, g_path_scrub_chunk{0}, g_path_enc_list{-1};
+    g_path_zc{3}, g_path_hp_tune{1}, g_path_rec_half{0}, g_path_dec_lab{0}, g_path_lds_big{1}, g_path_rows_direct{-1}, g_path_pat_tier{0}, g_path_bsdec_grid{0}, g_path_scrub_batch{-1}, g_path_scrub_chunk{0}, g_path_enc_list{-1}, g_path_rows_list{-1};
 bool bs_enabled() { return g_path_bs.load(std::memory_order_relaxed) != 0; }
 bool sub_enabled() { return g_path_sub.load(std::memory_order_relaxed) != 0; }
 bool prune_enabled() { return g_path_prune.load(std::memory_order_relaxed) != 0; }
@@ -4036,6 +4036,202 @@ int reconstruct_rows_patterns_call(rs_codec *c, uint8_t *base, size_t row_stride
     return dc.finish(rows_patterns_launch(c, base, row_stride, stripe_stride, nstripes, tb, npat, pattern_of, S, dc.s));
 }
 
+// ---- The same over a list of stripes of different sizes (rs_reconstruct_rows_dev_list)
+static_assert(sizeof(RowsListEntry) == kRowsListEntryBytes && offsetof(RowsListEntry, pat) == sizeof(rs_stripe) &&
+                  kDecGroup == kRowsListGroup,
+              "make_rows_list_plan lays out the kernel's entries");
+// Entries and prefixes of all launches of a range travel through one ring slot.
+constexpr size_t kRowsListSlotBytes = 4u << 20;
+constexpr size_t kRowsListMaxEntries = rows_list_max_entries(kRowsListSlotBytes);
+// launch_decode_rows_patterns's rule (kDecMinBlocks), over a launch's workgroups
+constexpr uint64_t kRowsListNarrowBelow = 1024;
+// A shard size whose workgroups at the narrow unit fit no grid: refused with the strides.
+constexpr uint64_t kRowsListMaxShard = kEncListMaxWg * (uint64_t)rows_list_wg_bytes(8, true);
+
+// The per-stripe tier choice: rows_pat_direct with a threshold of this call's
+// own at n = 256.  A stripe the direct tier does not take runs here on its own,
+// one launch per stripe, where the patterns call shares one launch of the
+// restricted tier among all of them, so the list kernel wins one row later
+// (profiles/rows_list_c2.txt; 128+32, 64 stripes, 32 erasures
+// in 8 rotations, us per call list kernel / loop): t = 8 at 4 KiB 323 / 2029,
+// at 64 KiB 480 / 2132, at 1 MiB 5670 / 6471, each by more than both spreads.
+// t = 9 (two launches of 5 + 4) is unmeasured and stays with the loop, as do
+// the other n with rows_pat_direct's thresholds.
+constexpr int kRowsListDirectAuto256 = 8;
+
+bool rows_list_direct(const rs_codec *c, int t) {
+    if (c->n == 256 && g_path_rows_direct.load(std::memory_order_relaxed) < 0) return c->dec_ok && t <= kRowsListDirectAuto256;
+    return rows_pat_direct(c, t);
+}
+
+// The header's error order: each rule over the whole list and the whole table
+// before the next.  Fills the tables.
+int rows_list_tables(const rs_codec *c, const rs_stripe *st, size_t n, const uint8_t *present, const uint8_t *required,
+                     size_t npat, const uint32_t *pattern_of, RowsPatTables &tb) {
+    if (!c || !st || !present || !pattern_of || c->multi || n > (size_t)INT32_MAX) return RS_ERR_INVALID_ARG;
+    if (npat == 0 || npat > 65536) return RS_ERR_INVALID_ARG;
+    for (size_t z = 0; z < n; z++)
+        if (pattern_of[z] >= npat || !st[z].base) return RS_ERR_INVALID_ARG;
+    const int total = c->total, k = c->k;
+    for (size_t z = 0; z < n; z++)
+        if (st[z].shard_size == 0) return RS_ERR_SHARD_NO_DATA;
+    tb.pres.assign(npat * total, 0), tb.want.assign(npat * total, 0);
+    tb.todo.assign(npat, 0), tb.npres.assign(npat, 0);
+    for (size_t q = 0; q < npat; q++)
+        for (int i = 0; i < total; i++) {
+            const size_t at = q * total + i;
+            tb.pres[at] = present[at] != 0;
+            tb.want[at] = !tb.pres[at] && (!required || required[at]);
+            tb.npres[q] += tb.pres[at];
+            tb.todo[q] += tb.want[at];
+        }
+    for (size_t q = 0; q < npat; q++)
+        if (tb.npres[q] == 0) return RS_ERR_SHARD_NO_DATA;
+    for (size_t q = 0; q < npat; q++)
+        if (tb.npres[q] < k) return RS_ERR_TOO_FEW_SHARDS;
+    for (size_t z = 0; z < n; z++)
+        if (st[z].shard_size % 64) return RS_ERR_INVALID_SHARD_SIZE;
+    for (size_t z = 0; z < n; z++)
+        if (st[z].row_stride < st[z].shard_size || st[z].shard_size > kRowsListMaxShard) return RS_ERR_INVALID_ARG;
+    if ((long)c->m + k > (long)c->F->order) return RS_ERR_PANIC;  // error_locators / decode_schedule: the reference panics
+    return RS_OK;
+}
+
+// One rows set's direct stripes: `direct` holds (stripe of the list, pair of
+// `pairs`).  One ring slot and one launch per wanted-row count for each range
+// of the plan; nothing waits for a kernel.
+int rows_list_launches(rs_codec *c, const rs_stripe *st, const std::vector<RowsSetPair> &pairs,
+                       const std::vector<std::pair<uint32_t, int>> &direct, hipStream_t s) {
+    if (direct.empty()) return RS_OK;
+    RowsSet *rs = nullptr;
+    if (int e = rows_set(c, pairs, &rs)) return e;
+    // a pair of more than kDecGroup rows has several descriptors: its stripe is in several launches
+    std::vector<RowsListEntry> ent;
+    std::vector<uint64_t> sizes;
+    std::vector<int> wanted;
+    for (const auto &zp : direct)
+        for (int d = rs->first_desc[zp.second]; d < rs->first_desc[zp.second + 1]; d++) {
+            const rs_stripe &x = st[zp.first];
+            ent.push_back(RowsListEntry{x.base, x.row_stride, x.shard_size, (uint32_t)d, 0});
+            sizes.push_back(x.shard_size);
+            wanted.push_back(rs->desc_t[d]);
+        }
+    std::vector<RowsListRange> plan;
+    if (!make_rows_list_plan(sizes.data(), wanted.data(), ent.size(), rows_list_wg_bytes(c->bits, false),
+                             rows_list_wg_bytes(c->bits, true), unit_width_override(), kRowsListNarrowBelow,
+                             kRowsListMaxEntries, kEncListMaxWg, plan))
+        return RS_ERR_INVALID_ARG;
+    for (const RowsListRange &r : plan) {
+        int slot = 0;
+        uint8_t *h = nullptr, *g = nullptr;
+        if (int e = ring_acquire(c, r.bytes, slot, h, g)) return e;
+        for (int t = 1; t <= kDecGroup; t++) {
+            if (!r.g[t].n) continue;
+            RowsListEntry *he = (RowsListEntry *)(h + r.g[t].o_ent);
+            for (size_t i = r.e0; i < r.e1; i++)
+                if (wanted[i] == t) *he++ = ent[i];
+            write_rows_list_prefix(sizes.data(), wanted.data(), r, t, (uint32_t *)(h + r.g[t].o_pre));
+        }
+        HIP_TRY(hipMemcpyAsync(g, h, r.bytes, hipMemcpyHostToDevice, s));
+        for (int t = 1; t <= kDecGroup; t++) {
+            if (!r.g[t].n) continue;
+            DecodeRowsListArgs a{};
+            a.list = (const RowsListEntry *)(g + r.g[t].o_ent);
+            a.first_wg = (const uint32_t *)(g + r.g[t].o_pre);
+            a.pat = rs->desc;
+            a.nlist = (uint32_t)r.g[t].n;
+            a.nwg = (uint32_t)r.g[t].nwg;
+            a.wg_bytes = r.g[t].wg_bytes;
+            a.nt = t;
+            HIP_TRY(launch_decode_rows_list(c->bits, a, s));
+        }
+        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
+        c->ring_used[slot] = true;
+    }
+    HIP_TRY(rs->mark_used(s));
+    return RS_OK;
+}
+
+// rs_reconstruct_rows_dev_list after rows_list_tables.
+int rows_list_call(rs_codec *c, const rs_stripe *st, size_t n, const RowsPatTables &tb, size_t npat,
+                   const uint32_t *pattern_of, void *stream) {
+    const int total = c->total;
+    bool any = false;
+    for (size_t z = 0; z < n && !any; z++) any = tb.todo[pattern_of[z]] > 0;
+    if (!any) return RS_OK;
+
+    DevCall dc(c, stream);
+    if (dc.err) return dc.err;
+    const hipStream_t s = dc.s;
+    if (int e = build_decode_plan(c)) return e;
+    if (!c->dec_ok) return RS_ERR_PANIC;
+    const bool list_on = g_path_rows_list.load(std::memory_order_relaxed) != 0;
+    // Equal pairs share a descriptor (as rows_patterns_launch).
+    std::vector<int> canon(npat, -1);
+    std::map<std::vector<uint8_t>, int> seen;
+    auto canon_of = [&](size_t q) {
+        if (canon[q] < 0) {
+            std::vector<uint8_t> f(tb.pres.begin() + q * total, tb.pres.begin() + (q + 1) * total);
+            f.insert(f.end(), tb.want.begin() + q * total, tb.want.begin() + (q + 1) * total);
+            canon[q] = seen.emplace(std::move(f), (int)q).first->second;
+        }
+        return canon[q];
+    };
+    // Direct stripes in ranges, each within the table budget and the stripe
+    // limit: one rows set per range.  The other stripes afterwards, one by one.
+    std::vector<int> id_of(npat, -1);  // a canonical pair's number in the current range
+    std::vector<RowsSetPair> pairs;
+    std::vector<int> members;
+    std::vector<std::pair<uint32_t, int>> direct;
+    std::vector<uint32_t> own;
+    size_t bytes = 0;
+    auto flush = [&]() -> int {
+        const int e = rows_list_launches(c, st, pairs, direct, s);
+        for (int cq : members) id_of[cq] = -1;
+        pairs.clear(), members.clear(), direct.clear();
+        bytes = 0;
+        return e;
+    };
+    for (size_t z = 0; z < n; z++) {
+        const size_t q = pattern_of[z];
+        if (!tb.todo[q]) continue;
+        const int cq = canon_of(q);
+        if (!list_on || !rows_list_direct(c, tb.todo[cq])) {
+            own.push_back((uint32_t)z);
+            continue;
+        }
+        if (id_of[cq] < 0) {
+            const size_t need = rows_set_pair_bytes(c->bits, tb.npres[cq], tb.todo[cq], kDecGroup);
+            if (!members.empty() && bytes + need > kPatSetBudget)
+                if (int e = flush()) return e;
+            bytes += need;
+            id_of[cq] = (int)pairs.size();
+            pairs.push_back(RowsSetPair{tb.pres.data() + (size_t)cq * total, tb.want.data() + (size_t)cq * total});
+            members.push_back(cq);
+        }
+        direct.emplace_back((uint32_t)z, id_of[cq]);
+        if (direct.size() >= kPatMaxStripes)
+            if (int e = flush()) return e;
+    }
+    if (int e = flush()) return e;
+    // What rs_reconstruct_rows_dev_batch runs for the stripe alone, the direct tier left out.
+    std::vector<uint8_t *> rows(total);
+    for (uint32_t z : own) {
+        const size_t q = pattern_of[z];
+        const std::vector<uint8_t> pr(tb.pres.begin() + q * total, tb.pres.begin() + (q + 1) * total);
+        const std::vector<uint8_t> rq(tb.want.begin() + q * total, tb.want.begin() + (q + 1) * total);
+        if (rec_lds_ok(c)) {
+            DevPlan *dpl = nullptr;
+            if (int e = dev_plan(c, pr, Want(rq), st[z].shard_size, &dpl)) return e;
+            if (int e = launch_rec_plan(c, dpl, st[z].base, st[z].row_stride, 0, 1, st[z].shard_size, s)) return e;
+        } else {
+            for (int i = 0; i < total; i++) rows[i] = st[z].base + (uint64_t)i * st[z].row_stride;
+            if (int e = reconstruct_device(c, rows.data(), pr, st[z].shard_size, Want(rq), s)) return e;
+        }
+    }
+    return dc.finish(RS_OK);
+}
+
 // ---- The same with check equations over the rows marked present
 // (rs_reconstruct_rows_checked_dev_batch_patterns)
 
@@ -4578,6 +4774,53 @@ int rs_debug_encode_list_plan(int bits, int p, int unit_width, const size_t *siz
             first_wg += l.z1 - l.z0 + 1;
         }
     }
+    return RS_OK;
+}
+
+int rs_reconstruct_rows_dev_list(rs_codec *c, const rs_stripe *stripes, size_t nstripes, const uint8_t *present,
+                                 const uint8_t *required, size_t npatterns, const uint32_t *pattern_of, void *stream) {
+    RowsPatTables tb;
+    if (int e = rows_list_tables(c, stripes, nstripes, present, required, npatterns, pattern_of, tb)) return e;
+    return rows_list_call(c, stripes, nstripes, tb, npatterns, pattern_of, stream);
+}
+
+int rs_debug_rows_list_plan(int bits, int unit_width, const size_t *sizes, const int *wanted, size_t nentries,
+                            size_t max_entries, size_t *entry_limit, int *nlaunches, uint64_t *launches,
+                            uint32_t *first_wg) {
+    if (entry_limit) *entry_limit = kRowsListMaxEntries;
+    if ((bits != 8 && bits != 16) || unit_width < -1 || unit_width > 1 || !sizes || !wanted || !nlaunches)
+        return RS_ERR_INVALID_ARG;
+    std::vector<uint64_t> sz(sizes, sizes + nentries);
+    for (uint64_t S : sz)
+        if (!S || S % 64) return RS_ERR_INVALID_ARG;
+    std::vector<RowsListRange> plan;
+    if (!make_rows_list_plan(sz.data(), wanted, nentries, rows_list_wg_bytes(bits, false), rows_list_wg_bytes(bits, true),
+                             unit_width, kRowsListNarrowBelow, max_entries ? max_entries : kRowsListMaxEntries,
+                             kEncListMaxWg, plan))
+        return RS_ERR_INVALID_ARG;
+    int nl = 0;
+    for (const RowsListRange &r : plan)
+        for (int t = 1; t <= kDecGroup; t++) {
+            const RowsListGroup &g = r.g[t];
+            if (!g.n) continue;
+            nl++;
+            if (launches) {
+                *launches++ = r.e0;
+                *launches++ = r.e1;
+                *launches++ = (uint64_t)t;
+                *launches++ = g.n;
+                *launches++ = g.wg_bytes;
+                *launches++ = g.nwg;
+                *launches++ = g.o_ent;
+                *launches++ = g.o_pre;
+                *launches++ = r.bytes;
+            }
+            if (first_wg) {
+                write_rows_list_prefix(sz.data(), wanted, r, t, first_wg);
+                first_wg += g.n + 1;
+            }
+        }
+    *nlaunches = nl;
     return RS_OK;
 }
 
@@ -5354,6 +5597,7 @@ int rs_debug_set_path(const char *knob, int value) {
     else if (k == "scrub_batch" && value >= -1 && value <= 1) g_path_scrub_batch = value;
     else if (k == "scrub_chunk" && value >= 0) g_path_scrub_chunk = value;
     else if (k == "enc_list" && value >= -1 && value <= 1) g_path_enc_list = value;
+    else if (k == "rows_list" && value >= -1 && value <= 0) g_path_rows_list = value;
     else return RS_ERR_INVALID_ARG;
     return RS_OK;
 }

@@ -533,6 +533,61 @@ void write_encode_list_prefix(const uint64_t *sizes, const EncListLaunch &l, uin
     *first_wg = (uint32_t)at;
 }
 
+bool make_rows_list_plan(const uint64_t *sizes, const int *wanted, size_t n, uint32_t wide, uint32_t narrow, int unit_width,
+                         uint64_t narrow_below, size_t max_entries, uint64_t max_wg, std::vector<RowsListRange> &out) {
+    out.clear();
+    if (!max_entries || !wide || !narrow) return false;
+    // the width the cuts are counted in; an automatic launch that turns narrow
+    // has fewer than narrow_below wide workgroups, so at most twice that many
+    const uint32_t cut = unit_width == 1 ? narrow : wide;
+    auto wgs = [](uint64_t S, uint32_t w) { return S / w + (S % w ? 1 : 0); };
+    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    for (size_t i = 0; i < n; i++)
+        if (wanted[i] < 1 || wanted[i] > kRowsListGroup || wgs(sizes[i], cut) > max_wg) return false;
+    for (size_t e = 0; e < n;) {
+        RowsListRange r{};
+        r.e0 = r.e1 = e;
+        for (; r.e1 < n && r.e1 - r.e0 < max_entries; r.e1++) {
+            RowsListGroup &g = r.g[wanted[r.e1]];
+            const uint64_t w = wgs(sizes[r.e1], cut);
+            if (g.nwg + w > max_wg) break;
+            g.nwg += w;
+            g.n++;
+        }
+        for (int t = 1; t <= kRowsListGroup; t++) {
+            RowsListGroup &g = r.g[t];
+            if (!g.n) continue;
+            g.wg_bytes = cut;
+            if (unit_width < 0 && g.nwg < narrow_below) {
+                uint64_t nn = 0;
+                for (size_t i = r.e0; i < r.e1; i++)
+                    if (wanted[i] == t) nn += wgs(sizes[i], narrow);
+                if (nn <= max_wg) {  // else the launch stays wide
+                    g.wg_bytes = narrow;
+                    g.nwg = nn;
+                }
+            }
+            g.o_ent = r.bytes;
+            g.o_pre = g.o_ent + a256(g.n * kRowsListEntryBytes);
+            r.bytes = g.o_pre + a256(4 * (g.n + 1));
+        }
+        out.push_back(r);
+        e = r.e1;
+    }
+    return true;
+}
+
+void write_rows_list_prefix(const uint64_t *sizes, const int *wanted, const RowsListRange &r, int t, uint32_t *first_wg) {
+    const uint32_t w = r.g[t].wg_bytes;
+    uint64_t at = 0;
+    for (size_t i = r.e0; i < r.e1; i++) {
+        if (wanted[i] != t) continue;
+        *first_wg++ = (uint32_t)at;
+        at += sizes[i] / w + (sizes[i] % w ? 1 : 0);
+    }
+    *first_wg = (uint32_t)at;
+}
+
 bool decode_schedule(const Field &F, int k, int p, std::vector<uint32_t> &ifft, std::vector<uint32_t> &fft) {
     const int m = ceil_pow2(p);
     if ((long)m + k > (long)F.order) return false;  // the Go code panics (see error_locators)

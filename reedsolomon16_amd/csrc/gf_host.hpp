@@ -227,6 +227,57 @@ inline uint32_t encode_list_find(const uint32_t *first_wg, uint32_t n, uint32_t 
     return lo;
 }
 
+// ---- Direct decode over a list of stripes of different sizes in one launch
+// (rs_reconstruct_rows_dev_list, kernels.hip k_decode_rows_list).  A list
+// entry is one (stripe, rows-set descriptor) pair: its stripe's shard size and
+// the descriptor's wanted-row count t in [1, kRowsListGroup].  The entries of
+// a range travel through one slot of the pinned ring in one copy; a range has
+// one launch per t that occurs, over the range's entries of that t in order.
+constexpr int kRowsListGroup = 8;  // kernels.hpp kDecGroup
+// Bytes of a row one workgroup of the direct decode covers (256 lanes, one
+// unit each): the wide unit (32 bytes a lane in GF(2^16), 16 in GF(2^8)) or
+// the narrow one, half of it; 0 for another field.
+constexpr uint32_t rows_list_wg_bytes(int bits, bool narrow) {
+    return bits == 16 ? (narrow ? 4096u : 8192u) : bits == 8 ? (narrow ? 2048u : 4096u) : 0u;
+}
+constexpr size_t kRowsListEntryBytes = 32;  // kernels.hpp RowsListEntry
+// One launch: `n` entries of the range with t wanted rows, nwg workgroups of
+// wg_bytes in all; in the slot the entries start at o_ent, the n + 1 prefix
+// words at o_pre (both 256-byte aligned).  n == 0: no launch for this t.
+struct RowsListGroup {
+    size_t n;
+    uint32_t wg_bytes;
+    uint64_t nwg;
+    size_t o_ent, o_pre;
+};
+// Entries [e0, e1) of the list, `bytes` of a ring slot, g[t] for t in [1, kRowsListGroup].
+struct RowsListRange {
+    size_t e0, e1, bytes;
+    RowsListGroup g[kRowsListGroup + 1];
+};
+// Slot bytes that always hold a range of `entries` entries however they split
+// into groups, and the largest entry count a slot of `slot_bytes` always holds.
+constexpr size_t rows_list_slot_bytes(size_t entries) {
+    return entries * (kRowsListEntryBytes + 4) + (size_t)kRowsListGroup * (2 * 256 + 4);
+}
+constexpr size_t rows_list_max_entries(size_t slot_bytes) {
+    return slot_bytes <= rows_list_slot_bytes(0) ? 0 : (slot_bytes - rows_list_slot_bytes(0)) / (kRowsListEntryBytes + 4);
+}
+// Cuts the entries (sizes[i] > 0, a multiple of 64; 1 <= wanted[i] <=
+// kRowsListGroup), in order, into ranges of at most max_entries entries whose
+// every launch has at most max_wg workgroups.  The unit of a launch follows
+// launch_decode_rows_patterns's rule over the launch's own total: unit_width
+// -1 automatic (narrow when the launch has fewer than narrow_below workgroups
+// at the wide unit), 0 wide, 1 narrow.  False when max_entries == 0, a wanted
+// count is out of range or one entry alone exceeds max_wg; the plan is then
+// unspecified.
+bool make_rows_list_plan(const uint64_t *sizes, const int *wanted, size_t n, uint32_t wide, uint32_t narrow, int unit_width,
+                         uint64_t narrow_below, size_t max_entries, uint64_t max_wg, std::vector<RowsListRange> &out);
+// first_wg[0 .. g[t].n] of the range's launch for t: first_wg[i] = workgroups
+// of the launch's entries before its i-th, first_wg[g[t].n] = g[t].nwg.  The
+// kernel's search is encode_list_find.
+void write_rows_list_prefix(const uint64_t *sizes, const int *wanted, const RowsListRange &r, int t, uint32_t *first_wg);
+
 // Decoder schedules over n = ceilPow2(m+k) rows (leopard16.go:573-657).
 bool decode_schedule(const Field &F, int k, int p, std::vector<uint32_t> &ifft_logs, std::vector<uint32_t> &fft_logs);
 

@@ -2794,6 +2794,110 @@ hipError_t launch_decode_rows_patterns(int bits, const DecodeRowsPatArgs &a, hip
     return narrow ? decode_rows_pat_f<F8<2>>(a, s) : decode_rows_pat_f<F8<4>>(a, s);
 }
 
+// ---------------------------------------------------------------- direct decode over a list of stripes
+// k_decode_rows_pat over stripes of different sizes, each in a buffer of its
+// own (kernels.hpp DecodeRowsListArgs, rs_reconstruct_rows_dev_list).  A copy
+// of that kernel's body: k_decode_rows, k_decode_rows_pat and
+// k_decode_rows_chk keep their registers.  The grid is one-dimensional over
+// the column blocks of all entries; a workgroup finds its entry by
+// k_encode_reg_list's binary search over the prefix first_wg, then reads the
+// entry and the entry's descriptor.  Prefix, entry and descriptor are the same
+// for the whole workgroup and read-only for the launch: scalar loads through
+// the constant address space, SGPRs and no VGPRs.  A workgroup never straddles
+// two entries, so np is wave-uniform; the lanes of an entry's last workgroup
+// past the row end return (there are no barriers).  All addresses are 64-bit.
+namespace {
+
+typedef __attribute__((address_space(4))) const RowsListEntry dec_clist_t;
+
+template <class F, int NT>
+__global__ void __launch_bounds__(256, 2) k_decode_rows_list(DecodeRowsListArgs a) {
+    typedef typename F::Vec V;
+    // the entry z with first_wg[z] <= blockIdx.x < first_wg[z + 1] (gf_host.hpp encode_list_find)
+    cu32_t *fw = (cu32_t *)a.first_wg;
+    const uint32_t wg = blockIdx.x;
+    uint32_t z = 0, zh = a.nlist;
+    while (zh - z > 1) {
+        const uint32_t mid = z + (zh - z) / 2;
+        if (fw[mid] <= wg) z = mid;
+        else zh = mid;
+    }
+    dec_clist_t &e = ((dec_clist_t *)a.list)[z];
+    const uint64_t u = (uint64_t)(wg - fw[z]) * 256 + threadIdx.x;
+    if (u >= F::units(e.shard_size)) return;
+    dec_cpat_t &d = ((dec_cpat_t *)a.pat)[e.pat];
+    uint8_t *const sb = e.base;
+    const uint64_t stride = e.row_stride;
+    const int np = d.np;
+    const uint32_t *tw = d.tw;  // table (j, i) at tw + (j * np + i) * TWD
+    upd_cint_t *si = (upd_cint_t *)d.src_idx, *di = (upd_cint_t *)d.dst_idx;
+    // always inlined: left to the inliner, k_encode_reg_list's staging lambdas
+    // stayed calls, with the kernel arguments in scratch and the search in vector loads
+    auto srow = [&](int i) __attribute__((always_inline)) -> const uint8_t * { return sb + (uint64_t)si[i] * stride; };
+    V acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; j++) acc[j] = F::zero();
+    const uint64_t trow = (uint64_t)np * F::TWD;
+    int i = 0;
+    for (; i + kDecRows <= np; i += kDecRows) {
+        V x[kDecRows];
+#pragma unroll
+        for (int q = 0; q < kDecRows; q++) x[q] = F::load(srow(i + q), u);
+#pragma unroll
+        for (int q = 0; q < kDecRows; q++) {
+            UpdMasks<F> mk;
+            mk.prepare(x[q]);
+#pragma unroll
+            for (int j = 0; j < NT; j++) {
+                const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)(i + q) * F::TWD);
+                mk.mul_add(acc[j], tb.v);
+            }
+        }
+    }
+    for (; i < np; i++) {
+        UpdMasks<F> mk;
+        mk.prepare(F::load(srow(i), u));
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)i * F::TWD);
+            mk.mul_add(acc[j], tb.v);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NT; j++) F::store(sb + (uint64_t)di[j] * stride, u, acc[j]);
+}
+
+template <class F>
+hipError_t decode_rows_list_f(const DecodeRowsListArgs &a, hipStream_t s) {
+    static_assert(kDecGroup == 8, "decode_rows_list_f dispatches group sizes 1..8");
+    const dim3 grid(a.nwg), block(256);
+    switch (a.nt) {
+        case 1: hipLaunchKernelGGL((k_decode_rows_list<F, 1>), grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL((k_decode_rows_list<F, 2>), grid, block, 0, s, a); break;
+        case 3: hipLaunchKernelGGL((k_decode_rows_list<F, 3>), grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL((k_decode_rows_list<F, 4>), grid, block, 0, s, a); break;
+        case 5: hipLaunchKernelGGL((k_decode_rows_list<F, 5>), grid, block, 0, s, a); break;
+        case 6: hipLaunchKernelGGL((k_decode_rows_list<F, 6>), grid, block, 0, s, a); break;
+        case 7: hipLaunchKernelGGL((k_decode_rows_list<F, 7>), grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL((k_decode_rows_list<F, 8>), grid, block, 0, s, a); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+// The unit width comes with the launch (gf_host.hpp make_rows_list_plan applies
+// launch_decode_rows_patterns's rule to the launch's total workgroup count).
+hipError_t launch_decode_rows_list(int bits, const DecodeRowsListArgs &a, hipStream_t s) {
+    if (!a.list || !a.first_wg || !a.pat || !a.nlist || !a.nwg || a.nwg > 0x7fffffffu) return hipErrorInvalidValue;
+    if (a.nt <= 0 || a.nt > kDecGroup) return hipErrorInvalidValue;
+    const uint32_t wide = bits == 16 ? 8192 : 4096;  // 256 lanes of 32 / 16 bytes
+    if (a.wg_bytes != wide && a.wg_bytes != wide / 2) return hipErrorInvalidValue;
+    const bool narrow = a.wg_bytes != wide;
+    if (bits == 16) return narrow ? decode_rows_list_f<F16<2>>(a, s) : decode_rows_list_f<F16<4>>(a, s);
+    return narrow ? decode_rows_list_f<F8<2>>(a, s) : decode_rows_list_f<F8<4>>(a, s);
+}
+
 // ---------------------------------------------------------------- direct decode with check equations
 // k_decode_rows_pat with NC more accumulators (kernels.hpp DecodeRowsChkArgs,
 // rs_reconstruct_rows_checked_dev_batch_patterns): the descriptor's table has

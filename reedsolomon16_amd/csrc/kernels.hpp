@@ -352,6 +352,29 @@ struct DecodeRowsPatArgs {
 };
 hipError_t launch_decode_rows_patterns(int bits, const DecodeRowsPatArgs &a, hipStream_t s);
 
+// The same over a list of stripes of different sizes, each in a buffer of its
+// own (rs_reconstruct_rows_dev_list; k_decode_rows_list): a one-dimensional
+// grid over the 256-unit column blocks of all entries.  Workgroup w serves the
+// entry e with first_wg[e] <= w < first_wg[e + 1] (gf_host.hpp
+// write_rows_list_prefix, encode_list_find) and its block w - first_wg[e].
+struct RowsListEntry {
+    uint8_t *base;        // shard i at base + i * row_stride (64-bit arithmetic: no span limit)
+    uint64_t row_stride;
+    uint64_t shard_size;  // > 0, a multiple of 64
+    uint32_t pat, pad;    // descriptor pat[pat]
+};
+struct DecodeRowsListArgs {
+    const RowsListEntry *list;  // device array, nlist entries; every pat[list[].pat].t == nt
+    const uint32_t *first_wg;   // device array, nlist + 1 entries, strictly ascending from 0
+    const RowsPattern *pat;     // device array
+    uint32_t nlist, nwg;        // nwg == first_wg[nlist] < 2^31
+    uint32_t wg_bytes;          // gf_host.hpp rows_list_wg_bytes: the wide or the narrow unit
+    int nt;                     // 1 <= nt <= kDecGroup
+};
+// hipErrorInvalidValue for a NULL array, nlist or nwg == 0, nwg > 0x7fffffff,
+// nt outside [1, kDecGroup] or a wg_bytes that is no unit of the field.
+hipError_t launch_decode_rows_list(int bits, const DecodeRowsListArgs &a, hipStream_t s);
+
 // The same with nc check equations over the present rows in the same pass
 // (rs_reconstruct_rows_checked_dev_batch_patterns; gf_host.hpp
 // make_check_weights): the descriptor's table holds the pair's t decode rows,

@@ -228,7 +228,7 @@ inline uint32_t encode_list_find(const uint32_t *first_wg, uint32_t n, uint32_t 
 }
 
 // ---- Direct decode over a list of stripes of different sizes in one launch
-// (rs_reconstruct_rows_dev_list, kernels.hip k_decode_rows_list).  A list
+// (rs_reconstruct_rows_dev_list, stream_kernels.hip k_decode_rows_list).  A list
 // entry is one (stripe, rows-set descriptor) pair: its stripe's shard size and
 // the descriptor's wanted-row count t in [1, kRowsListGroup].  The entries of
 // a range travel through one slot of the pinned ring in one copy; a range has

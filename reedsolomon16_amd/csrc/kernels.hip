@@ -20,7 +20,7 @@
 #include <cstdlib>
 #include <utility>
 
-#include "kernels.hpp"
+#include "field.hpp"
 #include "rec_common.hpp"
 #include "schedule.hpp"
 
@@ -31,212 +31,6 @@ using namespace rec;
 
 typedef __attribute__((address_space(1))) void gvoid_t;
 typedef __attribute__((address_space(3))) void lvoid_t;
-
-template <int W> struct VecOf;
-template <> struct VecOf<1> { typedef uint32_t T; };
-template <> struct VecOf<2> { typedef uint32_t T __attribute__((ext_vector_type(2))); };
-template <> struct VecOf<4> { typedef uint32_t T __attribute__((ext_vector_type(4))); };
-
-template <int W>
-__device__ __forceinline__ void ldw(const uint8_t *p, uint32_t (&v)[W]) {
-    typedef typename VecOf<W>::T T;
-    const T x = *(const __attribute__((address_space(1))) T *)(p);
-    if constexpr (W == 1) {
-        v[0] = x;
-    } else {
-#pragma unroll
-        for (int i = 0; i < W; i++) v[i] = x[i];
-    }
-}
-template <int W>
-__device__ __forceinline__ void stw(uint8_t *p, const uint32_t (&v)[W]) {
-    typedef typename VecOf<W>::T T;
-    T x;
-    if constexpr (W == 1) {
-        x = v[0];
-    } else {
-#pragma unroll
-        for (int i = 0; i < W; i++) x[i] = v[i];
-    }
-    *(__attribute__((address_space(1))) T *)(p) = x;
-}
-// LDS (address space 3) loads of W dwords.
-template <int W>
-__device__ __forceinline__ void ldw_lds(const uint8_t *p, uint32_t (&v)[W]) {
-    typedef typename VecOf<W>::T T;
-    const T x = *(const __attribute__((address_space(3))) T *)(p);
-    if constexpr (W == 1) {
-        v[0] = x;
-    } else {
-#pragma unroll
-        for (int i = 0; i < W; i++) v[i] = x[i];
-    }
-}
-
-// Verify's mismatch word is a device word the host reads back after the
-// launch (codec.cpp): every writer stores the same 1, so a plain store
-// suffices.  One lane per wave stores.
-__device__ __forceinline__ void flag_mismatch(int *f, bool bad) {
-    const uint64_t m = __ballot(bad);
-    if (m && __lane_id() == (unsigned)(__ffsll((unsigned long long)m) - 1) &&
-        __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)  // set stays set: no contended store
-        __hip_atomic_store(f, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint32_t perm(uint32_t s0, uint32_t s1, uint32_t sel) {
-    return __builtin_amdgcn_perm(s0, s1, sel);
-}
-// a ^ b ^ c in one VALU op (gfx950 v_bitop3_b32, truth table 0x96).
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-
-// ---------------------------------------------------------------- GF(2^16)
-template <int W_>
-struct F16 {
-    static constexpr int W = W_;
-    static constexpr bool SYM16 = true;  // 16-bit symbols (lo/hi halves of 64-byte blocks)
-    static constexpr int TWD = 24;     // dwords per twiddle table
-    static constexpr int TWU = 20;     // dwords used by mul_add
-    static constexpr int LOGIDX = 20;  // dword holding log_m
-    static constexpr uint32_t MOD = 65535;
-    static constexpr int UPB = 8 / W;  // units per 64-byte block
-    struct Vec {
-        uint32_t l[W], h[W];
-    };
-    __device__ static uint64_t units(uint64_t S) { return (S >> 6) * UPB; }
-    __device__ static uint64_t off(uint64_t u) { return (u / UPB) * 64 + (u % UPB) * (4 * W); }
-    __device__ static Vec load(const uint8_t *row, uint64_t u) {
-        Vec v;
-        const uint8_t *p = row + off(u);
-        ldw<W>(p, v.l);
-        ldw<W>(p + 32, v.h);
-        return v;
-    }
-    __device__ static void store(uint8_t *row, uint64_t u, const Vec &v) {
-        uint8_t *p = row + off(u);
-        stw<W>(p, v.l);
-        stw<W>(p + 32, v.h);
-    }
-    __device__ static Vec zero() {
-        Vec v;
-#pragma unroll
-        for (int i = 0; i < W; i++) v.l[i] = v.h[i] = 0;
-        return v;
-    }
-    // ---- LDS staging of one wave's 64 units of a row (512*W bytes).
-    // Row image: [lo halves of blocks 0..4W) [hi halves of blocks 0..4W)
-    //            [lo halves of blocks 4W..8W) [hi halves of blocks 4W..8W)
-    // so lane l reads its lo dwords at (l/32)*256W + (l%32)*4W and its hi dwords
-    // 128W bytes later: consecutive lanes hit consecutive banks (conflict-free).
-    static constexpr int ROWB = 512 * W;
-    __device__ static uint64_t span_off(uint64_t u0) { return (u0 / UPB) * 64; }
-    // Global byte offset (within the wave span) of the 16-byte LDS piece s.
-    __device__ static uint32_t piece_goff(uint32_t s) {
-        const uint32_t G = s / (8 * W), t = s % (8 * W);
-        return ((G >> 1) * 4 * W + (t >> 1)) * 64 + (G & 1) * 32 + (t & 1) * 16;
-    }
-    __device__ static Vec lds_load(const uint8_t *img, int lane) {
-        Vec v;
-        const uint8_t *p = img + (lane >> 5) * (256 * W) + (lane & 31) * (4 * W);
-        ldw_lds<W>(p, v.l);
-        ldw_lds<W>(p + 128 * W, v.h);
-        return v;
-    }
-    __device__ static void xor_into(Vec &a, const Vec &b) {
-#pragma unroll
-        for (int i = 0; i < W; i++) {
-            a.l[i] ^= b.l[i];
-            a.h[i] ^= b.h[i];
-        }
-    }
-    __device__ static uint32_t diff(const Vec &a, const Vec &b) {
-        uint32_t d = 0;
-#pragma unroll
-        for (int i = 0; i < W; i++) d |= (a.l[i] ^ b.l[i]) | (a.h[i] ^ b.h[i]);
-        return d;
-    }
-    // Empty asm that "redefines" the registers: chains the op that produced
-    // them ahead of this point (bounds code motion in the unrolled op lists).
-    __device__ static void pin(Vec &v) {
-#pragma unroll
-        for (int i = 0; i < W; i++) asm volatile("" : "+v"(v.l[i]), "+v"(v.h[i]));
-    }
-    // x ^= y * exp(log_m); t = twiddle table (wave-uniform).
-    __device__ static void mul_add(Vec &x, const Vec &y, const uint32_t *__restrict__ t) {
-#pragma unroll
-        for (int i = 0; i < W; i++) {
-            const uint32_t lo = y.l[i], hi = y.h[i];
-            const uint32_t a0 = lo & 0x07070707u, a1 = (lo >> 3) & 0x07070707u, a2 = (lo >> 6) & 0x03030303u;
-            const uint32_t b0 = hi & 0x07070707u, b1 = (hi >> 3) & 0x07070707u, b2 = (hi >> 6) & 0x03030303u;
-            x.l[i] = xor3(xor3(xor3(x.l[i], perm(t[1], t[0], a0), perm(t[5], t[4], a1)), perm(t[8], t[8], a2),
-                               perm(t[11], t[10], b0)),
-                          perm(t[15], t[14], b1), perm(t[18], t[18], b2));
-            x.h[i] = xor3(xor3(xor3(x.h[i], perm(t[3], t[2], a0), perm(t[7], t[6], a1)), perm(t[9], t[9], a2),
-                               perm(t[13], t[12], b0)),
-                          perm(t[17], t[16], b1), perm(t[19], t[19], b2));
-        }
-    }
-};
-
-// ---------------------------------------------------------------- GF(2^8)
-template <int W_>
-struct F8 {
-    static constexpr int W = W_;
-    static constexpr bool SYM16 = false;
-    static constexpr int TWD = 8;
-    static constexpr int TWU = 5;
-    static constexpr int LOGIDX = 5;
-    static constexpr uint32_t MOD = 255;
-    struct Vec {
-        uint32_t b[W];
-    };
-    __device__ static uint64_t units(uint64_t S) { return S / (4 * W); }
-    __device__ static uint64_t off(uint64_t u) { return u * (4 * W); }
-    __device__ static Vec load(const uint8_t *row, uint64_t u) {
-        Vec v;
-        ldw<W>(row + off(u), v.b);
-        return v;
-    }
-    __device__ static void store(uint8_t *row, uint64_t u, const Vec &v) { stw<W>(row + off(u), v.b); }
-    __device__ static Vec zero() {
-        Vec v;
-#pragma unroll
-        for (int i = 0; i < W; i++) v.b[i] = 0;
-        return v;
-    }
-    // LDS staging: natural layout, lane l at l*4W (conflict-free).
-    static constexpr int ROWB = 256 * W;
-    __device__ static uint64_t span_off(uint64_t u0) { return u0 * (4 * W); }
-    __device__ static uint32_t piece_goff(uint32_t s) { return s * 16; }
-    __device__ static Vec lds_load(const uint8_t *img, int lane) {
-        Vec v;
-        ldw_lds<W>(img + lane * (4 * W), v.b);
-        return v;
-    }
-    __device__ static void xor_into(Vec &a, const Vec &b) {
-#pragma unroll
-        for (int i = 0; i < W; i++) a.b[i] ^= b.b[i];
-    }
-    __device__ static uint32_t diff(const Vec &a, const Vec &b) {
-        uint32_t d = 0;
-#pragma unroll
-        for (int i = 0; i < W; i++) d |= a.b[i] ^ b.b[i];
-        return d;
-    }
-    __device__ static void pin(Vec &v) {
-#pragma unroll
-        for (int i = 0; i < W; i++) asm volatile("" : "+v"(v.b[i]));
-    }
-    __device__ static void mul_add(Vec &x, const Vec &y, const uint32_t *__restrict__ t) {
-#pragma unroll
-        for (int i = 0; i < W; i++) {
-            const uint32_t v = y.b[i];
-            const uint32_t a0 = v & 0x07070707u, a1 = (v >> 3) & 0x07070707u, a2 = (v >> 6) & 0x03030303u;
-            x.b[i] = xor3(x.b[i] ^ perm(t[1], t[0], a0), perm(t[3], t[2], a1), perm(t[4], t[4], a2));
-        }
-    }
-};
 
 // ---------------------------------------------------------------- GF(2^16) in subfield coordinates
 // Transforms whose twiddles all lie in GF(2^8) (fftSkew indices < 255, e.g. the
@@ -378,11 +172,6 @@ __device__ __forceinline__ uint8_t *row_ptr(const RowSet &rs, int i) {
 // Op lists (IfftOps / FftOps) and the half-wave split schedules live in
 // schedule.hpp, shared with the host.
 
-// Twiddle table held in registers (wave-uniform -> SGPRs).
-template <class F>
-struct Tab {
-    uint32_t v[F::TWU];
-};
 // LDS-resident table (uniform address: every lane reads the same 16-byte
 // slots, a broadcast); lands in VGPRs so both v_perm table operands are
 // VGPRs and no SGPR->VGPR copies are needed.
@@ -414,18 +203,6 @@ __device__ __forceinline__ void lds_tab_part(Tab<F> &r, uint32_t vaddr, int byte
         for (int j = 0; j < 4; j++)
             if (4 * q + j < F::TWU) r.v[4 * q + j] = x[j];
     }
-}
-
-// Loaded through the constant address space: read-only for the whole launch,
-// so the wave-uniform address turns into s_load_dwordx* (scalar cache).
-typedef __attribute__((address_space(4))) const uint32_t cu32_t;
-template <class F>
-__device__ __forceinline__ Tab<F> load_tab(const uint32_t *__restrict__ t) {
-    Tab<F> r;
-    cu32_t *ct = (cu32_t *)t;
-#pragma unroll
-    for (int j = 0; j < F::TWU; j++) r.v[j] = ct[j];
-    return r;
 }
 
 // Multiplying ops of a list, in order, each with the slot it reads; XOR-only
@@ -702,12 +479,7 @@ __global__ void __launch_bounds__(256, 2) k_encode_reg_list(EncodeListArgs a) {
     // the stripe z with first_wg[z] <= blockIdx.x < first_wg[z + 1] (gf_host.hpp encode_list_find)
     cu32_t *fw = (cu32_t *)a.first_wg;
     const uint32_t wg = blockIdx.x;
-    uint32_t z = 0, zh = a.nstripes;
-    while (zh - z > 1) {
-        const uint32_t mid = z + (zh - z) / 2;
-        if (fw[mid] <= wg) z = mid;
-        else zh = mid;
-    }
+    const uint32_t z = list_entry_of(fw, a.nstripes, wg);
     enc_cstripe_t &d = ((enc_cstripe_t *)a.stripes)[z];
     uint8_t *const sbase = d.base;
     const uint64_t stride = d.row_stride, shard_size = d.shard_size;
@@ -1145,21 +917,6 @@ __global__ void __launch_bounds__(256) k_reveal(uint8_t *const *dst, const uint8
     F::store(dst[i], u, v);
 }
 
-constexpr int kMaxGridY = 32768;
-inline dim3 grid_x(uint64_t units) { return dim3((unsigned)((units + 255) / 256)); }
-
-// Launch `body(y0, ny)` over y in [0, total) in slices of kMaxGridY.
-template <class Fn>
-hipError_t for_y(int total, Fn body) {
-    for (int y0 = 0; y0 < total; y0 += kMaxGridY) {
-        const int ny = total - y0 < kMaxGridY ? total - y0 : kMaxGridY;
-        body(y0, ny);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
 template <class F, int LOGM>
 hipError_t enc_reg(bool verify, const EncodeArgs &a, hipStream_t s) {
     uint64_t nunits;
@@ -1205,11 +962,14 @@ constexpr bool kLdsBranchFree = 1;  // lane-varying passes: branch-free multipli
 // rs_debug_set_path("unit_width", 0 / 1) forces the per-launch unit-width
 // choices below (LDS tiles of 128 vs 64 bytes; GF(2^8) register units of 16
 // vs 4 bytes) so the parity tests cover every variant at small sizes; -1 (the
-// default) keeps the automatic choice.  Testing only.
+// default) keeps the automatic choice.  Testing only.  Declared in field.hpp:
+// the stream launchers (stream_kernels.hip) apply it too.
+}  // namespace
 bool pick_narrow(bool automatic) {
     const int o = unit_width_override();
     return o < 0 ? automatic : o == 1;
 }
+namespace {
 
 // PK (the reconstruct kernels, k_rec_lds): 64-byte GF(2^16) tiles (W = 2)
 // keep a unit's 8 low and 8 high bytes together in one 16-byte LDS word,
@@ -2295,1331 +2055,6 @@ hipError_t launch_encode_lds(int bits, int logm, bool verify, const EncodeArgs &
     const bool narrow = pick_narrow((a.shard_size + 127) / 128 * (uint64_t)a.nstripes < kLdsMinGrid);
     if (narrow) return bits == 16 ? enc_lds_f<F16<2>>(logm, verify, a, s) : enc_lds_f<F8<2>>(logm, verify, a, s);
     return bits == 16 ? enc_lds_f<F16<4>>(logm, verify, a, s) : enc_lds_f<F8<4>>(logm, verify, a, s);
-}
-
-// ---------------------------------------------------------------- incremental parity update
-// parity row i ^= XOR over the changed data rows j of G[i][j] * (old_j ^ new_j)
-// (kernels.hpp UpdateArgs, gf_host.hpp generator_column).  A stream: every
-// byte is read once and written at most once, nothing is shared between lanes.
-namespace {
-
-// The nibble masks of mul_add depend only on the multiplicand.  An update
-// multiplies one difference by p constants, so the masks are prepared once per
-// difference and shared by all p rows: a product is then 12 v_perm_b32 +
-// 6 v_bitop3 per 4 symbols in GF(2^16) (3 + 2 in GF(2^8)) and no shifts.
-template <class F>
-struct UpdMasks;
-template <int W>
-struct UpdMasks<F16<W>> {
-    uint32_t a0[W], a1[W], a2[W], b0[W], b1[W], b2[W];
-    __device__ __forceinline__ void prepare(const typename F16<W>::Vec &y) {
-#pragma unroll
-        for (int i = 0; i < W; i++) {
-            const uint32_t lo = y.l[i], hi = y.h[i];
-            a0[i] = lo & 0x07070707u, a1[i] = (lo >> 3) & 0x07070707u, a2[i] = (lo >> 6) & 0x03030303u;
-            b0[i] = hi & 0x07070707u, b1[i] = (hi >> 3) & 0x07070707u, b2[i] = (hi >> 6) & 0x03030303u;
-        }
-    }
-    // x ^= y * c: t = c's table (F16::mul_add's layout), masks of y
-    __device__ __forceinline__ void mul_add(typename F16<W>::Vec &x, const uint32_t *t) const {
-#pragma unroll
-        for (int i = 0; i < W; i++) {
-            x.l[i] = xor3(xor3(xor3(x.l[i], perm(t[1], t[0], a0[i]), perm(t[5], t[4], a1[i])), perm(t[8], t[8], a2[i]),
-                               perm(t[11], t[10], b0[i])),
-                          perm(t[15], t[14], b1[i]), perm(t[18], t[18], b2[i]));
-            x.h[i] = xor3(xor3(xor3(x.h[i], perm(t[3], t[2], a0[i]), perm(t[7], t[6], a1[i])), perm(t[9], t[9], a2[i]),
-                               perm(t[13], t[12], b0[i])),
-                          perm(t[17], t[16], b1[i]), perm(t[19], t[19], b2[i]));
-        }
-    }
-};
-template <int W>
-struct UpdMasks<F8<W>> {
-    uint32_t a0[W], a1[W], a2[W];
-    __device__ __forceinline__ void prepare(const typename F8<W>::Vec &y) {
-#pragma unroll
-        for (int i = 0; i < W; i++) {
-            const uint32_t v = y.b[i];
-            a0[i] = v & 0x07070707u, a1[i] = (v >> 3) & 0x07070707u, a2[i] = (v >> 6) & 0x03030303u;
-        }
-    }
-    __device__ __forceinline__ void mul_add(typename F8<W>::Vec &x, const uint32_t *t) const {
-#pragma unroll
-        for (int i = 0; i < W; i++)
-            x.b[i] = xor3(x.b[i] ^ perm(t[1], t[0], a0[i]), perm(t[3], t[2], a1[i]), perm(t[4], t[4], a2[i]));
-    }
-};
-
-constexpr int kUpdRows = 4;  // parity rows whose loads a lane keeps in flight
-
-// Row pointers and changed indices are read-only for the whole launch: through
-// the constant address space their wave-uniform loads are scalar (as load_tab).
-typedef uint8_t *upd_rowp_t;
-typedef __attribute__((address_space(4))) const upd_rowp_t upd_crowp_t;
-typedef __attribute__((address_space(4))) const int upd_cint_t;
-__device__ __forceinline__ uint8_t *upd_row(uint8_t *const *rows, int i) { return ((upd_crowp_t *)rows)[i]; }
-
-// NT changed rows [j0, j0 + NT) of the call's t; PTR: rows through a.rows (one
-// stripe), else strided rows of stripe blockIdx.y + y0 with the new rows
-// stored over the old ones.  All addresses are 64-bit (row pointer + offset).
-template <class F, int NT, bool PTR>
-__global__ void __launch_bounds__(256, 2) k_update(UpdateArgs a, int j0, int y0) {
-    typedef typename F::Vec V;
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    UpdMasks<F> mk[NT];
-    uint8_t *pbase = nullptr;
-    if constexpr (PTR) {
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-            const uint8_t *o = upd_row(a.rows, a.p + j0 + j), *n = upd_row(a.rows, a.p + a.t + j0 + j);
-            V d = F::load(n, u);
-            if (o) F::xor_into(d, F::load(o, u));  // wave-uniform; no old row: the row is the difference
-            mk[j].prepare(d);
-        }
-    } else {
-        const uint64_t z = (uint64_t)blockIdx.y + (uint64_t)y0;
-        uint8_t *sb = a.base + z * a.stripe_stride;
-        const uint8_t *nb = a.nbase + z * a.new_stripe_stride + (uint64_t)j0 * a.new_row_stride;
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-            uint8_t *o = sb + (uint64_t)((upd_cint_t *)a.idx)[j0 + j] * a.row_stride;
-            const V nv = F::load(nb + (uint64_t)j * a.new_row_stride, u);
-            V d = F::load(o, u);
-            F::store(o, u, nv);
-            F::xor_into(d, nv);
-            mk[j].prepare(d);
-        }
-        pbase = sb + (uint64_t)a.k * a.row_stride;
-    }
-    const uint32_t *tw = a.tw + (uint64_t)j0 * F::TWD;  // table (i, j0 + j) at tw + (i * t + j) * TWD
-    const uint64_t trow = (uint64_t)a.t * F::TWD;
-    auto prow = [&](int i) -> uint8_t * {
-        if constexpr (PTR) return upd_row(a.rows, i);
-        else return pbase + (uint64_t)i * a.row_stride;
-    };
-    int i = 0;
-    for (; i + kUpdRows <= a.p; i += kUpdRows) {
-        uint8_t *r[kUpdRows];
-        V x[kUpdRows];
-#pragma unroll
-        for (int q = 0; q < kUpdRows; q++) {
-            r[q] = prow(i + q);
-            x[q] = F::load(r[q], u);
-        }
-#pragma unroll
-        for (int q = 0; q < kUpdRows; q++) {
-#pragma unroll
-            for (int j = 0; j < NT; j++) {
-                const Tab<F> tb = load_tab<F>(tw + (uint64_t)(i + q) * trow + (uint64_t)j * F::TWD);
-                mk[j].mul_add(x[q], tb.v);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < kUpdRows; q++) F::store(r[q], u, x[q]);
-    }
-    for (; i < a.p; i++) {
-        uint8_t *r = prow(i);
-        V x = F::load(r, u);
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-            const Tab<F> tb = load_tab<F>(tw + (uint64_t)i * trow + (uint64_t)j * F::TWD);
-            mk[j].mul_add(x, tb.v);
-        }
-        F::store(r, u, x);
-    }
-}
-
-template <class F, int NT>
-hipError_t update_group(const UpdateArgs &a, int j0, hipStream_t s) {
-    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
-    if (a.rows) {
-        hipLaunchKernelGGL((k_update<F, NT, true>), grid_x(units), dim3(256), 0, s, a, j0, 0);
-        return hipGetLastError();
-    }
-    return for_y(a.nstripes, [&](int y0, int ny) {
-        hipLaunchKernelGGL((k_update<F, NT, false>), dim3(grid_x(units).x, ny), dim3(256), 0, s, a, j0, y0);
-    });
-}
-
-template <class F>
-hipError_t update_f(const UpdateArgs &a, hipStream_t s) {
-    static_assert(kUpdGroup == 8, "update_f dispatches group sizes 1..8");
-    // ceil(t / kUpdGroup) launches of sizes as equal as t allows: a launch costs
-    // one pass over the parity rows plus a part that grows faster than its row
-    // count past 6 rows (registers: two waves per SIMD), so 9 rows run as 5 + 4
-    // (32 us per C3 stripe), not 8 + 1 (45 us).
-    const int nl = (a.t + kUpdGroup - 1) / kUpdGroup;
-    for (int g = 0, j0 = 0, nt = 0; g < nl; g++, j0 += nt) {
-        nt = a.t / nl + (g < a.t % nl ? 1 : 0);
-        hipError_t e;
-        switch (nt) {
-            case 1: e = update_group<F, 1>(a, j0, s); break;
-            case 2: e = update_group<F, 2>(a, j0, s); break;
-            case 3: e = update_group<F, 3>(a, j0, s); break;
-            case 4: e = update_group<F, 4>(a, j0, s); break;
-            case 5: e = update_group<F, 5>(a, j0, s); break;
-            case 6: e = update_group<F, 6>(a, j0, s); break;
-            case 7: e = update_group<F, 7>(a, j0, s); break;
-            default: e = update_group<F, 8>(a, j0, s); break;
-        }
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-}  // namespace
-
-// 32-byte units (16 in GF(2^8)) per lane, or 16-byte (8) ones where the wide
-// units would leave fewer than kUpdMinBlocks workgroups for the device.
-hipError_t launch_update(int bits, const UpdateArgs &a, hipStream_t s) {
-    constexpr uint64_t kUpdMinBlocks = 1024;
-    if (a.p <= 0 || a.t <= 0 || a.S == 0 || a.S % 64 || !a.tw) return hipErrorInvalidValue;
-    if (!a.rows && (!a.base || !a.nbase || !a.idx || a.nstripes <= 0)) return hipErrorInvalidValue;
-    const uint64_t ns = a.rows ? 1 : (uint64_t)a.nstripes;
-    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * ns;
-    const bool narrow = pick_narrow(wide_blocks < kUpdMinBlocks);
-    if (bits == 16) return narrow ? update_f<F16<2>>(a, s) : update_f<F16<4>>(a, s);
-    return narrow ? update_f<F8<2>>(a, s) : update_f<F8<4>>(a, s);
-}
-
-// ---------------------------------------------------------------- incremental update, a row list per stripe
-// k_update's strided body over a list of groups (rs_update_dev_batch_list,
-// kernels.hpp UpdateListArgs): every group of a launch changes NT rows of a
-// stripe of its own, each row with the tables of its own column.
-namespace {
-
-// Group blockIdx.y + y0.  Its descriptor (1 + 3 NT dwords: stripe, NT data
-// indices, NT table slots, NT entry numbers) is the same for the whole
-// workgroup and read-only for the launch: scalar loads through the constant
-// address space (as k_decode_rows_pat reads its own).  The loop is k_update's
-// (a copy: that kernel's instantiations keep their registers) with a table
-// base per row in place of one table row stride.  All addresses are 64-bit
-// (row pointer + offset).
-template <class F, int NT>
-__global__ void __launch_bounds__(256, 2) k_update_list(UpdateListArgs a, int y0) {
-    typedef typename F::Vec V;
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    cu32_t *d = (cu32_t *)a.list + ((uint64_t)blockIdx.y + (uint64_t)y0) * (uint64_t)(1 + 3 * NT);
-    uint8_t *sb = a.base + (uint64_t)d[0] * a.stripe_stride;
-    const uint64_t tcol = (uint64_t)a.p * F::TWD;  // dwords of a column's tables
-    UpdMasks<F> mk[NT];
-    const uint32_t *tw[NT];  // table (slot_j, i) at tw[j] + i * TWD
-#pragma unroll
-    for (int j = 0; j < NT; j++) {
-        uint8_t *o = sb + (uint64_t)d[1 + j] * a.row_stride;
-        tw[j] = a.tw + (uint64_t)d[1 + NT + j] * tcol;
-        const V nv = F::load(a.nbase + (uint64_t)d[1 + 2 * NT + j] * a.new_row_stride, u);
-        V x = F::load(o, u);
-        F::store(o, u, nv);
-        F::xor_into(x, nv);
-        mk[j].prepare(x);
-    }
-    uint8_t *pbase = sb + (uint64_t)a.k * a.row_stride;
-    int i = 0;
-    for (; i + kUpdRows <= a.p; i += kUpdRows) {
-        uint8_t *r[kUpdRows];
-        V x[kUpdRows];
-#pragma unroll
-        for (int q = 0; q < kUpdRows; q++) {
-            r[q] = pbase + (uint64_t)(i + q) * a.row_stride;
-            x[q] = F::load(r[q], u);
-        }
-#pragma unroll
-        for (int q = 0; q < kUpdRows; q++) {
-#pragma unroll
-            for (int j = 0; j < NT; j++) {
-                const Tab<F> tb = load_tab<F>(tw[j] + (uint64_t)(i + q) * F::TWD);
-                mk[j].mul_add(x[q], tb.v);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < kUpdRows; q++) F::store(r[q], u, x[q]);
-    }
-    for (; i < a.p; i++) {
-        uint8_t *r = pbase + (uint64_t)i * a.row_stride;
-        V x = F::load(r, u);
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-            const Tab<F> tb = load_tab<F>(tw[j] + (uint64_t)i * F::TWD);
-            mk[j].mul_add(x, tb.v);
-        }
-        F::store(r, u, x);
-    }
-}
-
-template <class F, int NT>
-hipError_t update_list_group(const UpdateListArgs &a, hipStream_t s) {
-    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
-    return for_y(a.nlist, [&](int y0, int ny) {
-        hipLaunchKernelGGL((k_update_list<F, NT>), dim3(grid_x(units).x, ny), dim3(256), 0, s, a, y0);
-    });
-}
-
-template <class F>
-hipError_t update_list_f(const UpdateListArgs &a, hipStream_t s) {
-    static_assert(kUpdGroup == 8, "update_list_f dispatches group sizes 1..8");
-    switch (a.nt) {
-        case 1: return update_list_group<F, 1>(a, s);
-        case 2: return update_list_group<F, 2>(a, s);
-        case 3: return update_list_group<F, 3>(a, s);
-        case 4: return update_list_group<F, 4>(a, s);
-        case 5: return update_list_group<F, 5>(a, s);
-        case 6: return update_list_group<F, 6>(a, s);
-        case 7: return update_list_group<F, 7>(a, s);
-        default: return update_list_group<F, 8>(a, s);
-    }
-}
-
-}  // namespace
-
-// Unit widths by launch_update's grid rule over the list's groups.
-hipError_t launch_update_list(int bits, const UpdateListArgs &a, hipStream_t s) {
-    constexpr uint64_t kUpdMinBlocks = 1024;
-    if (a.nt <= 0 || a.nt > kUpdGroup || a.nlist <= 0 || a.p <= 0 || a.S == 0 || a.S % 64) return hipErrorInvalidValue;
-    if (!a.base || !a.nbase || !a.tw || !a.list) return hipErrorInvalidValue;
-    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * (uint64_t)a.nlist;
-    const bool narrow = pick_narrow(wide_blocks < kUpdMinBlocks);
-    if (bits == 16) return narrow ? update_list_f<F16<2>>(a, s) : update_list_f<F16<4>>(a, s);
-    return narrow ? update_list_f<F8<2>>(a, s) : update_list_f<F8<4>>(a, s);
-}
-
-// ---------------------------------------------------------------- direct decode of a few rows
-// wanted row j = XOR over the present rows i of D[j][i] * row i (kernels.hpp
-// DecodeRowsArgs, gf_host.hpp decode_coefficients): k_update's shape
-// transposed.  A stream: every present byte is read once, every wanted byte
-// written once, nothing is shared between lanes.
-namespace {
-
-constexpr int kDecRows = 4;  // present rows whose loads a lane keeps in flight
-
-// NT wanted rows [j0, j0 + NT) of the call's t; PTR: rows through a.rows (one
-// stripe), else strided rows of stripe blockIdx.y + y0.  The masks of a present
-// unit are prepared once and shared by the NT products; the tables are
-// wave-uniform scalar loads.  All addresses are 64-bit (row pointer + offset).
-template <class F, int NT, bool PTR>
-__global__ void __launch_bounds__(256, 2) k_decode_rows(DecodeRowsArgs a, int j0, int y0) {
-    typedef typename F::Vec V;
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    uint8_t *sb = nullptr;
-    if constexpr (!PTR) sb = a.base + ((uint64_t)blockIdx.y + (uint64_t)y0) * a.stripe_stride;
-    auto srow = [&](int i) -> const uint8_t * {
-        if constexpr (PTR) return upd_row(a.rows, i);
-        else return sb + (uint64_t)((upd_cint_t *)a.src_idx)[i] * a.row_stride;
-    };
-    auto drow = [&](int j) -> uint8_t * {
-        if constexpr (PTR) return upd_row(a.rows, a.np + j);
-        else return sb + (uint64_t)((upd_cint_t *)a.dst_idx)[j] * a.row_stride;
-    };
-    V acc[NT];
-#pragma unroll
-    for (int j = 0; j < NT; j++) acc[j] = F::zero();
-    const uint64_t trow = (uint64_t)a.np * F::TWD;  // table (j0 + j, i) at tw + (j * np + i) * TWD
-    const uint32_t *tw = a.tw + (uint64_t)j0 * trow;
-    int i = 0;
-    for (; i + kDecRows <= a.np; i += kDecRows) {
-        V x[kDecRows];
-#pragma unroll
-        for (int q = 0; q < kDecRows; q++) x[q] = F::load(srow(i + q), u);
-#pragma unroll
-        for (int q = 0; q < kDecRows; q++) {
-            UpdMasks<F> mk;
-            mk.prepare(x[q]);
-#pragma unroll
-            for (int j = 0; j < NT; j++) {
-                const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)(i + q) * F::TWD);
-                mk.mul_add(acc[j], tb.v);
-            }
-        }
-    }
-    for (; i < a.np; i++) {
-        UpdMasks<F> mk;
-        mk.prepare(F::load(srow(i), u));
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-            const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)i * F::TWD);
-            mk.mul_add(acc[j], tb.v);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < NT; j++) F::store(drow(j0 + j), u, acc[j]);
-}
-
-template <class F, int NT>
-hipError_t decode_group(const DecodeRowsArgs &a, int j0, hipStream_t s) {
-    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
-    if (a.rows) {
-        hipLaunchKernelGGL((k_decode_rows<F, NT, true>), grid_x(units), dim3(256), 0, s, a, j0, 0);
-        return hipGetLastError();
-    }
-    return for_y(a.nstripes, [&](int y0, int ny) {
-        hipLaunchKernelGGL((k_decode_rows<F, NT, false>), dim3(grid_x(units).x, ny), dim3(256), 0, s, a, j0, y0);
-    });
-}
-
-template <class F>
-hipError_t decode_rows_f(const DecodeRowsArgs &a, hipStream_t s) {
-    static_assert(kDecGroup == 8, "decode_rows_f dispatches group sizes 1..8");
-    // ceil(t / kDecGroup) launches of sizes as equal as t allows (as update_f):
-    // every launch reads all present rows, so none should carry a lone row
-    const int nl = (a.t + kDecGroup - 1) / kDecGroup;
-    for (int g = 0, j0 = 0, nt = 0; g < nl; g++, j0 += nt) {
-        nt = a.t / nl + (g < a.t % nl ? 1 : 0);
-        hipError_t e;
-        switch (nt) {
-            case 1: e = decode_group<F, 1>(a, j0, s); break;
-            case 2: e = decode_group<F, 2>(a, j0, s); break;
-            case 3: e = decode_group<F, 3>(a, j0, s); break;
-            case 4: e = decode_group<F, 4>(a, j0, s); break;
-            case 5: e = decode_group<F, 5>(a, j0, s); break;
-            case 6: e = decode_group<F, 6>(a, j0, s); break;
-            case 7: e = decode_group<F, 7>(a, j0, s); break;
-            default: e = decode_group<F, 8>(a, j0, s); break;
-        }
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-}  // namespace
-
-// Unit widths by launch_update's grid rule.
-hipError_t launch_decode_rows(int bits, const DecodeRowsArgs &a, hipStream_t s) {
-    constexpr uint64_t kDecMinBlocks = 1024;
-    if (a.np <= 0 || a.t <= 0 || a.S == 0 || a.S % 64 || !a.tw) return hipErrorInvalidValue;
-    if (!a.rows && (!a.base || !a.src_idx || !a.dst_idx || a.nstripes <= 0)) return hipErrorInvalidValue;
-    const uint64_t ns = a.rows ? 1 : (uint64_t)a.nstripes;
-    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * ns;
-    const bool narrow = pick_narrow(wide_blocks < kDecMinBlocks);
-    if (bits == 16) return narrow ? decode_rows_f<F16<2>>(a, s) : decode_rows_f<F16<4>>(a, s);
-    return narrow ? decode_rows_f<F8<2>>(a, s) : decode_rows_f<F8<4>>(a, s);
-}
-
-// ---------------------------------------------------------------- direct decode, a pattern per stripe
-// k_decode_rows over a list of (stripe, descriptor) pairs
-// (rs_reconstruct_rows_dev_batch_patterns, kernels.hpp DecodeRowsPatArgs):
-// every stripe of a launch rebuilds NT rows, each from the tables and index
-// lists of its own descriptor.
-namespace {
-
-typedef __attribute__((address_space(4))) const RecStripe dec_cstripe_t;
-typedef __attribute__((address_space(4))) const RowsPattern dec_cpat_t;
-
-// List entry blockIdx.y + y0.  The entry and its descriptor are the same for
-// the whole workgroup and read-only for the launch: scalar loads through the
-// constant address space (as k_rec_lds_pat reads its descriptor).  The loop is
-// k_decode_rows's own (a copy: that kernel's 64 instantiations keep their
-// registers); np differs between the stripes of a launch but not within a
-// wave, so the loop bound is wave-uniform.  All addresses are 64-bit.
-template <class F, int NT>
-__global__ void __launch_bounds__(256, 2) k_decode_rows_pat(DecodeRowsPatArgs a, int y0) {
-    typedef typename F::Vec V;
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    dec_cstripe_t &e = ((dec_cstripe_t *)a.list)[(uint64_t)blockIdx.y + (uint64_t)y0];
-    dec_cpat_t &d = ((dec_cpat_t *)a.pat)[e.pat];
-    uint8_t *sb = a.base + (uint64_t)e.stripe * a.stripe_stride;
-    const int np = d.np;
-    const uint32_t *tw = d.tw;  // table (j, i) at tw + (j * np + i) * TWD
-    upd_cint_t *si = (upd_cint_t *)d.src_idx, *di = (upd_cint_t *)d.dst_idx;
-    auto srow = [&](int i) -> const uint8_t * { return sb + (uint64_t)si[i] * a.row_stride; };
-    V acc[NT];
-#pragma unroll
-    for (int j = 0; j < NT; j++) acc[j] = F::zero();
-    const uint64_t trow = (uint64_t)np * F::TWD;
-    int i = 0;
-    for (; i + kDecRows <= np; i += kDecRows) {
-        V x[kDecRows];
-#pragma unroll
-        for (int q = 0; q < kDecRows; q++) x[q] = F::load(srow(i + q), u);
-#pragma unroll
-        for (int q = 0; q < kDecRows; q++) {
-            UpdMasks<F> mk;
-            mk.prepare(x[q]);
-#pragma unroll
-            for (int j = 0; j < NT; j++) {
-                const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)(i + q) * F::TWD);
-                mk.mul_add(acc[j], tb.v);
-            }
-        }
-    }
-    for (; i < np; i++) {
-        UpdMasks<F> mk;
-        mk.prepare(F::load(srow(i), u));
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-            const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)i * F::TWD);
-            mk.mul_add(acc[j], tb.v);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < NT; j++) F::store(sb + (uint64_t)di[j] * a.row_stride, u, acc[j]);
-}
-
-template <class F, int NT>
-hipError_t decode_pat_group(const DecodeRowsPatArgs &a, hipStream_t s) {
-    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
-    return for_y(a.nlist, [&](int y0, int ny) {
-        hipLaunchKernelGGL((k_decode_rows_pat<F, NT>), dim3(grid_x(units).x, ny), dim3(256), 0, s, a, y0);
-    });
-}
-
-template <class F>
-hipError_t decode_rows_pat_f(const DecodeRowsPatArgs &a, hipStream_t s) {
-    static_assert(kDecGroup == 8, "decode_rows_pat_f dispatches group sizes 1..8");
-    switch (a.nt) {
-        case 1: return decode_pat_group<F, 1>(a, s);
-        case 2: return decode_pat_group<F, 2>(a, s);
-        case 3: return decode_pat_group<F, 3>(a, s);
-        case 4: return decode_pat_group<F, 4>(a, s);
-        case 5: return decode_pat_group<F, 5>(a, s);
-        case 6: return decode_pat_group<F, 6>(a, s);
-        case 7: return decode_pat_group<F, 7>(a, s);
-        default: return decode_pat_group<F, 8>(a, s);
-    }
-}
-
-}  // namespace
-
-// Unit widths by launch_decode_rows's grid rule over the list's stripes.
-hipError_t launch_decode_rows_patterns(int bits, const DecodeRowsPatArgs &a, hipStream_t s) {
-    constexpr uint64_t kDecMinBlocks = 1024;
-    if (a.nt <= 0 || a.nt > kDecGroup || a.nlist <= 0 || a.S == 0 || a.S % 64) return hipErrorInvalidValue;
-    if (!a.base || !a.pat || !a.list) return hipErrorInvalidValue;
-    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * (uint64_t)a.nlist;
-    const bool narrow = pick_narrow(wide_blocks < kDecMinBlocks);
-    if (bits == 16) return narrow ? decode_rows_pat_f<F16<2>>(a, s) : decode_rows_pat_f<F16<4>>(a, s);
-    return narrow ? decode_rows_pat_f<F8<2>>(a, s) : decode_rows_pat_f<F8<4>>(a, s);
-}
-
-// ---------------------------------------------------------------- direct decode over a list of stripes
-// k_decode_rows_pat over stripes of different sizes, each in a buffer of its
-// own (kernels.hpp DecodeRowsListArgs, rs_reconstruct_rows_dev_list).  A copy
-// of that kernel's body: k_decode_rows, k_decode_rows_pat and
-// k_decode_rows_chk keep their registers.  The grid is one-dimensional over
-// the column blocks of all entries; a workgroup finds its entry by
-// k_encode_reg_list's binary search over the prefix first_wg, then reads the
-// entry and the entry's descriptor.  Prefix, entry and descriptor are the same
-// for the whole workgroup and read-only for the launch: scalar loads through
-// the constant address space, SGPRs and no VGPRs.  A workgroup never straddles
-// two entries, so np is wave-uniform; the lanes of an entry's last workgroup
-// past the row end return (there are no barriers).  All addresses are 64-bit.
-namespace {
-
-typedef __attribute__((address_space(4))) const RowsListEntry dec_clist_t;
-
-template <class F, int NT>
-__global__ void __launch_bounds__(256, 2) k_decode_rows_list(DecodeRowsListArgs a) {
-    typedef typename F::Vec V;
-    // the entry z with first_wg[z] <= blockIdx.x < first_wg[z + 1] (gf_host.hpp encode_list_find)
-    cu32_t *fw = (cu32_t *)a.first_wg;
-    const uint32_t wg = blockIdx.x;
-    uint32_t z = 0, zh = a.nlist;
-    while (zh - z > 1) {
-        const uint32_t mid = z + (zh - z) / 2;
-        if (fw[mid] <= wg) z = mid;
-        else zh = mid;
-    }
-    dec_clist_t &e = ((dec_clist_t *)a.list)[z];
-    const uint64_t u = (uint64_t)(wg - fw[z]) * 256 + threadIdx.x;
-    if (u >= F::units(e.shard_size)) return;
-    dec_cpat_t &d = ((dec_cpat_t *)a.pat)[e.pat];
-    uint8_t *const sb = e.base;
-    const uint64_t stride = e.row_stride;
-    const int np = d.np;
-    const uint32_t *tw = d.tw;  // table (j, i) at tw + (j * np + i) * TWD
-    upd_cint_t *si = (upd_cint_t *)d.src_idx, *di = (upd_cint_t *)d.dst_idx;
-    // always inlined: left to the inliner, k_encode_reg_list's staging lambdas
-    // stayed calls, with the kernel arguments in scratch and the search in vector loads
-    auto srow = [&](int i) __attribute__((always_inline)) -> const uint8_t * { return sb + (uint64_t)si[i] * stride; };
-    V acc[NT];
-#pragma unroll
-    for (int j = 0; j < NT; j++) acc[j] = F::zero();
-    const uint64_t trow = (uint64_t)np * F::TWD;
-    int i = 0;
-    for (; i + kDecRows <= np; i += kDecRows) {
-        V x[kDecRows];
-#pragma unroll
-        for (int q = 0; q < kDecRows; q++) x[q] = F::load(srow(i + q), u);
-#pragma unroll
-        for (int q = 0; q < kDecRows; q++) {
-            UpdMasks<F> mk;
-            mk.prepare(x[q]);
-#pragma unroll
-            for (int j = 0; j < NT; j++) {
-                const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)(i + q) * F::TWD);
-                mk.mul_add(acc[j], tb.v);
-            }
-        }
-    }
-    for (; i < np; i++) {
-        UpdMasks<F> mk;
-        mk.prepare(F::load(srow(i), u));
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-            const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)i * F::TWD);
-            mk.mul_add(acc[j], tb.v);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < NT; j++) F::store(sb + (uint64_t)di[j] * stride, u, acc[j]);
-}
-
-template <class F>
-hipError_t decode_rows_list_f(const DecodeRowsListArgs &a, hipStream_t s) {
-    static_assert(kDecGroup == 8, "decode_rows_list_f dispatches group sizes 1..8");
-    const dim3 grid(a.nwg), block(256);
-    switch (a.nt) {
-        case 1: hipLaunchKernelGGL((k_decode_rows_list<F, 1>), grid, block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL((k_decode_rows_list<F, 2>), grid, block, 0, s, a); break;
-        case 3: hipLaunchKernelGGL((k_decode_rows_list<F, 3>), grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL((k_decode_rows_list<F, 4>), grid, block, 0, s, a); break;
-        case 5: hipLaunchKernelGGL((k_decode_rows_list<F, 5>), grid, block, 0, s, a); break;
-        case 6: hipLaunchKernelGGL((k_decode_rows_list<F, 6>), grid, block, 0, s, a); break;
-        case 7: hipLaunchKernelGGL((k_decode_rows_list<F, 7>), grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL((k_decode_rows_list<F, 8>), grid, block, 0, s, a); break;
-    }
-    return hipGetLastError();
-}
-
-}  // namespace
-
-// The unit width comes with the launch (gf_host.hpp make_rows_list_plan applies
-// launch_decode_rows_patterns's rule to the launch's total workgroup count).
-hipError_t launch_decode_rows_list(int bits, const DecodeRowsListArgs &a, hipStream_t s) {
-    if (!a.list || !a.first_wg || !a.pat || !a.nlist || !a.nwg || a.nwg > 0x7fffffffu) return hipErrorInvalidValue;
-    if (a.nt <= 0 || a.nt > kDecGroup) return hipErrorInvalidValue;
-    const uint32_t wide = bits == 16 ? 8192 : 4096;  // 256 lanes of 32 / 16 bytes
-    if (a.wg_bytes != wide && a.wg_bytes != wide / 2) return hipErrorInvalidValue;
-    const bool narrow = a.wg_bytes != wide;
-    if (bits == 16) return narrow ? decode_rows_list_f<F16<2>>(a, s) : decode_rows_list_f<F16<4>>(a, s);
-    return narrow ? decode_rows_list_f<F8<2>>(a, s) : decode_rows_list_f<F8<4>>(a, s);
-}
-
-// ---------------------------------------------------------------- direct decode with check equations
-// k_decode_rows_pat with NC more accumulators (kernels.hpp DecodeRowsChkArgs,
-// rs_reconstruct_rows_checked_dev_batch_patterns): the descriptor's table has
-// NT + NC rows over the same np present rows, so the loop is the same with
-// NT + NC products per prepared unit; the first NT sums are the wanted rows,
-// the last NC must be zero.
-namespace {
-
-typedef __attribute__((address_space(4))) const RowsChkPattern dec_cchk_t;
-
-// Waves per SIMD the compiler must leave room for: 2 as k_decode_rows_pat, but
-// 5 up to three accumulators, where that kernel's F16<4> variants have 91-93
-// VGPRs (96 allocated: five waves) and this one's <1, 2> came out at 97 (104
-// allocated: four waves) without the bound.
-constexpr int dec_chk_waves(int na) { return na <= 3 ? 5 : 2; }
-
-// A copy of k_decode_rows_pat's body (that kernel and its descriptor keep
-// their code and registers).  NT + NC <= kDecGroup accumulators, as there.
-// NT == 0: nothing is stored but the flag.
-template <class F, int NT, int NC>
-__global__ void __launch_bounds__(256, dec_chk_waves(NT + NC)) k_decode_rows_chk(DecodeRowsChkArgs a, int y0) {
-    typedef typename F::Vec V;
-    constexpr int NA = NT + NC;
-    static_assert(NA <= kDecGroup && NC >= 1, "accumulators of k_decode_rows_pat at most");
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    dec_cstripe_t &e = ((dec_cstripe_t *)a.list)[(uint64_t)blockIdx.y + (uint64_t)y0];
-    dec_cchk_t &d = ((dec_cchk_t *)a.pat)[e.pat];
-    uint8_t *sb = a.base + (uint64_t)e.stripe * a.stripe_stride;
-    const int np = d.np;
-    const uint32_t *tw = d.tw;  // table (j, i) at tw + (j * np + i) * TWD
-    upd_cint_t *si = (upd_cint_t *)d.src_idx, *di = (upd_cint_t *)d.dst_idx;
-    auto srow = [&](int i) -> const uint8_t * { return sb + (uint64_t)si[i] * a.row_stride; };
-    V acc[NA];
-#pragma unroll
-    for (int j = 0; j < NA; j++) acc[j] = F::zero();
-    const uint64_t trow = (uint64_t)np * F::TWD;
-    int i = 0;
-    for (; i + kDecRows <= np; i += kDecRows) {
-        V x[kDecRows];
-#pragma unroll
-        for (int q = 0; q < kDecRows; q++) x[q] = F::load(srow(i + q), u);
-#pragma unroll
-        for (int q = 0; q < kDecRows; q++) {
-            UpdMasks<F> mk;
-            mk.prepare(x[q]);
-#pragma unroll
-            for (int j = 0; j < NA; j++) {
-                const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)(i + q) * F::TWD);
-                mk.mul_add(acc[j], tb.v);
-            }
-        }
-    }
-    for (; i < np; i++) {
-        UpdMasks<F> mk;
-        mk.prepare(F::load(srow(i), u));
-#pragma unroll
-        for (int j = 0; j < NA; j++) {
-            const Tab<F> tb = load_tab<F>(tw + (uint64_t)j * trow + (uint64_t)i * F::TWD);
-            mk.mul_add(acc[j], tb.v);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < NT; j++) F::store(sb + (uint64_t)di[j] * a.row_stride, u, acc[j]);
-    uint32_t any = 0;
-#pragma unroll
-    for (int j = NT; j < NA; j++) any |= F::diff(acc[j], F::zero());
-    flag_mismatch(a.bad + (uint64_t)e.stripe, any != 0);  // one plain store per wave with a non-zero sum
-}
-
-template <class F, int NT, int NC>
-hipError_t decode_chk_group(const DecodeRowsChkArgs &a, hipStream_t s) {
-    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
-    return for_y(a.nlist, [&](int y0, int ny) {
-        hipLaunchKernelGGL((k_decode_rows_chk<F, NT, NC>), dim3(grid_x(units).x, ny), dim3(256), 0, s, a, y0);
-    });
-}
-
-template <class F, int NC>
-hipError_t decode_rows_chk_c(const DecodeRowsChkArgs &a, hipStream_t s) {
-    static_assert(kDecGroup == 8 && kDecChecksMax == 2, "decode_rows_chk_c dispatches 0..6 rows with 1..2 checks");
-    switch (a.nt) {
-        case 0: return decode_chk_group<F, 0, NC>(a, s);
-        case 1: return decode_chk_group<F, 1, NC>(a, s);
-        case 2: return decode_chk_group<F, 2, NC>(a, s);
-        case 3: return decode_chk_group<F, 3, NC>(a, s);
-        case 4: return decode_chk_group<F, 4, NC>(a, s);
-        case 5: return decode_chk_group<F, 5, NC>(a, s);
-        default: return decode_chk_group<F, 6, NC>(a, s);
-    }
-}
-
-template <class F>
-hipError_t decode_rows_chk_f(const DecodeRowsChkArgs &a, hipStream_t s) {
-    return a.nc == 1 ? decode_rows_chk_c<F, 1>(a, s) : decode_rows_chk_c<F, 2>(a, s);
-}
-
-}  // namespace
-
-// Unit widths by launch_decode_rows_patterns's rule.
-hipError_t launch_decode_rows_checked(int bits, const DecodeRowsChkArgs &a, hipStream_t s) {
-    constexpr uint64_t kDecMinBlocks = 1024;
-    if (a.nt < 0 || a.nt > kDecGroup - kDecChecksMax || a.nc < 1 || a.nc > kDecChecksMax) return hipErrorInvalidValue;
-    if (a.nlist <= 0 || a.S == 0 || a.S % 64 || !a.base || !a.pat || !a.list || !a.bad) return hipErrorInvalidValue;
-    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * (uint64_t)a.nlist;
-    const bool narrow = pick_narrow(wide_blocks < kDecMinBlocks);
-    if (bits == 16) return narrow ? decode_rows_chk_f<F16<2>>(a, s) : decode_rows_chk_f<F16<4>>(a, s);
-    return narrow ? decode_rows_chk_f<F8<2>>(a, s) : decode_rows_chk_f<F8<4>>(a, s);
-}
-
-// ---------------------------------------------------------------- syndrome scan (scrub)
-// Stored parity rows against freshly encoded ones (kernels.hpp ScanArgs):
-// k_update's shape without a product.  A stream: every byte of the 2 p rows is
-// read once, nothing is written into either set; per wave at most one flag
-// store per differing row and one 64-bit atomic minimum.
-namespace {
-
-constexpr int kScanRows = 4;  // parity rows whose two loads a lane keeps in flight (8 loads)
-
-template <class F>
-__device__ __forceinline__ void or_into(typename F::Vec &a, const typename F::Vec &b) {
-    if constexpr (F::SYM16) {
-#pragma unroll
-        for (int i = 0; i < F::W; i++) a.l[i] |= b.l[i], a.h[i] |= b.h[i];
-    } else {
-#pragma unroll
-        for (int i = 0; i < F::W; i++) a.b[i] |= b.b[i];
-    }
-}
-// Byte index, within the unit's 4 W (low) bytes, of the first symbol with a set
-// bit in m; 4 W when there is none.
-template <class F>
-__device__ __forceinline__ uint32_t first_symbol(const typename F::Vec &m) {
-    uint32_t r = 4 * F::W;
-#pragma unroll
-    for (int i = F::W - 1; i >= 0; i--) {
-        uint32_t w;
-        if constexpr (F::SYM16) w = m.l[i] | m.h[i];
-        else w = m.b[i];
-        if (w) r = 4 * i + ((uint32_t)__builtin_ctz(w) >> 3);
-    }
-    return r;
-}
-
-// PTR: rows through a.rows, else strided.  All addresses are 64-bit (row pointer + offset).
-template <class F, bool PTR>
-__global__ void __launch_bounds__(256) k_syndrome_scan(ScanArgs a) {
-    typedef typename F::Vec V;
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    auto srow = [&](int i) -> const uint8_t * {
-        if constexpr (PTR) return upd_row(a.rows, i);
-        else return a.stored + (uint64_t)i * a.stored_stride;
-    };
-    auto frow = [&](int i) -> const uint8_t * {
-        if constexpr (PTR) return upd_row(a.rows, a.p + i);
-        else return a.fresh + (uint64_t)i * a.fresh_stride;
-    };
-    V any = F::zero();
-    int i = 0;
-    for (; i + kScanRows <= a.p; i += kScanRows) {
-        V x[kScanRows], y[kScanRows];
-#pragma unroll
-        for (int q = 0; q < kScanRows; q++) {
-            x[q] = F::load(srow(i + q), u);
-            y[q] = F::load(frow(i + q), u);
-        }
-#pragma unroll
-        for (int q = 0; q < kScanRows; q++) {
-            F::xor_into(x[q], y[q]);
-            or_into<F>(any, x[q]);
-            flag_mismatch(a.rowbad + i + q, F::diff(x[q], F::zero()) != 0);
-        }
-    }
-    for (; i < a.p; i++) {
-        V x = F::load(srow(i), u);
-        F::xor_into(x, F::load(frow(i), u));
-        or_into<F>(any, x);
-        flag_mismatch(a.rowbad + i, F::diff(x, F::zero()) != 0);
-    }
-    // lanes own ascending units: the first lane that saw a difference holds the wave's minimum
-    const uint64_t m = __ballot(F::diff(any, F::zero()) != 0);
-    if (m && __lane_id() == (unsigned)(__ffsll((unsigned long long)m) - 1))
-        (void)__hip_atomic_fetch_min(a.first, (unsigned long long)(F::off(u) + first_symbol<F>(any)), __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <class F>
-hipError_t syndrome_scan_f(const ScanArgs &a, hipStream_t s) {
-    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
-    if (a.rows) hipLaunchKernelGGL((k_syndrome_scan<F, true>), grid_x(units), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_syndrome_scan<F, false>), grid_x(units), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-}  // namespace
-
-// Unit widths by launch_update's grid rule (one stripe).
-hipError_t launch_syndrome_scan(int bits, const ScanArgs &a, hipStream_t s) {
-    constexpr uint64_t kScanMinBlocks = 1024;
-    if (a.p <= 0 || a.S == 0 || a.S % 64 || !a.rowbad || !a.first) return hipErrorInvalidValue;
-    if (!a.rows && (!a.stored || !a.fresh)) return hipErrorInvalidValue;
-    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256;
-    const bool narrow = pick_narrow(wide_blocks < kScanMinBlocks);
-    if (bits == 16) return narrow ? syndrome_scan_f<F16<2>>(a, s) : syndrome_scan_f<F16<4>>(a, s);
-    return narrow ? syndrome_scan_f<F8<2>>(a, s) : syndrome_scan_f<F8<4>>(a, s);
-}
-
-// ---------------------------------------------------------------- locate of many stripes (scrub)
-// rs_locate_dev_batch (kernels.hpp ScrubListArgs): the scan over a list of
-// stripes, the pick of the two syndrome symbols the host classifies by, the
-// confirm of its candidates on the 2 p parity rows, and the repair.  A
-// descriptor is the same for the whole workgroup and read-only for the launch:
-// scalar loads through the constant address space (as k_update_list reads its
-// own).  All row addresses are 64-bit (row pointer + offset).
-namespace {
-
-static_assert(kScrubMaxList <= kMaxGridY, "one descriptor per blockIdx.y");
-
-// k_syndrome_scan's strided body (a copy: that kernel's instantiations keep
-// their registers) with the stripe's parity rows as the stored set, scratch
-// slot blockIdx.y as the fresh one, and the entry's own rowbad and first.
-template <class F>
-__global__ void __launch_bounds__(256) k_syndrome_scan_list(ScrubListArgs a) {
-    typedef typename F::Vec V;
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    const uint64_t e = blockIdx.y;
-    const uint8_t *stored = a.base + (uint64_t)((cu32_t *)a.list)[e] * a.stripe_stride + (uint64_t)a.k * a.row_stride;
-    const uint8_t *fresh = a.fresh + e * a.fresh_slot_stride;
-    int *rowbad = a.rowbad + e * (uint64_t)a.p;
-    V any = F::zero();
-    int i = 0;
-    for (; i + kScanRows <= a.p; i += kScanRows) {
-        V x[kScanRows], y[kScanRows];
-#pragma unroll
-        for (int q = 0; q < kScanRows; q++) {
-            x[q] = F::load(stored + (uint64_t)(i + q) * a.row_stride, u);
-            y[q] = F::load(fresh + (uint64_t)(i + q) * a.fresh_stride, u);
-        }
-#pragma unroll
-        for (int q = 0; q < kScanRows; q++) {
-            F::xor_into(x[q], y[q]);
-            or_into<F>(any, x[q]);
-            flag_mismatch(rowbad + i + q, F::diff(x[q], F::zero()) != 0);
-        }
-    }
-    for (; i < a.p; i++) {
-        V x = F::load(stored + (uint64_t)i * a.row_stride, u);
-        F::xor_into(x, F::load(fresh + (uint64_t)i * a.fresh_stride, u));
-        or_into<F>(any, x);
-        flag_mismatch(rowbad + i, F::diff(x, F::zero()) != 0);
-    }
-    const uint64_t m = __ballot(F::diff(any, F::zero()) != 0);
-    if (m && __lane_id() == (unsigned)(__ffsll((unsigned long long)m) - 1))
-        (void)__hip_atomic_fetch_min(a.first + e, (unsigned long long)(F::off(u) + first_symbol<F>(any)),
-                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// One lane per entry: eight byte loads at most, behind the scan on the stream.
-template <bool SYM16>
-__global__ void __launch_bounds__(256) k_syndrome_pick(ScrubListArgs a) {
-    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= (uint32_t)a.nlist) return;
-    const uint64_t first = a.first[e];
-    uint32_t e0 = 0, e1 = 0;
-    if (first < a.S) {
-        const uint8_t *stored = a.base + (uint64_t)a.list[e] * a.stripe_stride + (uint64_t)a.k * a.row_stride;
-        const uint8_t *fresh = a.fresh + (uint64_t)e * a.fresh_slot_stride;
-        auto symbol = [&](const uint8_t *row) -> uint32_t {
-            if constexpr (SYM16) {
-                // low bytes in [0, 32) of the 64-byte block, high bytes in [32, 64)
-                const uint64_t lo = (first & ~(uint64_t)63) + (first & 31);
-                return (uint32_t)row[lo] | (uint32_t)row[lo + 32] << 8;
-            } else {
-                return row[first];
-            }
-        };
-        e0 = symbol(stored) ^ symbol(fresh);
-        if (a.p > 1) e1 = symbol(stored + a.row_stride) ^ symbol(fresh + a.fresh_stride);
-    }
-    a.sym[2 * (uint64_t)e] = e0;
-    a.sym[2 * (uint64_t)e + 1] = e1;
-}
-
-constexpr int kConfRows = 4;  // parity rows whose two loads a lane keeps in flight (8 loads, as the scan)
-
-// Candidate blockIdx.y: t = scale * (P_0 ^ P'_0) is the difference of data row
-// j if the candidate is right; its masks are prepared once and shared by the
-// p products G[i][j] * t, each compared with the syndrome row P_i ^ P'_i.
-template <class F>
-__global__ void __launch_bounds__(256, 2) k_syndrome_confirm(ScrubListArgs a) {
-    typedef typename F::Vec V;
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubDescDwords;
-    const uint8_t *stored = a.base + (uint64_t)d[0] * a.stripe_stride + (uint64_t)a.k * a.row_stride;
-    const uint8_t *fresh = a.fresh + (uint64_t)d[1] * a.fresh_slot_stride;
-    const uint32_t *ctw = a.col_tw + (uint64_t)d[2] * (uint64_t)a.p * F::TWD;  // table (slot, i) at ctw + i * TWD
-    const uint32_t n = d[3];
-    UpdMasks<F> mk;
-    {
-        V e0 = F::load(stored, u);
-        F::xor_into(e0, F::load(fresh, u));
-        V t = F::zero();
-        const Tab<F> tb = load_tab<F>(a.scale_tw + (uint64_t)n * F::TWD);
-        F::mul_add(t, e0, tb.v);
-        mk.prepare(t);
-    }
-    V any = F::zero();
-    int i = 0;
-    for (; i + kConfRows <= a.p; i += kConfRows) {
-        V x[kConfRows], y[kConfRows];
-#pragma unroll
-        for (int q = 0; q < kConfRows; q++) {
-            x[q] = F::load(stored + (uint64_t)(i + q) * a.row_stride, u);
-            y[q] = F::load(fresh + (uint64_t)(i + q) * a.fresh_stride, u);
-        }
-#pragma unroll
-        for (int q = 0; q < kConfRows; q++) {
-            F::xor_into(x[q], y[q]);
-            const Tab<F> tb = load_tab<F>(ctw + (uint64_t)(i + q) * F::TWD);
-            mk.mul_add(x[q], tb.v);  // e_i ^ G[i][j] * t
-            or_into<F>(any, x[q]);
-        }
-    }
-    for (; i < a.p; i++) {
-        V x = F::load(stored + (uint64_t)i * a.row_stride, u);
-        F::xor_into(x, F::load(fresh + (uint64_t)i * a.fresh_stride, u));
-        const Tab<F> tb = load_tab<F>(ctw + (uint64_t)i * F::TWD);
-        mk.mul_add(x, tb.v);
-        or_into<F>(any, x);
-    }
-    flag_mismatch(a.bad + n, F::diff(any, F::zero()) != 0);
-}
-
-template <class F>
-__global__ void __launch_bounds__(256) k_syndrome_fix(ScrubListArgs a) {
-    typedef typename F::Vec V;
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubDescDwords;
-    uint8_t *sb = a.base + (uint64_t)d[0] * a.stripe_stride;
-    uint8_t *row = sb + (uint64_t)d[2] * a.row_stride;
-    V e0 = F::load(sb + (uint64_t)a.k * a.row_stride, u);
-    F::xor_into(e0, F::load(a.fresh + (uint64_t)d[1] * a.fresh_slot_stride, u));
-    V x = F::load(row, u);
-    const Tab<F> tb = load_tab<F>(a.scale_tw + (uint64_t)d[3] * F::TWD);
-    F::mul_add(x, e0, tb.v);
-    F::store(row, u, x);
-}
-
-bool scrub_list_ok(const ScrubListArgs &a) {
-    return a.p > 0 && a.k > 0 && a.nlist > 0 && a.nlist <= kScrubMaxList && a.S != 0 && a.S % 64 == 0 && a.base &&
-           a.fresh && a.list && a.row_stride >= a.S && a.fresh_stride >= a.S;
-}
-// Unit widths by launch_update's grid rule over the list.
-bool scrub_list_narrow(int bits, const ScrubListArgs &a) {
-    constexpr uint64_t kScrubMinBlocks = 1024;
-    const uint64_t wide_blocks = (a.S / (bits == 16 ? 32 : 16) + 255) / 256 * (uint64_t)a.nlist;
-    return pick_narrow(wide_blocks < kScrubMinBlocks);
-}
-template <class F>
-dim3 scrub_list_grid(const ScrubListArgs &a) {
-    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
-    return dim3(grid_x(units).x, (unsigned)a.nlist);
-}
-
-}  // namespace
-
-#define RS_SCRUB_LIST_LAUNCH(kernel)                                                                                \
-    do {                                                                                                            \
-        const bool narrow = scrub_list_narrow(bits, a);                                                             \
-        if (bits == 16) {                                                                                           \
-            if (narrow) hipLaunchKernelGGL(kernel<F16<2>>, scrub_list_grid<F16<2>>(a), dim3(256), 0, s, a);         \
-            else hipLaunchKernelGGL(kernel<F16<4>>, scrub_list_grid<F16<4>>(a), dim3(256), 0, s, a);                \
-        } else {                                                                                                    \
-            if (narrow) hipLaunchKernelGGL(kernel<F8<2>>, scrub_list_grid<F8<2>>(a), dim3(256), 0, s, a);           \
-            else hipLaunchKernelGGL(kernel<F8<4>>, scrub_list_grid<F8<4>>(a), dim3(256), 0, s, a);                  \
-        }                                                                                                           \
-        return hipGetLastError();                                                                                   \
-    } while (0)
-
-hipError_t launch_syndrome_scan_list(int bits, const ScrubListArgs &a, hipStream_t s) {
-    if (!scrub_list_ok(a) || !a.rowbad || !a.first) return hipErrorInvalidValue;
-    RS_SCRUB_LIST_LAUNCH(k_syndrome_scan_list);
-}
-
-hipError_t launch_syndrome_pick(int bits, const ScrubListArgs &a, hipStream_t s) {
-    if (!scrub_list_ok(a) || !a.first || !a.sym) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((a.nlist + 255) / 256));
-    if (bits == 16) hipLaunchKernelGGL(k_syndrome_pick<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_syndrome_pick<false>, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_syndrome_confirm(int bits, const ScrubListArgs &a, hipStream_t s) {
-    if (!scrub_list_ok(a) || !a.col_tw || !a.scale_tw || !a.bad) return hipErrorInvalidValue;
-    RS_SCRUB_LIST_LAUNCH(k_syndrome_confirm);
-}
-
-hipError_t launch_syndrome_fix(int bits, const ScrubListArgs &a, hipStream_t s) {
-    if (!scrub_list_ok(a) || !a.scale_tw) return hipErrorInvalidValue;
-    RS_SCRUB_LIST_LAUNCH(k_syndrome_fix);
-}
-#undef RS_SCRUB_LIST_LAUNCH
-
-// ---------------------------------------------------------------- locate of a set of shards (scrub)
-// rs_locate_set_dev_batch (kernels.hpp ScrubSetArgs): all p syndrome symbols
-// of a stripe at one position for the host's decoder, the confirm of a set of
-// up to four shards on the 2 p parity rows, and its repair.  Beside the four
-// kernels above, whose instantiations stay as they are.  Descriptors and
-// tables are wave-uniform and read-only for the launch (scalar loads); all row
-// addresses are 64-bit (row pointer + offset); no LDS.
-namespace {
-
-static_assert(kScrubSetMax == 4 && kScrubSetDescDwords >= 22, "the descriptor's fields");
-
-// Descriptor blockIdx.y, lanes stride over the parity rows.
-template <bool SYM16>
-__global__ void __launch_bounds__(256) k_syndrome_pick_rows(ScrubSetArgs a) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= (uint32_t)a.p) return;
-    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubPickDescDwords;
-    const uint64_t pos = (uint64_t)d[2] | (uint64_t)d[3] << 32;
-    uint32_t e = 0;
-    if (pos < a.S) {
-        const uint8_t *stored = a.base + (uint64_t)d[0] * a.stripe_stride + ((uint64_t)a.k + i) * a.row_stride;
-        const uint8_t *fresh = a.fresh + (uint64_t)d[1] * a.fresh_slot_stride + (uint64_t)i * a.fresh_stride;
-        auto symbol = [&](const uint8_t *row) -> uint32_t {
-            if constexpr (SYM16) {
-                // low bytes in [0, 32) of the 64-byte block, high bytes in [32, 64)
-                const uint64_t lo = (pos & ~(uint64_t)63) + (pos & 31);
-                return (uint32_t)row[lo] | (uint32_t)row[lo + 32] << 8;
-            } else {
-                return row[pos];
-            }
-        };
-        e = symbol(stored) ^ symbol(fresh);
-    }
-    a.sym[(uint64_t)blockIdx.y * (uint64_t)a.p + i] = e;
-}
-
-// D = A^-1 * e_R for this lane's unit; D[j] is zero for j >= s.
-template <class F>
-__device__ __forceinline__ void set_diffs(const ScrubSetArgs &a, cu32_t *d, const uint8_t *stored, const uint8_t *fresh,
-                                          uint64_t u, int s, typename F::Vec (&D)[kScrubSetMax]) {
-    typedef typename F::Vec V;
-    V eR[kScrubSetMax];
-#pragma unroll
-    for (int r = 0; r < kScrubSetMax; r++) {
-        eR[r] = F::zero();
-        if (r < s) {
-            const uint64_t i = d[8 + r];
-            eR[r] = F::load(stored + i * a.row_stride, u);
-            F::xor_into(eR[r], F::load(fresh + i * a.fresh_stride, u));
-        }
-    }
-    const uint32_t *itw = a.inv_tw + (uint64_t)d[16] * F::TWD;
-#pragma unroll
-    for (int j = 0; j < kScrubSetMax; j++) {
-        D[j] = F::zero();
-        if (j < s) {
-#pragma unroll
-            for (int r = 0; r < kScrubSetMax; r++) {
-                if (r < s) {
-                    const Tab<F> tb = load_tab<F>(itw + (uint64_t)(s * j + r) * F::TWD);
-                    F::mul_add(D[j], eR[r], tb.v);
-                }
-            }
-        }
-    }
-}
-
-// Candidate blockIdx.y: the masks of the s differences are prepared once and
-// shared by the p rows; row i outside J_p must satisfy e_i == sum_j G[i][J_d[j]] * D_j.
-// A row of J_p is not part of the test; whether it differs from its right
-// content goes into `used`, as whether D_j is non-zero does.
-template <class F>
-__global__ void __launch_bounds__(256, 2) k_syndrome_confirm_set(ScrubSetArgs a) {
-    typedef typename F::Vec V;
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubSetDescDwords;
-    const uint8_t *stored = a.base + (uint64_t)d[0] * a.stripe_stride + (uint64_t)a.k * a.row_stride;
-    const uint8_t *fresh = a.fresh + (uint64_t)d[1] * a.fresh_slot_stride;
-    const uint32_t n = d[2];
-    const int s = (int)d[3];
-    const uint32_t x0 = d[12], x1 = d[13], x2 = d[14], x3 = d[15];
-    int *used = a.used + (uint64_t)n * 8;
-    UpdMasks<F> mk[kScrubSetMax];
-    const uint32_t *ctw[kScrubSetMax];
-    {
-        V D[kScrubSetMax];
-        set_diffs<F>(a, d, stored, fresh, u, s, D);
-#pragma unroll
-        for (int j = 0; j < kScrubSetMax; j++) {
-            mk[j].prepare(D[j]);
-            ctw[j] = a.col_tw + (uint64_t)d[4 + j] * (uint64_t)a.p * F::TWD;  // table (slot, i) at ctw + i * TWD
-            if (j < s) flag_mismatch(used + j, F::diff(D[j], F::zero()) != 0);
-        }
-    }
-    V any = F::zero();
-    auto row = [&](V &x, int i) {  // x = e_i on entry
-#pragma unroll
-        for (int j = 0; j < kScrubSetMax; j++) {
-            if (j < s) {
-                const Tab<F> tb = load_tab<F>(ctw[j] + (uint64_t)i * F::TWD);
-                mk[j].mul_add(x, tb.v);
-            }
-        }
-        const uint32_t ui = (uint32_t)i;
-        if (ui == x0 || ui == x1 || ui == x2 || ui == x3) {
-            const int q = ui == x0 ? 0 : ui == x1 ? 1 : ui == x2 ? 2 : 3;
-            flag_mismatch(used + 4 + q, F::diff(x, F::zero()) != 0);
-        } else {
-            or_into<F>(any, x);
-        }
-    };
-    int i = 0;
-    for (; i + kConfRows <= a.p; i += kConfRows) {
-        V x[kConfRows], y[kConfRows];
-#pragma unroll
-        for (int q = 0; q < kConfRows; q++) {
-            x[q] = F::load(stored + (uint64_t)(i + q) * a.row_stride, u);
-            y[q] = F::load(fresh + (uint64_t)(i + q) * a.fresh_stride, u);
-        }
-#pragma unroll
-        for (int q = 0; q < kConfRows; q++) {
-            F::xor_into(x[q], y[q]);
-            row(x[q], i + q);
-        }
-    }
-    for (; i < a.p; i++) {
-        V x = F::load(stored + (uint64_t)i * a.row_stride, u);
-        F::xor_into(x, F::load(fresh + (uint64_t)i * a.fresh_stride, u));
-        row(x, i);
-    }
-    // lanes own ascending units: the first lane that saw a failure holds the wave's minimum
-    const uint64_t m = __ballot(F::diff(any, F::zero()) != 0);
-    if (m && __lane_id() == (unsigned)(__ffsll((unsigned long long)m) - 1)) {
-        // flag_mismatch's body on the ballot the atomic minimum needs anyway (set stays set)
-        if (__hip_atomic_load(a.bad + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
-            __hip_atomic_store(a.bad + n, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        (void)__hip_atomic_fetch_min(a.fail + n, (unsigned long long)(F::off(u) + first_symbol<F>(any)), __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// The confirmed candidate blockIdx.y: D again, then the data rows of J_d and
-// the parity rows of J_p in place.  R and J_p are disjoint and R holds parity
-// rows only, so no row that D is formed from is written.
-template <class F>
-__global__ void __launch_bounds__(256, 2) k_syndrome_fix_set(ScrubSetArgs a) {
-    typedef typename F::Vec V;
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubSetDescDwords;
-    uint8_t *sb = a.base + (uint64_t)d[0] * a.stripe_stride;
-    uint8_t *stored = sb + (uint64_t)a.k * a.row_stride;
-    const uint8_t *fresh = a.fresh + (uint64_t)d[1] * a.fresh_slot_stride;
-    const int s = (int)d[3];
-    const uint32_t wr = d[21];
-    V D[kScrubSetMax];
-    set_diffs<F>(a, d, stored, fresh, u, s, D);
-#pragma unroll
-    for (int j = 0; j < kScrubSetMax; j++) {
-        if (j < s && (wr >> j & 1)) {
-            uint8_t *r = sb + (uint64_t)d[17 + j] * a.row_stride;
-            V x = F::load(r, u);
-            F::xor_into(x, D[j]);
-            F::store(r, u, x);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < kScrubSetMax; q++) {
-        const uint32_t i = d[12 + q];
-        if (i < (uint32_t)a.p && (wr >> (4 + q) & 1)) {
-            V x = F::load(fresh + (uint64_t)i * a.fresh_stride, u);
-#pragma unroll
-            for (int j = 0; j < kScrubSetMax; j++) {
-                if (j < s) {
-                    const uint32_t *ctw = a.col_tw + ((uint64_t)d[4 + j] * (uint64_t)a.p + i) * F::TWD;
-                    const Tab<F> tb = load_tab<F>(ctw);
-                    F::mul_add(x, D[j], tb.v);
-                }
-            }
-            F::store(stored + (uint64_t)i * a.row_stride, u, x);
-        }
-    }
-}
-
-// The confirmed candidate blockIdx.y of a checked rebuild: D as above, the
-// survivors T in place, then the stripe's e missing rows, kConfRows loads in
-// flight, each ^= sum_j c[x][T[j]] * D_j through masks prepared once.  D is
-// complete (every row of R loaded) before the first store and a lane owns its
-// unit in every row, so a row of R that is also written is read first.
-template <class F>
-__global__ void __launch_bounds__(256, 2) k_syndrome_fix_present(ScrubPresentArgs pa) {
-    typedef typename F::Vec V;
-    const ScrubSetArgs &a = pa.set;
-    const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= F::units(a.S)) return;
-    cu32_t *d = (cu32_t *)a.list + (uint64_t)blockIdx.y * kScrubSetDescDwords;
-    uint8_t *sb = a.base + (uint64_t)d[0] * a.stripe_stride;
-    const uint8_t *stored = sb + (uint64_t)a.k * a.row_stride;
-    const uint8_t *fresh = a.fresh + (uint64_t)d[1] * a.fresh_slot_stride;
-    const int s = (int)d[3];
-    const uint32_t wr = d[21];
-    UpdMasks<F> mk[kScrubSetMax];
-    {
-        V D[kScrubSetMax];
-        set_diffs<F>(a, d, stored, fresh, u, s, D);
-#pragma unroll
-        for (int j = 0; j < kScrubSetMax; j++) {
-            mk[j].prepare(D[j]);
-            if (j < s && (wr >> j & 1)) {
-                uint8_t *r = sb + (uint64_t)d[17 + j] * a.row_stride;
-                V x = F::load(r, u);
-                F::xor_into(x, D[j]);
-                F::store(r, u, x);
-            }
-        }
-    }
-    const int ne = (int)d[12];
-    cu32_t *rows = (cu32_t *)pa.rows + d[13];
-    const uint32_t *ftw = pa.fix_tw + (uint64_t)d[14] * F::TWD;
-    auto terms = [&](V &x, int q) {
-#pragma unroll
-        for (int j = 0; j < kScrubSetMax; j++) {
-            if (j < s) {
-                const Tab<F> tb = load_tab<F>(ftw + ((uint64_t)q * (uint64_t)s + j) * F::TWD);
-                mk[j].mul_add(x, tb.v);
-            }
-        }
-    };
-    int q = 0;
-    for (; q + kConfRows <= ne; q += kConfRows) {
-        V x[kConfRows];
-        uint8_t *r[kConfRows];
-#pragma unroll
-        for (int i = 0; i < kConfRows; i++) {
-            r[i] = sb + (uint64_t)rows[q + i] * a.row_stride;
-            x[i] = F::load(r[i], u);
-        }
-#pragma unroll
-        for (int i = 0; i < kConfRows; i++) {
-            terms(x[i], q + i);
-            F::store(r[i], u, x[i]);
-        }
-    }
-    for (; q < ne; q++) {
-        uint8_t *r = sb + (uint64_t)rows[q] * a.row_stride;
-        V x = F::load(r, u);
-        terms(x, q);
-        F::store(r, u, x);
-    }
-}
-
-bool scrub_set_ok(const ScrubSetArgs &a) {
-    return a.p > 0 && a.k > 0 && a.nlist > 0 && a.nlist <= kScrubMaxList && a.S != 0 && a.S % 64 == 0 && a.base &&
-           a.fresh && a.list && a.row_stride >= a.S && a.fresh_stride >= a.S;
-}
-// Unit widths by scrub_list_narrow's rule over the descriptors.
-bool scrub_set_narrow(int bits, const ScrubSetArgs &a) {
-    ScrubListArgs l{};
-    l.S = a.S;
-    l.nlist = a.nlist;
-    return scrub_list_narrow(bits, l);
-}
-template <class F>
-dim3 scrub_set_grid(const ScrubSetArgs &a) {
-    const uint64_t units = F::SYM16 ? (a.S >> 6) * (8 / F::W) : a.S / (4 * F::W);
-    return dim3(grid_x(units).x, (unsigned)a.nlist);
-}
-
-}  // namespace
-
-#define RS_SCRUB_SET_LAUNCH(kernel)                                                                                 \
-    do {                                                                                                            \
-        const bool narrow = scrub_set_narrow(bits, a);                                                              \
-        if (bits == 16) {                                                                                           \
-            if (narrow) hipLaunchKernelGGL(kernel<F16<2>>, scrub_set_grid<F16<2>>(a), dim3(256), 0, s, a);          \
-            else hipLaunchKernelGGL(kernel<F16<4>>, scrub_set_grid<F16<4>>(a), dim3(256), 0, s, a);                 \
-        } else {                                                                                                    \
-            if (narrow) hipLaunchKernelGGL(kernel<F8<2>>, scrub_set_grid<F8<2>>(a), dim3(256), 0, s, a);            \
-            else hipLaunchKernelGGL(kernel<F8<4>>, scrub_set_grid<F8<4>>(a), dim3(256), 0, s, a);                   \
-        }                                                                                                           \
-        return hipGetLastError();                                                                                   \
-    } while (0)
-
-hipError_t launch_syndrome_pick_rows(int bits, const ScrubSetArgs &a, hipStream_t s) {
-    if (!scrub_set_ok(a) || !a.sym) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((a.p + 255) / 256), (unsigned)a.nlist);
-    if (bits == 16) hipLaunchKernelGGL(k_syndrome_pick_rows<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_syndrome_pick_rows<false>, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_syndrome_confirm_set(int bits, const ScrubSetArgs &a, hipStream_t s) {
-    if (!scrub_set_ok(a) || !a.col_tw || !a.inv_tw || !a.bad || !a.used || !a.fail) return hipErrorInvalidValue;
-    RS_SCRUB_SET_LAUNCH(k_syndrome_confirm_set);
-}
-
-hipError_t launch_syndrome_fix_set(int bits, const ScrubSetArgs &a, hipStream_t s) {
-    if (!scrub_set_ok(a) || !a.col_tw || !a.inv_tw) return hipErrorInvalidValue;
-    RS_SCRUB_SET_LAUNCH(k_syndrome_fix_set);
-}
-#undef RS_SCRUB_SET_LAUNCH
-
-hipError_t launch_syndrome_fix_present(int bits, const ScrubPresentArgs &pa, hipStream_t s) {
-    const ScrubSetArgs &a = pa.set;
-    if (!scrub_set_ok(a) || !a.inv_tw || !pa.rows || !pa.fix_tw) return hipErrorInvalidValue;
-    const bool narrow = scrub_set_narrow(bits, a);
-    if (bits == 16) {
-        if (narrow) hipLaunchKernelGGL(k_syndrome_fix_present<F16<2>>, scrub_set_grid<F16<2>>(a), dim3(256), 0, s, pa);
-        else hipLaunchKernelGGL(k_syndrome_fix_present<F16<4>>, scrub_set_grid<F16<4>>(a), dim3(256), 0, s, pa);
-    } else {
-        if (narrow) hipLaunchKernelGGL(k_syndrome_fix_present<F8<2>>, scrub_set_grid<F8<2>>(a), dim3(256), 0, s, pa);
-        else hipLaunchKernelGGL(k_syndrome_fix_present<F8<4>>, scrub_set_grid<F8<4>>(a), dim3(256), 0, s, pa);
-    }
-    return hipGetLastError();
 }
 
 }  // namespace rs

@@ -1,5 +1,5 @@
 """GPU tests of the checked rebuild (rs_reconstruct_checked_dev_batch_patterns;
-kernels.hip k_syndrome_fix_present, with k_syndrome_confirm_set on the check
+stream_kernels.hip k_syndrome_fix_present, with k_syndrome_confirm_set on the check
 matrix's columns) on oracle-encoded stripes in a padded slab, one erasure
 pattern per stripe: every stripe gets exactly the verdict its tampering calls
 for, a located stripe ends bit for bit as the codeword, and everything else is

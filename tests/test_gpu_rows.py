@@ -1,7 +1,7 @@
 """GPU tests of the selective reconstruct (rs_reconstruct_rows_dev,
 rs_reconstruct_rows_dev_batch, rs_reconstruct_rows) under both tiers: the
 restricted transform (rows_direct 0) and the direct decode kernel (rows_direct
-1, kernels.hip k_decode_rows).  The wanted rows must be, bit for bit, what the
+1, stream_kernels.hip k_decode_rows).  The wanted rows must be, bit for bit, what the
 oracle's Reconstruct puts there for the same present rows, and no other byte
 may change.
 """

@@ -1,5 +1,5 @@
 """GPU tests of the degraded read of a list of stripes of different sizes
-(rs_reconstruct_rows_dev_list; kernels.hip k_decode_rows_list) against the
+(rs_reconstruct_rows_dev_list; stream_kernels.hip k_decode_rows_list) against the
 oracle: after a call the whole buffer that holds the stripes must be, bit for
 bit, the expected image -- a fresh oracle's Reconstruct per stripe in the rows
 that are missing and required, and every other byte as it was: present rows,

@@ -1,5 +1,5 @@
 """GPU tests of the scrub (rs_verify_dev_batch_map, rs_locate_dev,
-rs_scrub_dev_batch; kernels.hip k_syndrome_scan and the per-stripe mismatch
+rs_scrub_dev_batch; stream_kernels.hip k_syndrome_scan and the per-stripe mismatch
 words of the verify kernels) on oracle-encoded stripes: a tampered shard must
 be named, repaired bit for bit, and nothing else written.
 """

@@ -1,4 +1,4 @@
-"""GPU tests of the batched locate (rs_locate_dev_batch; kernels.hip
+"""GPU tests of the batched locate (rs_locate_dev_batch; stream_kernels.hip
 k_syndrome_scan_list, k_syndrome_pick, k_syndrome_confirm, k_syndrome_fix) and
 of rs_scrub_dev_batch routed through it, on oracle-encoded stripes in a padded
 slab: every listed stripe gets rs_locate_dev's verdict, a located shard is

@@ -1,5 +1,5 @@
 """GPU tests of the set locate (rs_locate_set_dev_batch, rs_scrub_set_dev_batch;
-kernels.hip k_syndrome_pick_rows, k_syndrome_confirm_set, k_syndrome_fix_set)
+stream_kernels.hip k_syndrome_pick_rows, k_syndrome_confirm_set, k_syndrome_fix_set)
 on oracle-encoded stripes in a padded slab: every listed stripe gets exactly
 the set of shards that was tampered with, a located set is repaired bit for
 bit, and nothing else -- padding, clean stripes, unlocated stripes, corrupt

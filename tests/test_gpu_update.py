@@ -1,5 +1,5 @@
 """GPU tests of the incremental parity update (rs_update_dev, rs_encode_idx_dev,
-rs_update_dev_batch; kernels.hip k_update) against the oracle: after an update
+rs_update_dev_batch; stream_kernels.hip k_update) against the oracle: after an update
 the parity rows must be, bit for bit, the oracle's encode of the new data.
 """
 import numpy as np

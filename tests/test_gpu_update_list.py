@@ -1,5 +1,5 @@
 """GPU tests of the batched update from a list of changed rows, a different set
-per stripe (rs_update_dev_batch_list; kernels.hip k_update_list) against the
+per stripe (rs_update_dev_batch_list; stream_kernels.hip k_update_list) against the
 oracle: afterwards every named stripe must be, bit for bit, the new data and
 the oracle's encode of it, and nothing else may have been written.
 """

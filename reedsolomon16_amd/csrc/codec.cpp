@@ -8,492 +8,9 @@
 //   Verify       leopard16.go:361-387
 //   reconstruct  leopard16.go:390-430
 // GF(2^8) twins: leopard8.go:141-150, 415-436, 439-480.
-#include <hip/hip_runtime.h>
+#include <functional>
 
-#include <algorithm>
-#include <array>
-#include <atomic>
-#include <cstdlib>
-#include <cstring>
-#include <list>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
-
-#include "../../include/rs_mi355x.h"
-#include "gf_host.hpp"
-#include "kernels.hpp"
-#include "multi.hpp"
-#include "schedule.hpp"
-
-using namespace rs;
-
-namespace {
-
-constexpr int kMaxRegLogM = 5;  // m <= 32: fused register kernel
-constexpr int kMaxLdsLogN = 8;  // n (or m) <= 256: LDS-resident transform kernels
-constexpr int kHostBufs = 3;    // staging slabs of the host-resident pipeline
-constexpr uint64_t kHostSegTarget = 32ull << 20;  // bytes copied in per segment (scripts/host_seg_sweep.py: 256 KiB rows at 128+32)
-
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;  // elements
-    hipError_t ensure(size_t want) {
-        if (want <= n) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        hipError_t e = hipMalloc(&p, want * sizeof(T));
-        if (e == hipSuccess) n = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-// Pinned host memory grown on demand, the host-side twin of DevBuf.  Neither
-// has a destructor: ~rs_codec releases them while its DeviceGuard is alive.
-struct PinnedBuf {
-    uint8_t *p = nullptr;
-    size_t n = 0;  // bytes
-    hipError_t ensure(size_t want) {
-        if (want <= n) return hipSuccess;
-        hipError_t e = p ? hipHostFree(p) : hipSuccess;
-        if (e != hipSuccess) return e;
-        p = nullptr;
-        n = 0;
-        e = hipHostMalloc((void **)&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) n = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// Scoped hipSetDevice that restores the caller's device.
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        (void)hipGetDevice(&prev);
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-#define HIP_TRY(x)                                   \
-    do {                                             \
-        hipError_t e_ = (x);                         \
-        if (e_ != hipSuccess) return RS_ERR_DEVICE;  \
-    } while (0)
-
-// Grow `dst` to the size of a host table and copy the table there.
-template <class T>
-int upload(DevBuf<T> &dst, const std::vector<T> &src) {
-    HIP_TRY(dst.ensure(src.size()));
-    HIP_TRY(hipMemcpy(dst.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return RS_OK;
-}
-
-// Host half of a reconstruct (leopard16.go:432-568) for one erasure pattern:
-// which shard feeds each of the n work rows, the input scalings (errLocs),
-// which shards are rebuilt from which work row, and their output scalings.
-struct RecPlan {
-    std::vector<int> src_shard;   // n entries: shard index feeding work row r, or -1 (zero row)
-    std::vector<int> dst_shard;   // shards to rebuild, ascending
-    std::vector<int> pos;         // work row each rebuilt shard is read from
-    std::vector<uint32_t> tw_in, tw_out;
-};
-
-// The streams that launched with a cached device blob.  One event per stream,
-// recorded after each such launch: an eviction frees the blob only after the
-// last launch on every one of those streams (one event alone would cover only
-// the latest).
-struct StreamUses {
-    std::vector<std::pair<hipStream_t, hipEvent_t>> used;
-    hipError_t mark_used(hipStream_t s) {
-        for (auto &u : used)
-            if (u.first == s) return hipEventRecord(u.second, s);
-        // a new stream: first drop the streams whose last launch has finished
-        // (short-lived caller streams would otherwise pile up events)
-        for (size_t i = 0; i < used.size();) {
-            if (hipEventQuery(used[i].second) == hipSuccess) {
-                (void)hipEventDestroy(used[i].second);
-                used[i] = used.back();
-                used.pop_back();
-            } else {
-                i++;
-            }
-        }
-        hipEvent_t ev = nullptr;
-        hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (e != hipSuccess) return e;
-        used.emplace_back(s, ev);
-        return hipEventRecord(ev, s);
-    }
-    // Host wait for the last launch on every stream (before the blob is freed).
-    void drain() {
-        for (auto &u : used) {
-            (void)hipEventSynchronize(u.second);
-            (void)hipEventDestroy(u.second);
-        }
-        used.clear();
-    }
-};
-
-// A cached reconstruct plan with its per-pattern tables (scale-in / reveal
-// images, rebuilt-row positions) resident in HBM: rs_reconstruct_dev of a
-// pattern seen before uploads only its row pointers.
-struct DevPlan : StreamUses {
-    RecPlan pl;
-    DevBuf<uint8_t> blob;
-    const uint32_t *tw_in = nullptr, *tw_out = nullptr;
-    const int *pos = nullptr;
-    const int *src_idx = nullptr, *dst_idx = nullptr;  // pl.src_shard / pl.dst_shard (strided launches)
-    uint32_t need[8] = {};
-    const uint32_t *need_w = nullptr;  // the revealed-row mask, n / 32 words (kernels read it for n > 256)
-    const int *rev = nullptr;          // output index of each work row, -1: not revealed (n > 256)
-    ~DevPlan() {
-        drain();
-        blob.release();
-    }
-};
-
-// The device tables of a set of erasure patterns
-// (rs_reconstruct_dev_batch_patterns): per pattern what a DevPlan holds (less
-// pos, which the LDS-resident kernels do not read), in one blob, and the array
-// of descriptors that point into it; a stripe names its pattern by descriptor index.
-struct PatternSet : StreamUses {
-    DevBuf<uint8_t> blob;
-    const RecPattern *desc = nullptr;  // device array, one per pattern of the set
-    // codecs of the bit-sliced n = 256 decoder: the phase-1 wave plan the set's
-    // patterns share (each descriptor holds its own phase-3 placement)
-    bool bs_ok = false;
-    uint64_t code1[3] = {};
-    ~PatternSet() {
-        drain();
-        blob.release();
-    }
-};
-
-// The device tables of an incremental update for one ordered list of changed
-// data rows: p x t multiply-by-G[i][idx[j]] images (make_update_tables) and
-// the indices themselves (the strided kernel reads them).
-struct UpdPlan : StreamUses {
-    DevBuf<uint8_t> blob;
-    const uint32_t *tw = nullptr;
-    const int *idx = nullptr;
-    ~UpdPlan() {
-        drain();
-        blob.release();
-    }
-};
-
-// The device tables of a set of changed columns (rs_update_dev_batch_list):
-// per column of `cols` (ascending) its p x 1 update tables, slot by slot
-// (gf_host.hpp make_update_columns).
-struct UpdColSet : StreamUses {
-    DevBuf<uint8_t> blob;
-    const uint32_t *tw = nullptr;
-    std::vector<int> cols;
-    ~UpdColSet() {
-        drain();
-        blob.release();
-    }
-};
-
-// The device tables of a direct decode (rs_reconstruct_rows_dev*) for one
-// (present, rows rebuilt) pair: t x np multiply-by-D[j][i] images
-// (make_decode_tables) and the present / rebuilt shard indices.
-struct RowsPlan : StreamUses {
-    DevBuf<uint8_t> blob;
-    const uint32_t *tw = nullptr;
-    const int *src_idx = nullptr, *dst_idx = nullptr;  // device copies of src / dst (strided launches)
-    std::vector<int> src, dst;                         // present shards, rebuilt shards, ascending
-    ~RowsPlan() {
-        drain();
-        blob.release();
-    }
-};
-
-// The device tables of a set of (present, rows rebuilt) pairs
-// (rs_reconstruct_rows_dev_batch_patterns' direct tier): per pair what a
-// RowsPlan holds, in one blob (gf_host.hpp make_rows_set), and the array of
-// descriptors that point into it.
-struct RowsSet : StreamUses {
-    DevBuf<uint8_t> blob;
-    const RowsPattern *desc = nullptr;  // device array
-    std::vector<int> first_desc;        // pair q's descriptors: [first_desc[q], first_desc[q + 1])
-    std::vector<int> desc_t;            // rows each descriptor rebuilds (1..kDecGroup)
-    ~RowsSet() {
-        drain();
-        blob.release();
-    }
-};
-
-// The same with each pair's check tables behind its decode tables
-// (rs_reconstruct_rows_checked_dev_batch_patterns; gf_host.hpp
-// make_rows_chk_set): one descriptor per pair.
-struct RowsChkSet : StreamUses {
-    DevBuf<uint8_t> blob;
-    const RowsChkPattern *desc = nullptr;  // device array
-    ~RowsChkSet() {
-        drain();
-        blob.release();
-    }
-};
-
-// A small bounded LRU, most recent first.  find() moves a hit to the front;
-// put() inserts at the front and evicts past the cache's capacity, which runs
-// the evicted value's destructor (a DevPlan / UpdPlan waits there for its last
-// launch on every stream).  A pointer handed out stays valid until the next
-// put() into the same cache (calls are serialized by the codec mutex).
-template <class K, class V, size_t Cap>
-struct Lru {
-    std::list<std::pair<K, V>> items;
-    V *find(const K &key) {
-        auto it = std::find_if(items.begin(), items.end(), [&](const auto &e) { return e.first == key; });
-        if (it == items.end()) return nullptr;
-        items.splice(items.begin(), items, it);
-        return &items.front().second;
-    }
-    V *put(K key, V val) {
-        items.emplace_front(std::move(key), std::move(val));
-        if (items.size() > Cap) items.pop_back();
-        return &items.front().second;
-    }
-};
-
-}  // namespace
-
-struct rs_codec {
-    int bits = 16, k = 0, p = 0, total = 0, m = 1, logm = 0, device = 0;
-    const Field *F = nullptr;
-    int twd = kTwDwords16;
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-
-    // encode plan
-    bool enc_ok = false, dev_ready = false;
-    int nchunks = 0;
-    std::vector<uint32_t> enc_ifft_logs, enc_fft_logs;
-    DevBuf<uint32_t> tw_ifft, tw_fft;
-    bool split_ok = false;            // half-wave split kernel available (GF(2^16), 4 <= m <= 32)
-    bool bs_ok = false;               // bit-sliced kernel covers (k, p) (GF(2^16), m = 16 or 32)
-    int cus = 0;                      // compute units of the device (persistent grids)
-    DevBuf<uint32_t> tws_ifft, tws_fft;
-    // LDS-kernel encode (GF(2^16), even log m): the final FFT's subfield tables
-    // and the coordinate-change map (EncodeArgs::tw_fft_sub / tw_dmap)
-    DevBuf<uint32_t> tw_fft_sub, tw_dmap;
-    bool fft_sub = false;  // its twiddle images (schedule.hpp EncodeSplit)
-    // ... and the chunk IFFT passes from ifft_nff[c] on (EncodeArgs::tw_ifft_sub)
-    DevBuf<uint32_t> tw_ifft_sub;
-    DevBuf<int> ifft_nff;
-    bool ifft_sub = false;
-    std::string path;
-
-    // decode plan (built on first reconstruct)
-    bool dec_built = false, dec_ok = false;
-    bool dec_sub = false;  // LDS reconstruct runs its transforms in subfield coordinates
-    int n = 0, logn = 0;
-    std::vector<uint32_t> dec_ifft_logs, dec_fft_logs;  // decode_schedule's logs (the direct decode's coefficients)
-    DevBuf<uint32_t> dtw_ifft, dtw_fft;
-    // n = 512..2048: subfield tables of the passes that run in subfield
-    // coordinates (RecArgs::tw_ifft_sub / tw_fft_sub, kernels.hip BigSub)
-    bool dec_big_sub = false;
-    DevBuf<uint32_t> dtw_ifft_sub, dtw_fft_sub, dec_dmap;
-
-    // scratch shared by the codec's calls (row table, multi-pass work rows,
-    // reconstruct blob).  Calls may run on different caller streams and the
-    // device-resident encodes return before their kernels finish, so every call
-    // records scratch_ev after its last launch, and the next call orders itself
-    // behind it (stream wait) before touching the scratch (host wait before a
-    // host-side overwrite or a reallocation).
-    hipEvent_t scratch_ev = nullptr;
-    bool scratch_used = false;
-    hipStream_t scratch_stream = nullptr;  // stream of the last scratch user
-    DevBuf<uint8_t> work;
-    DevBuf<uint8_t *> rows;         // row-pointer table (non-strided inputs)
-    std::vector<uint8_t *> rows_host;
-    int *hflag = nullptr, *dflag = nullptr;  // verify mismatch word: device word + pinned host readback
-    // per-call reconstruct inputs, packed into one blob and uploaded with one copy
-    DevBuf<uint8_t> rc_blob;
-    PinnedBuf rc_host;  // pinned staging of the blob
-    const uint8_t **rc_src = nullptr;
-    uint8_t **rc_dst = nullptr;
-    uint32_t *rc_tw_in = nullptr, *rc_tw_out = nullptr;
-    int *rc_pos = nullptr;
-
-    // reconstruct plans keyed by (erasure pattern, recover_all) (bounded LRU)
-    Lru<std::vector<uint8_t>, RecPlan, 16> plan_cache;
-    // device-resident plans of rs_reconstruct_dev (same key), and a ring of
-    // per-call row-pointer slots (pinned host + HBM), each reusable once the
-    // launch that read it has finished (ring_ev)
-    Lru<std::vector<uint8_t>, std::unique_ptr<DevPlan>, 16> dplan_cache;
-    static constexpr int kRing = 8;
-    DevBuf<uint8_t> ring_dev;
-    PinnedBuf ring_host;
-    size_t ring_slot = 0;  // bytes per slot
-    hipEvent_t ring_ev[kRing] = {};
-    bool ring_used[kRing] = {};
-    int ring_next = 0;
-    // incremental-update tables keyed by the ordered list of changed indices
-    // (bounded LRU, as dplan_cache); their row pointers use the ring above
-    Lru<std::vector<int>, std::unique_ptr<UpdPlan>, 16> uplan_cache;
-    // column sets of rs_update_dev_batch_list keyed by the sorted distinct
-    // changed columns of a call (or of a pass of it); a set that holds every
-    // column asked for serves the call too
-    Lru<std::vector<int>, std::unique_ptr<UpdColSet>, 4> ucol_cache;
-    // direct-decode tables keyed by (erasure pattern, rows rebuilt), likewise
-    Lru<std::vector<uint8_t>, std::unique_ptr<RowsPlan>, 16> rowsplan_cache;
-    // pattern sets keyed by (recover_all, the set's erasure patterns in order);
-    // one set holds every pattern of a call (or of a stripe range of it), so a
-    // rotated layout's 160 patterns take one slot here and none of dplan_cache
-    Lru<std::vector<uint8_t>, std::unique_ptr<PatternSet>, 4> pset_cache;
-    // rows sets keyed by their (present, rows rebuilt) pairs in order of first
-    // use: the direct tier's counterpart of pset_cache
-    Lru<std::vector<uint8_t>, std::unique_ptr<RowsSet>, 4> rset_cache;
-    // checked rows sets keyed by the check count and their (present, rows
-    // rebuilt) pairs, and the per-stripe flags of a checked call with their
-    // pinned readback (the call waits for its launches before it returns, under
-    // the codec mutex: no other call sees the two buffers in use)
-    Lru<std::vector<uint8_t>, std::unique_ptr<RowsChkSet>, 4> rchk_cache;
-    DevBuf<int> rchk_bad;
-    PinnedBuf rchk_host;
-    // scrub (rs_verify_dev_batch_map / rs_locate_dev / rs_scrub_dev_batch): the
-    // ratio map of the data shards (built on the first locate), the device
-    // tables of a repaired row keyed by its data shard (UpdPlan::tw: the three
-    // make_repair_tables images), p + 1 scratch rows (the recomputed parity and
-    // the repaired row), and the per-stripe flags / scan results with their
-    // pinned readback.  The buffers are codec scratch (scratch_acquire / _release).
-    bool locate_built = false;
-    LocateMap locate_map;
-    Lru<int, std::unique_ptr<UpdPlan>, 16> fixplan_cache;
-    DevBuf<uint8_t> scrub_rows, scrub_dev;
-    PinnedBuf scrub_host;
-    // rs_locate_dev_batch: the scan, pick and confirm results of a pass with
-    // their pinned readback (the passes' recomputed parity rows are scrub_rows)
-    DevBuf<uint8_t> scrub_list_dev;
-    PinnedBuf scrub_list_host;
-    // rs_locate_set_dev_batch: the weights and locators of the per-symbol
-    // decoder (built on the first use, like the ratio map), and the picked
-    // symbols and confirm results of a pass with their pinned readback
-    bool locate_set_built = false;
-    LocateSet locate_set;
-    DevBuf<uint8_t> scrub_set_dev;
-    PinnedBuf scrub_set_host;
-    // rs_reconstruct_checked_dev_batch_patterns: all p weight rows and the
-    // locators of the errors-and-erasures decoder (built on the first use)
-    bool locate_present_built = false;
-    LocatePresent locate_present;
-    // ... and the coefficient rows of the erasure patterns it has met (host
-    // data only), dropped as a whole past kChkCacheBytes
-    std::map<std::vector<uint8_t>, std::shared_ptr<const PresentPattern>> chk_cache;
-    size_t chk_cache_bytes = 0;
-
-    // error-locator cache keyed by erasure pattern (bounded LRU)
-    Lru<std::vector<uint8_t>, std::vector<uint32_t>, 64> el_cache;
-    // rs_set_reference_inversion_cache: the GF(2^8) inversion cache exactly as
-    // leopard8.go:508-555 keys it (raw erasure bits on lookup, bits after
-    // prepare() on store), so the output is the reference's on every call
-    // sequence; on by default (a drop-in returns the reference's bytes), off
-    // keys the locators on the exact pattern
-    bool ref_inv = true;
-    std::map<std::array<uint64_t, 4>, std::vector<uint32_t>> ref_inv_cache;
-
-    // host-resident pipeline (rs_encode / rs_verify / rs_reconstruct): copy-in,
-    // compute and copy-out streams over kHostBufs rotating staging slabs
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    hipEvent_t ev_in[kHostBufs] = {}, ev_k[kHostBufs] = {}, ev_free[kHostBufs] = {};
-    DevBuf<uint8_t> stage;
-    uint64_t host_seg_bytes = 0;  // 0: automatic
-    // staging-slab rotation continues across calls, so the segments of an
-    // asynchronous encode queue behind the previous call's (rs_encode_async)
-    uint64_t pipe_seq = 0;
-    // asynchronous calls (encode / verify / reconstruct): ticket t completes at
-    // done_ev[t % kTickets]; a verify ticket's mismatch word is slot t % kTickets
-    // of tk_dflag (device), copied to tk_hflag (pinned) by the ticket's own work
-    static constexpr int kTickets = 64;
-    hipEvent_t done_ev[kTickets] = {};
-    uint64_t next_ticket = 1;
-    int *tk_hflag = nullptr, *tk_dflag = nullptr;
-    uint8_t tk_kind[kTickets] = {};  // HostOp of the slot's latest ticket, + 1
-    // pinned bounce slabs for outputs in pageable host memory (kHostBufs x total x seg)
-    PinnedBuf bounce;
-
-    // rs_new_multi: the per-device parts (this codec then owns no device
-    // resources of its own; its caches hold the reconstruct locators)
-    Multi *multi = nullptr;
-
-    ~rs_codec() {
-        if (multi) multi_destroy(multi);  // joins the part workers, frees the parts
-        multi = nullptr;
-        if (!dev_ready && !stream) return;
-        DeviceGuard g(device);
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (scratch_ev) {
-            (void)hipEventSynchronize(scratch_ev);
-            (void)hipEventDestroy(scratch_ev);
-        }
-        tw_ifft.release(); tw_fft.release(); tws_ifft.release(); tws_fft.release(); tw_fft_sub.release(); tw_dmap.release(); tw_ifft_sub.release(); ifft_nff.release(); dtw_ifft.release(); dtw_fft.release(); dtw_ifft_sub.release(); dtw_fft_sub.release(); dec_dmap.release();
-        work.release(); rows.release();
-        if (hflag) (void)hipHostFree(hflag);
-        if (dflag) (void)hipFree(dflag);
-        rc_blob.release();
-        rc_host.release();
-        dplan_cache.items.clear();  // each plan waits for its last launch
-        uplan_cache.items.clear();
-        ucol_cache.items.clear();
-        rowsplan_cache.items.clear();
-        pset_cache.items.clear();
-        rset_cache.items.clear();
-        rchk_cache.items.clear();
-        rchk_bad.release();
-        rchk_host.release();
-        fixplan_cache.items.clear();
-        scrub_rows.release(); scrub_dev.release(); scrub_list_dev.release(); scrub_set_dev.release();
-        scrub_host.release();
-        scrub_list_host.release();
-        scrub_set_host.release();
-        for (int i = 0; i < kRing; i++)
-            if (ring_ev[i]) {
-                (void)hipEventSynchronize(ring_ev[i]);
-                (void)hipEventDestroy(ring_ev[i]);
-            }
-        ring_dev.release();
-        ring_host.release();
-        if (s_in) (void)hipStreamSynchronize(s_in);
-        if (s_out) (void)hipStreamSynchronize(s_out);
-        stage.release();
-        bounce.release();
-        for (int t = 0; t < kTickets; t++)
-            if (done_ev[t]) (void)hipEventDestroy(done_ev[t]);
-        if (tk_hflag) (void)hipHostFree(tk_hflag);
-        if (tk_dflag) (void)hipFree(tk_dflag);
-        for (int b = 0; b < kHostBufs; b++) {
-            if (ev_in[b]) (void)hipEventDestroy(ev_in[b]);
-            if (ev_k[b]) (void)hipEventDestroy(ev_k[b]);
-            if (ev_free[b]) (void)hipEventDestroy(ev_free[b]);
-        }
-        if (s_in) (void)hipStreamDestroy(s_in);
-        if (s_out) (void)hipStreamDestroy(s_out);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
+#include "codec_impl.hpp"
 
 namespace {
 
@@ -550,18 +67,12 @@ int upload_split(rs_codec *c) {
     return RS_OK;
 }
 
-// Test-only path overrides, set through rs_debug_set_path (include/rs_mi355x.h).
-// The parity tests use them to run the kernel variants that other geometries
-// select (the bit-sliced encode off, the transforms in full-field coordinates,
-// the reconstruct FFT unpruned, the narrow / wide LDS units) on the same small
-// inputs.  Process-wide; read when a codec is created (bs) or at each launch.
+}  // namespace
+// The test-only path overrides (codec_impl.hpp).
+namespace rs {
 std::atomic<int> g_path_bs{1}, g_path_sub{1}, g_path_prune{1}, g_path_unit_width{-1}, g_path_hp_tiles{0}, g_path_hp_step{0},
     g_path_zc{3}, g_path_hp_tune{1}, g_path_rec_half{0}, g_path_dec_lab{0}, g_path_lds_big{1}, g_path_rows_direct{-1}, g_path_pat_tier{0}, g_path_bsdec_grid{0}, g_path_scrub_batch{-1}, g_path_scrub_chunk{0}, g_path_enc_list{-1}, g_path_rows_list{-1};
-bool bs_enabled() { return g_path_bs.load(std::memory_order_relaxed) != 0; }
-bool sub_enabled() { return g_path_sub.load(std::memory_order_relaxed) != 0; }
-bool prune_enabled() { return g_path_prune.load(std::memory_order_relaxed) != 0; }
-int zc_mask() { return g_path_zc.load(std::memory_order_relaxed); }
-}  // namespace
+}  // namespace rs
 int rs::unit_width_override() { return g_path_unit_width.load(std::memory_order_relaxed); }
 int rs::hp_tiles_override() { return g_path_hp_tiles.load(std::memory_order_relaxed); }
 int rs::hp_step_override() { return g_path_hp_step.load(std::memory_order_relaxed); }
@@ -569,15 +80,6 @@ bool rs::hp_tune_enabled() { return g_path_hp_tune.load(std::memory_order_relaxe
 bool rs::rec_half_enabled() { return g_path_rec_half.load(std::memory_order_relaxed) != 0; }
 int rs::bsdec_grid_override() { return g_path_bsdec_grid.load(std::memory_order_relaxed); }
 namespace {
-
-// One LDS-resident encode launch covers m <= 256 (both fields) and, for
-// GF(2^16), m up to 4096 (64-byte tiles, half tiles at 2048, quarter tiles at
-// 4096, kernels.hpp kMaxLdsEncLogM16);
-// larger m runs the multi-pass kernels.
-bool enc_lds_ok(const rs_codec *c) {
-    return c->logm <= kMaxLdsLogN ||
-           (c->bits == 16 && c->logm <= kMaxLdsEncLogM16 && g_path_lds_big.load(std::memory_order_relaxed));
-}
 
 // Host half of the encode plan (no device calls): twiddle schedule and panic check.
 void plan_encode_host(rs_codec *c) {
@@ -621,6 +123,8 @@ int upload_ifft_sub(rs_codec *c) {
     return RS_OK;
 }
 
+}  // namespace
+namespace rs {
 // Device half, on first use: stream, flag word, encode twiddle tables.
 int ensure_device(rs_codec *c) {
     if (c->dev_ready) return RS_OK;
@@ -664,6 +168,8 @@ int ensure_device(rs_codec *c) {
     c->dev_ready = true;
     return RS_OK;
 }
+}  // namespace rs
+namespace {
 
 // n = 512..2048 (GF(2^16)): the decoder layers with a full-field twiddle are
 // 0 (n = 512), 0-1 (1024) and 0-2 (2048), fftSkew indices >= 255 everywhere
@@ -702,6 +208,8 @@ int upload_big_sub(rs_codec *c, const std::vector<uint32_t> &il, const std::vect
     return RS_OK;
 }
 
+}  // namespace
+namespace rs {
 int build_decode_plan(rs_codec *c) {
     if (c->dec_built) return RS_OK;
     std::vector<uint32_t> &il = c->dec_ifft_logs, &fl = c->dec_fft_logs;
@@ -738,67 +246,6 @@ bool rec_lds_ok(const rs_codec *c) {
            (c->bits == 16 && (c->logn <= 11 || (c->logn <= kMaxLdsRecLogN16 && g_path_lds_big.load(std::memory_order_relaxed))));
 }
 
-hipStream_t pick_stream(rs_codec *c, void *s) {
-    return s == RS_NULL_STREAM ? (hipStream_t)0 : s ? (hipStream_t)s : c->stream;
-}
-
-// What every stream-ordered entry point does once its arguments are checked:
-// take the codec mutex, select the codec's device, create the device half on
-// first use (err), pick the call's stream; and at the end, finish().
-struct DevCall {
-    std::lock_guard<std::mutex> lk;
-    DeviceGuard g;
-    const int err;
-    const hipStream_t s;
-    const bool wait;  // no caller stream: the call completes on return
-    DevCall(rs_codec *c, void *stream)
-        : lk(c->mu), g(c->device), err(ensure_device(c)), s(pick_stream(c, stream)), wait(!stream) {}
-    int finish(int e) const {
-        if (e) return e;
-        if (wait) HIP_TRY(hipStreamSynchronize(s));
-        return RS_OK;
-    }
-};
-
-// Order this call's stream behind the previous user of the codec scratch
-// (nothing to do when that was this stream: it is in order already, and an
-// explicit wait would stop the next launch from being queued behind the
-// previous one).
-int scratch_acquire(rs_codec *c, hipStream_t s) {
-    if (c->scratch_used && s != c->scratch_stream)
-        HIP_TRY(hipStreamWaitEvent(s, c->scratch_ev, 0));
-    return RS_OK;
-}
-// Host wait for the previous user of the scratch (before a host-side write or a reallocation).
-int scratch_host_wait(rs_codec *c) {
-    if (c->scratch_used) HIP_TRY(hipEventSynchronize(c->scratch_ev));
-    return RS_OK;
-}
-// Does an encode launch over these row sets touch the codec scratch (the
-// device row table, the multi-pass work rows)?  Launches that do not skip the
-// scratch event: one hipEventRecord less per call (the single-stripe
-// device-resident encode is host-bound).
-bool encode_uses_scratch(const rs_codec *c, const RowSet &data, const RowSet &par) {
-    return data.table || par.table || !enc_lds_ok(c);
-}
-// Mark the scratch as used by the work queued on `s` so far.
-int scratch_release(rs_codec *c, hipStream_t s) {
-    if (!c->scratch_ev) HIP_TRY(hipEventCreateWithFlags(&c->scratch_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->scratch_ev, s));
-    c->scratch_used = true;
-    c->scratch_stream = s;
-    return RS_OK;
-}
-// DevBuf::ensure for codec scratch: a reallocation frees a buffer that a
-// kernel of an earlier call (on another stream) may still read.
-template <class T>
-int scratch_ensure(rs_codec *c, DevBuf<T> &b, size_t want) {
-    if (want <= b.n) return RS_OK;
-    if (int e = scratch_host_wait(c)) return e;
-    HIP_TRY(b.ensure(want));
-    return RS_OK;
-}
-
 // Data rows [0,k) and parity rows [k,k+p) as RowSets: strided when both sets'
 // pointers are equally spaced (AllocAligned slab), else both via a device
 // table (one strided set and one table would reach a kernel whose ROWTAB
@@ -831,6 +278,8 @@ int make_rowsets(rs_codec *c, uint8_t *const *d, hipStream_t s, RowSet &data, Ro
     par = RowSet{c->rows.p + c->k, nullptr, 0};
     return RS_OK;
 }
+}  // namespace rs
+namespace {
 
 // Multi-pass transform over `rows` rows of `work` (m or n rows).
 int run_passes(rs_codec *c, bool inverse, uint8_t *work, uint64_t S, int logsz, int mtrunc, const uint32_t *tw,
@@ -884,10 +333,12 @@ EncodeArgs encode_args(const rs_codec *c, RowSet data, RowSet par, uint64_t S, u
     return a;
 }
 
+}  // namespace
+namespace rs {
 // mismatch != nullptr: verify.  mismatch_stride: ints per stripe between the
 // stripes' mismatch words (kernels.hpp EncodeArgs), 0: one word for all.
 int encode_device(rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t stripe_stride, int nstripes,
-                  int *mismatch, hipStream_t s, int mismatch_stride = 0) {
+                  int *mismatch, hipStream_t s, int mismatch_stride) {
     if (!c->enc_ok) return RS_ERR_PANIC;
     if (c->logm <= kMaxRegLogM) {
         EncodeArgs a = encode_args(c, data, par, S, stripe_stride, nstripes, mismatch, mismatch_stride);
@@ -944,6 +395,8 @@ int encode_device(rs_codec *c, RowSet data, RowSet par, uint64_t S, uint64_t str
     }
     return RS_OK;
 }
+}  // namespace rs
+namespace {
 
 // errLocs for an erasure pattern (cached: analog of leopard8.go:508-555, but
 // keyed by the full pattern so a hit is always exact).
@@ -1024,6 +477,8 @@ std::vector<uint8_t> plan_key(const std::vector<uint8_t> &present, Want want, co
     return key;
 }
 
+}  // namespace
+namespace rs {
 // The plan of one erasure pattern from its locators `el` (leopard16.go:432-568).
 int plan_reconstruct_new(rs_codec *c, const std::vector<uint8_t> &present, Want want,
                          const std::vector<uint32_t> &el, RecPlan &pl) {
@@ -1064,6 +519,8 @@ int plan_reconstruct_new(rs_codec *c, const std::vector<uint8_t> &present, Want 
     }
     return RS_OK;
 }
+}  // namespace rs
+namespace {
 
 // Plans are cached per (erasure pattern, recover_all): repeated repairs of
 // the same pattern skip the table construction.
@@ -1135,9 +592,11 @@ int launch_reconstruct(rs_codec *c, const RecPlan &pl, int set, uint64_t S, hipS
     return RS_OK;
 }
 
+}  // namespace
+namespace rs {
 // Device-resident plan for (present, recover_all), built and uploaded on first use.
 int dev_plan(rs_codec *c, const std::vector<uint8_t> &present, Want want, uint64_t S, DevPlan **out,
-             const ElExt *el_ext = nullptr) {
+             const ElExt *el_ext) {
     ElExt loc;
     if (int e = resolve_locators(c, present, want, S, el_ext, loc)) return e;
     std::vector<uint8_t> key = plan_key(present, want, loc);
@@ -1231,7 +690,7 @@ int launch_rec_plan(rs_codec *c, DevPlan *dpl, uint8_t *base, uint64_t stride, u
 // The next slot of the per-call row-pointer ring with room for `want` bytes:
 // its pinned host half h and its HBM half g, free once the copy and the kernel
 // of the slot's previous call are done.  The caller fills h, copies it to g on
-// its stream, launches, and records ring_ev[slot] there (ring_used[slot] = true).
+// its stream, launches, and posts the slot there (ring_post).
 int ring_acquire(rs_codec *c, size_t want, int &slot, uint8_t *&h, uint8_t *&g) {
     const size_t bytes = align256(want);
     if (c->ring_slot < bytes) {
@@ -1251,6 +710,8 @@ int ring_acquire(rs_codec *c, size_t want, int &slot, uint8_t *&h, uint8_t *&g) 
     g = c->ring_dev.p + (size_t)i * c->ring_slot;
     return RS_OK;
 }
+}  // namespace rs
+namespace {
 
 // rs_reconstruct_dev with rec_lds_ok (one LDS-resident launch): the plan's tables
 // stay in HBM; equally strided shards (an AllocAligned slab, a torch 2-D
@@ -1301,8 +762,7 @@ int reconstruct_device_lds(rs_codec *c, uint8_t *const *d, const std::vector<uin
     ra.src = (const uint8_t *const *)g;
     ra.dst = (uint8_t *const *)g + n;
     HIP_TRY(launch_rec_lds(c->bits, c->logn, c->dec_sub, ra, s));
-    HIP_TRY(hipEventRecord(c->ring_ev[i], s));
-    c->ring_used[i] = true;
+    if (int e = ring_post(c, i, s)) return e;
     HIP_TRY(dp->mark_used(s));
     return RS_OK;
 }
@@ -1328,6 +788,8 @@ int upd_plan(rs_codec *c, const std::vector<int> &idx, UpdPlan **out) {
     return RS_OK;
 }
 
+}  // namespace
+namespace rs {
 // Changed rows per plan: a plan's tables take p * t * twd * 4 bytes, so a long
 // index list on a codec with many parity rows runs as several plans (each its
 // own cache entry), one after the other on the stream.
@@ -1336,6 +798,8 @@ int upd_piece(const rs_codec *c) {
     const size_t per_row = (size_t)c->p * c->twd * 4;
     return (int)std::max<size_t>(kUpdGroup, kUpdPlanBytes / per_row / kUpdGroup * kUpdGroup);
 }
+}  // namespace rs
+namespace {
 
 // Pointer form: parity rows par[0..p), differences old[j] ^ nw[j] of data rows
 // idx[j] (old == nullptr: the rows nw themselves, EncodeIdx).  The row
@@ -1367,8 +831,7 @@ int update_device_rows(rs_codec *c, uint8_t *const *par, const std::vector<int> 
         a.t = t;
         a.nstripes = 1;
         HIP_TRY(launch_update(c->bits, a, s));
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
+        if (int e = ring_post(c, slot, s)) return e;
         HIP_TRY(up->mark_used(s));
     }
     return RS_OK;
@@ -1406,6 +869,8 @@ int update_device_batch(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_
 // ---- A list of changed rows, a different set per stripe (rs_update_dev_batch_list)
 static_assert(kUpdListGroup == kUpdGroup, "the host plan cuts the groups k_update_list runs");
 
+}  // namespace
+namespace rs {
 // The cached device set with the tables of `cols` (ascending, distinct), built
 // and uploaded on first use.  A cached set that holds more columns serves as
 // well (a slot is a column's position in the set's own list), so the changing
@@ -1433,6 +898,8 @@ int upd_col_set(rs_codec *c, const std::vector<int> &cols, UpdColSet **out) {
     *out = c->ucol_cache.put(cols, std::move(us))->get();  // an eviction waits for that set's last launch
     return RS_OK;
 }
+}  // namespace rs
+namespace {
 
 // The plan's launches in order.  The descriptor lists of as many launches of a
 // pass as fit kUpdListSlotBytes travel through one ring slot (a longer list is
@@ -1490,8 +957,7 @@ int update_device_list(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t
             a.nt = plan.launches[pc.launch].nt;
             HIP_TRY(launch_update_list(c->bits, a, s));
         }
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
+        if (int e = ring_post(c, slot, s)) return e;
         HIP_TRY(us->mark_used(s));
     }
     return RS_OK;
@@ -1510,11 +976,15 @@ constexpr int kRowsDirectMaxN = 2048;
 // the smaller value.
 constexpr int kRowsDirectAuto = 6, kRowsDirectAuto2048 = 8;
 
+}  // namespace
+namespace rs {
 bool rows_direct(const rs_codec *c, int t) {
     if (!c->dec_ok || c->n > kRowsDirectMaxN) return false;
     const int knob = g_path_rows_direct.load(std::memory_order_relaxed);
     return knob == 1 || (knob < 0 && t <= (c->n == 2048 ? kRowsDirectAuto2048 : kRowsDirectAuto));
 }
+}  // namespace rs
+namespace {
 
 // Cached device tables for (present, required), built and uploaded on first
 // use, always from the exact locators of the pattern.
@@ -1585,13 +1055,14 @@ int decode_rows_device(rs_codec *c, uint8_t *const *d, uint8_t *base, uint64_t r
     }
     HIP_TRY(launch_decode_rows(c->bits, a, s));
     if (slot >= 0) {
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
+        if (int e = ring_post(c, slot, s)) return e;
     }
     HIP_TRY(dp->mark_used(s));
     return RS_OK;
 }
 
+}  // namespace
+namespace rs {
 // Device reconstruct (leopard16.go:432-568) for already-validated input.
 int reconstruct_device(rs_codec *c, uint8_t *const *d, const std::vector<uint8_t> &present, uint64_t S,
                        Want want, hipStream_t s) {
@@ -1609,6 +1080,8 @@ int reconstruct_device(rs_codec *c, uint8_t *const *d, const std::vector<uint8_t
     HIP_TRY(hipStreamSynchronize(s));  // the pinned staging of the upload is reused by the next call
     return RS_OK;
 }
+}  // namespace rs
+namespace {
 
 // checkShards / shardSize (encoder.go:102-126)
 size_t shard_size_of(const size_t *lens, int n) {
@@ -2033,955 +1506,6 @@ int encode_dev_call(rs_codec *c, uint8_t *const *d, uint8_t *base, uint64_t row_
     return RS_OK;
 }
 
-// ---- Scrub (rs_verify_dev_batch_map / rs_locate_dev / rs_scrub_dev_batch; rs_mi355x.h)
-// scrub_dev: [first position, 8 bytes][rowbad, p ints] then, 256-aligned, one
-// mismatch int per stripe; scrub_host mirrors the head, then four 64-byte
-// blocks (the syndrome symbols), then the stripes' ints.
-size_t scrub_head(const rs_codec *c) { return align256(8 + 4 * (size_t)c->p); }
-int scrub_buffers(rs_codec *c, int nstripes) {
-    const size_t head = scrub_head(c), flags = 4 * (size_t)nstripes;
-    if (int e = scratch_ensure(c, c->scrub_dev, head + flags)) return e;
-    if (head + 256 + flags > c->scrub_host.n) {
-        if (int e = scratch_host_wait(c)) return e;
-        HIP_TRY(c->scrub_host.ensure(head + 256 + flags));
-    }
-    return RS_OK;
-}
-
-// The verify of rs_verify_dev_batch with one mismatch word per stripe: the same
-// launches, the words cleared by one memset and read back by one copy.  Returns
-// with the stream drained; *flags: nstripes ints in pinned memory, non-zero = bad.
-int verify_map_device(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, int nstripes, uint64_t S,
-                      hipStream_t s, const int **flags) {
-    if (int e = scrub_buffers(c, nstripes)) return e;
-    int *dflags = (int *)(c->scrub_dev.p + scrub_head(c));
-    int *hflags = (int *)(c->scrub_host.p + scrub_head(c) + 256);
-    HIP_TRY(hipMemsetAsync(dflags, 0, 4 * (size_t)nstripes, s));
-    const RowSet data{nullptr, base, row_stride}, par{nullptr, base + (size_t)c->k * row_stride, row_stride};
-    if (int e = encode_device(c, data, par, S, stripe_stride, nstripes, dflags, s, 1)) return e;
-    HIP_TRY(hipMemcpyAsync(hflags, dflags, 4 * (size_t)nstripes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *flags = hflags;
-    return RS_OK;
-}
-
-// ---- A list of stripes of different sizes (rs_encode_dev_list / rs_verify_dev_list; rs_mi355x.h)
-static_assert(sizeof(EncListStripe) == 24 && sizeof(rs_stripe) == 24 && offsetof(rs_stripe, row_stride) == 8 &&
-                  offsetof(rs_stripe, shard_size) == 16,
-              "a host descriptor is the kernel's descriptor");
-// Descriptors and prefix of one launch travel through one ring slot.
-constexpr size_t kEncListSlotBytes = 4u << 20;
-constexpr size_t kEncListMaxStripes = (kEncListSlotBytes - 256 - 4) / (sizeof(EncListStripe) + 4);
-// pick_narrow's rule for the GF(2^8) register units (kernels.hip launch_encode_reg), over a launch's workgroups
-constexpr uint64_t kEncListNarrowBelow = 1024;
-
-// The launches of the list kernel over stripes[order[0..n)], in order; stripe
-// order[i]'s mismatch word is mismatch[i] (verify).  Nothing waits for a kernel.
-int encode_list_launches(rs_codec *c, const rs_stripe *stripes, const std::vector<uint32_t> &order, int *mismatch,
-                         hipStream_t s) {
-    const size_t n = order.size();
-    if (!n) return RS_OK;
-    std::vector<uint64_t> sizes(n);
-    for (size_t i = 0; i < n; i++) sizes[i] = stripes[order[i]].shard_size;
-    std::vector<EncListLaunch> plan;
-    if (!make_encode_list_plan(sizes.data(), n, encode_list_wg_bytes(c->bits, c->logm, false),
-                               encode_list_wg_bytes(c->bits, c->logm, true), unit_width_override(), kEncListNarrowBelow,
-                               kEncListMaxStripes, kEncListMaxWg, plan))
-        return RS_ERR_INVALID_ARG;
-    for (const EncListLaunch &l : plan) {
-        const size_t nl = l.z1 - l.z0, o_pre = align256(nl * sizeof(EncListStripe));
-        int slot = 0;
-        uint8_t *h = nullptr, *g = nullptr;
-        if (int e = ring_acquire(c, o_pre + 4 * (nl + 1), slot, h, g)) return e;
-        EncListStripe *hd = (EncListStripe *)h;
-        for (size_t i = 0; i < nl; i++) {
-            const rs_stripe &st = stripes[order[l.z0 + i]];
-            hd[i] = EncListStripe{st.base, st.row_stride, st.shard_size};
-        }
-        write_encode_list_prefix(sizes.data(), l, (uint32_t *)(h + o_pre));
-        HIP_TRY(hipMemcpyAsync(g, h, o_pre + 4 * (nl + 1), hipMemcpyHostToDevice, s));
-        EncodeListArgs a{};
-        a.stripes = (const EncListStripe *)g;
-        a.first_wg = (const uint32_t *)(g + o_pre);
-        a.nstripes = (uint32_t)nl;
-        a.nwg = (uint32_t)l.nwg;
-        a.wg_bytes = l.wg_bytes;
-        a.k = c->k;
-        a.p = c->p;
-        a.nchunks = c->nchunks;
-        a.tw_ifft = c->tw_ifft.p;
-        a.tw_fft = c->tw_fft.p;
-        a.mismatch = mismatch ? mismatch + l.z0 : nullptr;
-        HIP_TRY(launch_encode_reg_list(c->bits, c->logm, mismatch != nullptr, a, s));
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
-    }
-    return RS_OK;
-}
-
-// Largest shard size the automatic routing hands to the list kernel where a
-// stripe alone takes the bit-sliced (m = 32, m = 16) or the split kernel: the
-// largest measured size at which the list kernel was faster
-// (profiles/encode_list_c2.txt).  UINT64_MAX: the geometry
-// has the register kernel only (GF(2^8), GF(2^16) m <= 2).  Host only: the
-// split kernel serves every GF(2^16) codec with m = 4..32 (plan_encode_host).
-uint64_t encode_list_max(const rs_codec *c) {
-    if (c->bits != 16 || c->logm < 2 || c->logm > kMaxRegLogM) return UINT64_MAX;
-    if (c->bs_ok) return c->logm == 5 ? RS_ENCODE_LIST_MAX_BS32 : RS_ENCODE_LIST_MAX_BS16;
-    return RS_ENCODE_LIST_MAX_SPLIT;
-}
-// Does the automatic / forced routing give a stripe of this size a launch of its own?
-bool encode_list_own(const rs_codec *c, uint64_t shard_size) {
-    const int knob = g_path_enc_list.load(std::memory_order_relaxed);
-    if (c->logm > kMaxRegLogM || knob == 0) return true;
-    return knob < 0 && shard_size > encode_list_max(c);
-}
-
-// rs_encode_dev_list (verdict == ok == nullptr) and rs_verify_dev_list after their argument checks.
-int encode_list_call(rs_codec *c, const rs_stripe *stripes, size_t n, int8_t *verdict, int *ok, void *stream) {
-    DevCall dc(c, stream);
-    if (dc.err) return dc.err;
-    const hipStream_t s = dc.s;
-    const bool verify = ok != nullptr;
-    std::vector<uint32_t> order, own;  // through the list kernel / one encode_device each
-    for (size_t z = 0; z < n; z++) (encode_list_own(c, stripes[z].shard_size) ? own : order).push_back((uint32_t)z);
-    int *dflags = nullptr, *hflags = nullptr;
-    // the codec scratch: the verify's mismatch words, and the work rows of a
-    // multi-pass encode; the list kernel and the strided launches of the
-    // other encodes touch none (encode_uses_scratch)
-    const bool scr = verify || (!own.empty() && !enc_lds_ok(c));
-    if (scr)
-        if (int e = scratch_acquire(c, s)) return e;
-    if (verify) {
-        if (int e = scrub_buffers(c, (int)n)) return e;
-        dflags = (int *)(c->scrub_dev.p + scrub_head(c));
-        hflags = (int *)(c->scrub_host.p + scrub_head(c) + 256);
-        HIP_TRY(hipMemsetAsync(dflags, 0, 4 * n, s));
-    }
-    // mismatch words: the list's stripes in list order, then the others
-    if (int e = encode_list_launches(c, stripes, order, dflags, s)) return e;
-    for (size_t i = 0; i < own.size(); i++) {
-        const rs_stripe &st = stripes[own[i]];
-        const RowSet data{nullptr, st.base, st.row_stride}, par{nullptr, st.base + (size_t)c->k * st.row_stride, st.row_stride};
-        if (int e = encode_device(c, data, par, st.shard_size, 0, 1, verify ? dflags + order.size() + i : nullptr, s))
-            return e;
-    }
-    if (scr)
-        if (int e = scratch_release(c, s)) return e;
-    if (!verify) return dc.finish(RS_OK);
-    HIP_TRY(hipMemcpyAsync(hflags, dflags, 4 * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    int all = 1;
-    for (size_t i = 0; i < n; i++) {
-        const int good = ((volatile int *)hflags)[i] == 0;
-        if (verdict) verdict[i < order.size() ? order[i] : own[i - order.size()]] = (int8_t)good;
-        all &= good;
-    }
-    *ok = all;
-    return RS_OK;
-}
-
-// The common distance of rows[0..n) when they are equally spaced upwards, else 0.
-uint64_t common_stride(uint8_t *const *rows, int n) {
-    if (n < 2 || rows[1] <= rows[0]) return 0;
-    const uint64_t st = (uint64_t)(rows[1] - rows[0]);
-    for (int i = 2; i < n; i++)
-        if (rows[i] <= rows[i - 1] || (uint64_t)(rows[i] - rows[i - 1]) != st) return 0;
-    return st;
-}
-
-// Device tables of the repaired row of data shard j (make_repair_tables), cached.
-int fix_plan(rs_codec *c, int j, uint32_t scale, UpdPlan **out) {
-    if (auto *hit = c->fixplan_cache.find(j)) {
-        *out = hit->get();
-        return RS_OK;
-    }
-    std::vector<uint8_t> h((size_t)3 * c->twd * 4, 0);
-    make_repair_tables(*c->F, scale, (uint32_t *)h.data());
-    auto up = std::make_unique<UpdPlan>();
-    if (int e = upload(up->blob, h)) return e;
-    up->tw = (const uint32_t *)up->blob.p;
-    *out = c->fixplan_cache.put(j, std::move(up))->get();  // an eviction waits for that plan's last launch
-    return RS_OK;
-}
-
-// Locate (and repair) of one stripe whose rows are d[0..total), all on the
-// caller's stream s inside the caller's scratch_acquire / scratch_release:
-// recompute the parity into scratch rows, scan it against the stored parity,
-// classify; for a data candidate build the repaired row, confirm it with the
-// pointer-form verify, and only then name (and overwrite) the shard.  Returns
-// with every readback done; a repair copy may still be queued on s.
-int locate_stripe(rs_codec *c, uint8_t *const *d, uint64_t S, bool repair, hipStream_t s, int *verdict) {
-    const int k = c->k, p = c->p;
-    *verdict = RS_SCRUB_UNLOCATED;
-    if (int e = scrub_buffers(c, 0)) return e;
-    // scratch rows at the data rows' own stride where that keeps the bit-sliced
-    // kernel eligible (one stride for data and parity), else packed
-    uint64_t qs = S;
-    const uint64_t ds = common_stride(d, k);
-    if (c->bs_ok && ds >= S && ds <= 2 * S && encode_bs_fits(k, p, ds, S)) qs = ds;
-    if (int e = scratch_ensure(c, c->scrub_rows, (size_t)p * qs + S)) return e;
-    uint8_t *q = c->scrub_rows.p, *fix = q + (size_t)p * qs;
-    std::vector<uint8_t *> rows(d, d + c->total);
-    for (int i = 0; i < p; i++) rows[k + i] = q + (size_t)i * qs;
-    {
-        RowSet data, par;
-        if (int e = make_rowsets(c, rows.data(), s, data, par)) return e;
-        if (int e = encode_device(c, data, par, S, 0, 1, nullptr, s)) return e;
-    }
-    uint8_t *dev = c->scrub_dev.p, *host = c->scrub_host.p;
-    HIP_TRY(hipMemsetAsync(dev, 0xff, 8, s));
-    HIP_TRY(hipMemsetAsync(dev + 8, 0, 4 * (size_t)p, s));
-    ScanArgs sa{};
-    sa.S = S;
-    sa.p = p;
-    sa.first = (unsigned long long *)dev;
-    sa.rowbad = (int *)(dev + 8);
-    const uint64_t ps = common_stride(d + k, p);
-    int slot = -1;
-    if (p == 1 || ps) {
-        sa.stored = d[k];
-        sa.stored_stride = ps;
-        sa.fresh = q;
-        sa.fresh_stride = qs;
-    } else {
-        uint8_t *h = nullptr, *g = nullptr;
-        const size_t bytes = (size_t)2 * p * sizeof(void *);
-        if (int e = ring_acquire(c, bytes, slot, h, g)) return e;
-        uint8_t **rp = (uint8_t **)h;
-        for (int i = 0; i < p; i++) rp[i] = d[k + i], rp[p + i] = q + (size_t)i * qs;
-        HIP_TRY(hipMemcpyAsync(g, h, bytes, hipMemcpyHostToDevice, s));
-        sa.rows = (uint8_t *const *)g;
-    }
-    HIP_TRY(launch_syndrome_scan(c->bits, sa, s));
-    if (slot >= 0) {
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
-    }
-    HIP_TRY(hipMemcpyAsync(host, dev, 8 + 4 * (size_t)p, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const volatile int *rowbad = (const volatile int *)(host + 8);
-    const uint64_t first = *(const volatile uint64_t *)host;
-    int nb = 0, bi = -1;
-    for (int i = 0; i < p; i++)
-        if (rowbad[i]) nb++, bi = i;
-    if (!nb) {
-        *verdict = RS_SCRUB_CLEAN;
-        return RS_OK;
-    }
-    if (p == 1) return RS_OK;  // one syndrome row cannot tell the shards apart
-    if (nb == 1) {
-        // data and the other parity rows form a codeword by construction
-        *verdict = k + bi;
-        if (repair) HIP_TRY(hipMemcpyAsync(d[k + bi], q + (size_t)bi * qs, S, hipMemcpyDeviceToDevice, s));
-        return RS_OK;
-    }
-    if (nb < p || first >= S) return RS_OK;  // a data shard's difference shows in every parity row
-    // the two syndrome symbols at the first differing position
-    const uint64_t blk = first & ~(uint64_t)63;
-    uint8_t *sym = host + scrub_head(c);
-    const uint8_t *from[4] = {d[k], q, d[k + 1], q + qs};
-    for (int i = 0; i < 4; i++) HIP_TRY(hipMemcpyAsync(sym + 64 * i, from[i] + blk, 64, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    auto symbol = [&](int i) -> uint32_t {
-        const volatile uint8_t *b = sym + 64 * i;
-        const int o = (int)(first & 63);
-        // GF(2^16): low bytes in [0, 32) of the block, high bytes in [32, 64)
-        return c->bits == 16 ? (uint32_t)b[o & 31] | (uint32_t)b[(o & 31) + 32] << 8 : b[o];
-    };
-    const uint32_t e0 = symbol(0) ^ symbol(1), e1 = symbol(2) ^ symbol(3);
-    if (!c->locate_built) {
-        make_locate_map(*c->F, k, p, c->locate_map);
-        c->locate_built = true;
-    }
-    uint32_t scale = 0;
-    const int j = locate_shard(*c->F, c->locate_map, e0, e1, &scale);
-    if (j < 0) return RS_OK;
-    // R = row_j ^ scale * (P_0 ^ P'_0) into the spare scratch row
-    UpdPlan *fp = nullptr;
-    if (int e = fix_plan(c, j, scale, &fp)) return e;
-    {
-        uint8_t *h = nullptr, *g = nullptr;
-        const size_t bytes = 4 * sizeof(void *);
-        if (int e = ring_acquire(c, bytes, slot, h, g)) return e;
-        uint8_t **rp = (uint8_t **)h;
-        rp[0] = d[j], rp[1] = d[k], rp[2] = q, rp[3] = fix;
-        HIP_TRY(hipMemcpyAsync(g, h, bytes, hipMemcpyHostToDevice, s));
-        DecodeRowsArgs a{};
-        a.rows = (uint8_t *const *)g;
-        a.tw = fp->tw;
-        a.S = S;
-        a.np = 3;
-        a.t = 1;
-        a.nstripes = 1;
-        HIP_TRY(launch_decode_rows(c->bits, a, s));
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
-        HIP_TRY(fp->mark_used(s));
-    }
-    // never from the ratio alone: the stripe with R in place of row j must verify
-    std::copy(d, d + c->total, rows.begin());
-    rows[j] = fix;
-    {
-        RowSet data, par;
-        if (int e = make_rowsets(c, rows.data(), s, data, par)) return e;
-        HIP_TRY(hipMemsetAsync(c->dflag, 0, sizeof(int), s));
-        if (int e = encode_device(c, data, par, S, 0, 1, c->dflag, s)) return e;
-        HIP_TRY(hipMemcpyAsync(c->hflag, c->dflag, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    if (*(volatile int *)c->hflag != 0) return RS_OK;
-    *verdict = j;
-    if (repair) HIP_TRY(hipMemcpyAsync(d[j], fix, S, hipMemcpyDeviceToDevice, s));
-    return RS_OK;
-}
-
-// ---- The locate of many stripes in shared launches (rs_locate_dev_batch)
-// Scratch bytes of a pass: p recomputed parity rows per listed stripe.  A pass
-// takes as many stripes as fit this bound (always at least one), at most
-// kScrubMaxList (one per blockIdx.y), and at most the "scrub_chunk" knob.
-constexpr size_t kScrubListScratch = (size_t)1 << 30;
-// rs_scrub_dev_batch sends its bad stripes through the batched route from this
-// many on: the smallest count at which that route measured faster than one
-// stripe at a time by more than the latter's pass-to-pass spread
-// (profiles/scrub_batch_c3.txt).  At 128+32 x 1 MiB, 256
-// stripes: with two bad stripes 7.58-7.68 ms per scrub against 7.95-8.01
-// (spread 0.01-0.11) in both runs; with one, 7.53-7.63 against 7.60-7.69, which
-// cleared the spread (0.04-0.08) in one run and not in the other, so a single
-// bad stripe keeps the one-stripe route.
-constexpr size_t kScrubBatchMin = 2;
-
-// locate_stripe for stripes[0..nlist) of the slab at `base` (distinct, checked
-// by the caller), verdict[e] for stripes[e], on the caller's stream s inside
-// the caller's scratch_acquire / scratch_release.  Per pass: the stripes'
-// encodes into their scratch slots, the list scan and the pick, one readback
-// (host wait 1); the host classifies as locate_stripe does; the data
-// candidates' confirm on the 2 p parity rows, one readback (host wait 2); the
-// repairs are queued and left to the caller's final wait.
-int locate_list_device(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, const uint32_t *stripes,
-                       size_t nlist, uint64_t S, bool repair, hipStream_t s, int32_t *verdict) {
-    const int k = c->k, p = c->p;
-    for (size_t e = 0; e < nlist; e++) verdict[e] = RS_SCRUB_UNLOCATED;
-    if (!nlist) return RS_OK;
-    // scratch rows at the data rows' own stride where that keeps the bit-sliced
-    // kernel eligible, else packed (locate_stripe's rule)
-    uint64_t qs = S;
-    const uint64_t ds = k > 1 ? row_stride : 0;
-    if (c->bs_ok && ds >= S && ds <= 2 * S && encode_bs_fits(k, p, ds, S)) qs = ds;
-    const size_t slot_bytes = align256((size_t)p * qs);
-    size_t chunk = std::min<size_t>(nlist, (size_t)kScrubMaxList);
-    chunk = std::min(chunk, std::max<size_t>(1, kScrubListScratch / slot_bytes));
-    if (const int knob = g_path_scrub_chunk.load(std::memory_order_relaxed)) chunk = std::min(chunk, (size_t)knob);
-    if (int e = scratch_ensure(c, c->scrub_rows, chunk * slot_bytes)) return e;
-    // results of a pass: [first, 8 bytes per entry][rowbad, p ints][symbols, 2 dwords][confirm word]
-    const size_t o_rowbad = align256(8 * chunk), o_sym = o_rowbad + align256(4 * chunk * p);
-    const size_t o_bad = o_sym + align256(8 * chunk), res_bytes = o_bad + align256(4 * chunk);
-    if (int e = scratch_ensure(c, c->scrub_list_dev, res_bytes)) return e;
-    if (res_bytes > c->scrub_list_host.n) {
-        if (int e = scratch_host_wait(c)) return e;
-        HIP_TRY(c->scrub_list_host.ensure(res_bytes));
-    }
-    if (p > 1 && !c->locate_built) {
-        make_locate_map(*c->F, k, p, c->locate_map);
-        c->locate_built = true;
-    }
-    uint8_t *q = c->scrub_rows.p, *dev = c->scrub_list_dev.p;
-    uint8_t *host = c->scrub_list_host.p;
-    ScrubListArgs a{};
-    a.base = base;
-    a.row_stride = row_stride;
-    a.stripe_stride = stripe_stride;
-    a.fresh = q;
-    a.fresh_stride = qs;
-    a.fresh_slot_stride = slot_bytes;
-    a.S = S;
-    a.k = k;
-    a.p = p;
-    a.first = (unsigned long long *)dev;
-    a.rowbad = (int *)(dev + o_rowbad);
-    a.sym = (uint32_t *)(dev + o_sym);
-    a.bad = (int *)(dev + o_bad);
-    struct Cand {
-        uint32_t e;  // entry of the pass (its scratch slot)
-        int j;
-        uint32_t scale;
-    };
-    std::vector<Cand> cand;
-    std::vector<std::pair<uint32_t, int>> parity;  // (entry, parity row) located by the scan alone
-    std::vector<int> cols;
-    const int piece = upd_piece(c);
-    for (size_t c0 = 0; c0 < nlist; c0 += chunk) {
-        const size_t n = std::min(chunk, nlist - c0);
-        const uint32_t *zs = stripes + c0;
-        int32_t *v = verdict + c0;
-        int slot = 0;
-        uint8_t *h = nullptr, *g = nullptr;
-        if (int e = ring_acquire(c, 4 * n, slot, h, g)) return e;
-        std::memcpy(h, zs, 4 * n);
-        HIP_TRY(hipMemcpyAsync(g, h, 4 * n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(dev, 0xff, 8 * n, s));
-        HIP_TRY(hipMemsetAsync(dev + o_rowbad, 0, res_bytes - o_rowbad, s));
-        for (size_t e = 0; e < n; e++) {
-            const RowSet data{nullptr, base + (size_t)zs[e] * stripe_stride, ds};
-            const RowSet par{nullptr, q + e * slot_bytes, p > 1 ? qs : 0};
-            if (int err = encode_device(c, data, par, S, 0, 1, nullptr, s)) return err;
-        }
-        a.list = (const uint32_t *)g;
-        a.nlist = (int)n;
-        HIP_TRY(launch_syndrome_scan_list(c->bits, a, s));
-        HIP_TRY(launch_syndrome_pick(c->bits, a, s));
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
-        HIP_TRY(hipMemcpyAsync((void *)host, dev, o_bad, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        cand.clear();
-        parity.clear();
-        const volatile uint64_t *first = (const volatile uint64_t *)host;
-        const volatile uint32_t *sym = (const volatile uint32_t *)(host + o_sym);
-        for (size_t e = 0; e < n; e++) {
-            const volatile int *rowbad = (const volatile int *)(host + o_rowbad) + e * p;
-            int nb = 0, bi = -1;
-            for (int i = 0; i < p; i++)
-                if (rowbad[i]) nb++, bi = i;
-            if (!nb) {
-                v[e] = RS_SCRUB_CLEAN;
-            } else if (p == 1) {  // one syndrome row cannot tell the shards apart
-            } else if (nb == 1) {
-                v[e] = k + bi;
-                if (repair) parity.emplace_back((uint32_t)e, bi);
-            } else if (nb == p && first[e] < S) {  // a data shard's difference shows in every parity row
-                uint32_t scale = 0;
-                const int j = locate_shard(*c->F, c->locate_map, sym[2 * e], sym[2 * e + 1], &scale);
-                if (j >= 0) cand.push_back(Cand{(uint32_t)e, j, scale});
-            }
-        }
-        if (!cand.empty()) {
-            // never from the ratio alone.  Candidate number = position by
-            // column; a pass of the confirm takes the candidates of at most
-            // `piece` distinct columns (one column set)
-            std::stable_sort(cand.begin(), cand.end(), [](const Cand &x, const Cand &y) { return x.j < y.j; });
-            const size_t nc = cand.size(), twb = (size_t)c->twd * 4, db = 4 * (size_t)kScrubDescDwords;
-            const size_t o_tw = align256(db * nc), o_fix = o_tw + align256(nc * twb);
-            if (int e = ring_acquire(c, o_fix + align256(db * nc), slot, h, g)) return e;
-            for (size_t i = 0; i < nc; i++)
-                make_twiddle(*c->F, c->F->log[cand[i].scale], (uint32_t *)(h + o_tw + i * twb), true);
-            HIP_TRY(hipMemcpyAsync(g + o_tw, h + o_tw, nc * twb, hipMemcpyHostToDevice, s));
-            a.scale_tw = (const uint32_t *)(g + o_tw);
-            for (size_t n0 = 0, n1 = 0; n0 < nc; n0 = n1) {
-                cols.clear();
-                for (n1 = n0; n1 < nc; n1++) {
-                    if (!cols.empty() && cols.back() == cand[n1].j) continue;
-                    if ((int)cols.size() == piece) break;
-                    cols.push_back(cand[n1].j);
-                }
-                UpdColSet *us = nullptr;
-                if (int e = upd_col_set(c, cols, &us)) return e;
-                uint32_t *d = (uint32_t *)h + n0 * kScrubDescDwords;
-                for (size_t i = n0; i < n1; i++, d += kScrubDescDwords) {
-                    d[0] = zs[cand[i].e];
-                    d[1] = cand[i].e;
-                    d[2] = (uint32_t)(std::lower_bound(us->cols.begin(), us->cols.end(), cand[i].j) - us->cols.begin());
-                    d[3] = (uint32_t)i;
-                }
-                HIP_TRY(hipMemcpyAsync(g + db * n0, h + db * n0, db * (n1 - n0), hipMemcpyHostToDevice, s));
-                a.list = (const uint32_t *)(g + db * n0);
-                a.nlist = (int)(n1 - n0);
-                a.col_tw = us->tw;
-                HIP_TRY(launch_syndrome_confirm(c->bits, a, s));
-                HIP_TRY(us->mark_used(s));
-            }
-            HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-            c->ring_used[slot] = true;
-            HIP_TRY(hipMemcpyAsync((void *)(host + o_bad), dev + o_bad, 4 * nc, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            const volatile int *bad = (const volatile int *)(host + o_bad);
-            size_t nfix = 0;
-            uint32_t *d = (uint32_t *)(h + o_fix);
-            for (size_t i = 0; i < nc; i++) {
-                if (bad[i]) continue;
-                v[cand[i].e] = cand[i].j;
-                d[0] = zs[cand[i].e], d[1] = cand[i].e, d[2] = (uint32_t)cand[i].j, d[3] = (uint32_t)i;
-                d += kScrubDescDwords, nfix++;
-            }
-            if (repair && nfix) {
-                HIP_TRY(hipMemcpyAsync(g + o_fix, h + o_fix, db * nfix, hipMemcpyHostToDevice, s));
-                a.list = (const uint32_t *)(g + o_fix);
-                a.nlist = (int)nfix;
-                HIP_TRY(launch_syndrome_fix(c->bits, a, s));
-                HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-            }
-        }
-        for (const auto &pr : parity) {
-            uint8_t *row = base + (size_t)zs[pr.first] * stripe_stride + (size_t)(k + pr.second) * row_stride;
-            HIP_TRY(hipMemcpyAsync(row, q + pr.first * slot_bytes + (size_t)pr.second * qs, S, hipMemcpyDeviceToDevice, s));
-        }
-    }
-    return RS_OK;
-}
-
-// rs_locate_dev_batch after its argument checks.  Complete on return.
-int locate_batch_call(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, const uint32_t *stripes,
-                      size_t nlist, uint64_t S, int repair, int32_t *verdict, void *stream) {
-    DevCall dc(c, stream);
-    if (dc.err) return dc.err;
-    const hipStream_t s = dc.s;
-    if (int e = scratch_acquire(c, s)) return e;
-    const int err = locate_list_device(c, base, row_stride, stripe_stride, stripes, nlist, S, repair != 0, s, verdict);
-    if (int e = scratch_release(c, s)) return err ? err : e;
-    if (err) return err;
-    HIP_TRY(hipStreamSynchronize(s));  // the queued repairs
-    return RS_OK;
-}
-
-// ---- The locate of up to four corrupt shards per stripe (rs_locate_set_dev_batch)
-// Passes, confirm rounds and host waits of the set locate so far (rs_debug_locate_set_stats).
-std::atomic<uint64_t> g_set_passes{0}, g_set_rounds{0}, g_set_waits{0};
-
-static_assert(kLocateSetMax == RS_LOCATE_SET_MAX && kScrubSetMax == RS_LOCATE_SET_MAX, "one set size in all layers");
-// cap of a call: min(max_shards, p / 2) but at least 1, and 1 where the
-// geometry leaves no shift point (LocateSet::cap).
-int locate_set_cap(rs_codec *c, int max_shards) {
-    if (!c->locate_set_built) {
-        make_locate_set(*c->F, c->k, c->p, c->locate_set);
-        c->locate_set_built = true;
-    }
-    return std::max(1, std::min(max_shards, c->locate_set.cap));
-}
-
-// A candidate set of a listed stripe: nj shards J, ascending.
-struct SetCand {
-    uint32_t e = 0;  // entry of the pass (its scratch slot)
-    int nj = 0;
-    int J[kLocateSetMax] = {};
-    uint64_t pos = 0;  // where the next decode reads its symbols
-    int nd(int k) const {  // the data shards among them (they come first)
-        int n = 0;
-        while (n < nj && J[n] < k) n++;
-        return n;
-    }
-};
-
-// count[e] and shards[e * stride ..] for stripes[0..nlist), cap >= 2, on the
-// caller's stream s inside the caller's scratch_acquire / scratch_release;
-// locate_list_device's passes.  Per pass: the recompute and the list scan with
-// one readback (host wait 1); entries with at most cap (and fewer than p) bad
-// parity rows become the candidate of those parity shards, the others are
-// decoded at their first differing position; then rounds of a confirm over all
-// candidates (one readback) and, for those that fail with room left, a pick of
-// the p symbols at the first failing position (one readback) and a decode that
-// must add a shard: at most cap rounds, 1 + 2 cap host waits.  The repairs of
-// the confirmed sets are queued and left to the caller's final wait.
-int locate_set_list_device(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride,
-                           const uint32_t *stripes, size_t nlist, uint64_t S, int cap, int stride, bool repair,
-                           hipStream_t s, int32_t *count, int32_t *shards) {
-    const int k = c->k, p = c->p;
-    const LocateSet &ls = c->locate_set;
-    for (size_t e = 0; e < nlist; e++) count[e] = RS_SCRUB_UNLOCATED;
-    std::fill(shards, shards + nlist * (size_t)stride, -1);
-    if (!nlist) return RS_OK;
-    uint64_t qs = S;  // locate_list_device's scratch rule
-    const uint64_t ds = k > 1 ? row_stride : 0;
-    if (c->bs_ok && ds >= S && ds <= 2 * S && encode_bs_fits(k, p, ds, S)) qs = ds;
-    const size_t slot_bytes = align256((size_t)p * qs);
-    size_t chunk = std::min<size_t>(nlist, (size_t)kScrubMaxList);
-    chunk = std::min(chunk, std::max<size_t>(1, kScrubListScratch / slot_bytes));
-    if (const int knob = g_path_scrub_chunk.load(std::memory_order_relaxed)) chunk = std::min(chunk, (size_t)knob);
-    if (int e = scratch_ensure(c, c->scrub_rows, chunk * slot_bytes)) return e;
-    // scan results of a pass: [first, 8 bytes per entry][rowbad, p ints]
-    const size_t o_rowbad = align256(8 * chunk), scan_bytes = o_rowbad + align256(4 * chunk * p);
-    if (int e = scratch_ensure(c, c->scrub_list_dev, scan_bytes)) return e;
-    if (scan_bytes > c->scrub_list_host.n) {
-        if (int e = scratch_host_wait(c)) return e;
-        HIP_TRY(c->scrub_list_host.ensure(scan_bytes));
-    }
-    // confirm and pick results: [bad, 1 int per candidate][used, 8 ints][fail, 8 bytes][symbols, p per pick]
-    const size_t o_used = align256(4 * chunk), o_fail = o_used + align256(32 * chunk);
-    const size_t o_sym = o_fail + align256(8 * chunk), set_bytes = o_sym + align256(4 * chunk * p);
-    if (int e = scratch_ensure(c, c->scrub_set_dev, set_bytes)) return e;
-    if (set_bytes > c->scrub_set_host.n) {
-        if (int e = scratch_host_wait(c)) return e;
-        HIP_TRY(c->scrub_set_host.ensure(set_bytes));
-    }
-    uint8_t *q = c->scrub_rows.p, *dev = c->scrub_list_dev.p, *sdev = c->scrub_set_dev.p;
-    uint8_t *host = c->scrub_list_host.p, *shost = c->scrub_set_host.p;
-    ScrubListArgs a{};
-    a.base = base;
-    a.row_stride = row_stride;
-    a.stripe_stride = stripe_stride;
-    a.fresh = q;
-    a.fresh_stride = qs;
-    a.fresh_slot_stride = slot_bytes;
-    a.S = S;
-    a.k = k;
-    a.p = p;
-    a.first = (unsigned long long *)dev;
-    a.rowbad = (int *)(dev + o_rowbad);
-    ScrubSetArgs b{};
-    b.base = base;
-    b.row_stride = row_stride;
-    b.stripe_stride = stripe_stride;
-    b.fresh = q;
-    b.fresh_stride = qs;
-    b.fresh_slot_stride = slot_bytes;
-    b.S = S;
-    b.k = k;
-    b.p = p;
-    b.sym = (uint32_t *)(sdev + o_sym);
-    b.bad = (int *)sdev;
-    b.used = (int *)(sdev + o_used);
-    b.fail = (unsigned long long *)(sdev + o_fail);
-    const size_t twb = (size_t)c->twd * 4, db = 4 * (size_t)kScrubSetDescDwords;
-    const int piece = upd_piece(c);
-    std::vector<SetCand> conf, pick, good;
-    std::vector<int> cols;
-    std::vector<uint32_t> gcol, sym((size_t)p);
-    std::vector<std::vector<uint32_t>> G;  // generator columns of the data shards of a piece
-
-    // Descriptors and A^-1 tables of cand[n0..n1) (one column set `us`) into
-    // the slot image h: descriptor i at h + db * i, tables from h + o_tw.
-    // wr: the fix's write bits, one word per candidate (nullptr: the confirm).
-    auto describe = [&](const std::vector<SetCand> &cand, size_t n0, size_t n1, const UpdColSet *us, const uint32_t *zs,
-                        uint8_t *h, size_t o_tw, size_t &ntab, const uint32_t *wr) -> bool {
-        G.assign(cols.size(), {});
-        for (size_t i = n0; i < n1; i++) {
-            const SetCand &cd = cand[i];
-            uint32_t *d = (uint32_t *)(h + db * i);
-            std::fill(d, d + kScrubSetDescDwords, 0u);
-            const int sd = cd.nd(k);
-            d[0] = zs[cd.e];
-            d[1] = cd.e;
-            d[2] = (uint32_t)i;
-            d[3] = (uint32_t)sd;
-            for (int x = 0; x < kScrubSetMax; x++) d[12 + x] = 0xffffffffu;
-            for (int x = sd; x < cd.nj; x++) d[12 + x - sd] = (uint32_t)(cd.J[x] - k);
-            // R: the first sd parity rows not in J_p
-            int R[kLocateSetMax] = {}, nr = 0;
-            for (int r = 0; r < p && nr < sd; r++) {
-                bool ex = false;
-                for (int x = sd; x < cd.nj; x++) ex |= cd.J[x] - k == r;
-                if (!ex) R[nr++] = r;
-            }
-            if (nr < sd) return false;
-            uint32_t A[kLocateSetMax * kLocateSetMax], inv[kLocateSetMax * kLocateSetMax];
-            for (int j = 0; j < sd; j++) {
-                const size_t slot = (size_t)(std::lower_bound(cols.begin(), cols.end(), cd.J[j]) - cols.begin());
-                if (G[slot].empty())
-                    generator_column_from(*c->F, k, p, cd.J[j], c->enc_ifft_logs, c->enc_fft_logs, G[slot]);
-                d[4 + j] = (uint32_t)(std::lower_bound(us->cols.begin(), us->cols.end(), cd.J[j]) - us->cols.begin());
-                d[8 + j] = (uint32_t)R[j];
-                d[17 + j] = (uint32_t)cd.J[j];
-                for (int r = 0; r < sd; r++) A[r * sd + j] = G[slot][R[r]];
-            }
-            if (!invert_matrix(*c->F, sd, A, inv)) return false;
-            d[16] = (uint32_t)ntab;
-            for (int x = 0; x < sd * sd; x++, ntab++)
-                make_twiddle(*c->F, inv[x] ? c->F->log[inv[x]] : c->F->mod, (uint32_t *)(h + o_tw + ntab * twb), true);
-            d[21] = wr ? wr[i] : 0;
-        }
-        return true;
-    };
-    // Cuts cand (sorted by its sets) into pieces of at most `piece` distinct
-    // data columns and runs `launch` over each with the piece's column set.
-    auto for_pieces = [&](std::vector<SetCand> &cand, const uint32_t *zs, const uint32_t *wr, bool fix) -> int {
-        const size_t nc = cand.size();
-        size_t ntot = 0;  // A^-1 tables: sd * sd per candidate
-        for (const SetCand &cd : cand) ntot += (size_t)cd.nd(k) * cd.nd(k);
-        const size_t o_tw = align256(db * nc), slot_need = o_tw + std::max<size_t>(1, ntot) * twb;
-        int slot = 0;
-        uint8_t *h = nullptr, *g = nullptr;
-        if (int e = ring_acquire(c, slot_need, slot, h, g)) return e;
-        size_t ntab = 0;
-        b.inv_tw = (const uint32_t *)(g + o_tw);
-        for (size_t n0 = 0, n1 = 0; n0 < nc; n0 = n1) {
-            cols.clear();
-            for (n1 = n0; n1 < nc; n1++) {
-                std::vector<int> add;
-                for (int x = 0; x < cand[n1].nj && cand[n1].J[x] < k; x++)
-                    if (!std::binary_search(cols.begin(), cols.end(), cand[n1].J[x])) add.push_back(cand[n1].J[x]);
-                if (n1 > n0 && (int)(cols.size() + add.size()) > piece) break;
-                cols.insert(cols.end(), add.begin(), add.end());
-                std::sort(cols.begin(), cols.end());
-            }
-            UpdColSet *us = nullptr;
-            if (!cols.empty())
-                if (int e = upd_col_set(c, cols, &us)) return e;
-            const size_t t0 = ntab;
-            // (an MDS generator has no singular minor, and |J| <= p / 2 leaves the rows R)
-            if (!describe(cand, n0, n1, us, zs, h, o_tw, ntab, wr)) return RS_ERR_DEVICE;
-            HIP_TRY(hipMemcpyAsync(g + db * n0, h + db * n0, db * (n1 - n0), hipMemcpyHostToDevice, s));
-            if (ntab > t0)
-                HIP_TRY(hipMemcpyAsync(g + o_tw + t0 * twb, h + o_tw + t0 * twb, (ntab - t0) * twb, hipMemcpyHostToDevice, s));
-            b.list = (const uint32_t *)(g + db * n0);
-            b.nlist = (int)(n1 - n0);
-            b.col_tw = us ? us->tw : b.inv_tw;  // no data shard in the piece: never read
-            if (fix) HIP_TRY(launch_syndrome_fix_set(c->bits, b, s));
-            else HIP_TRY(launch_syndrome_confirm_set(c->bits, b, s));
-            if (us) HIP_TRY(us->mark_used(s));
-        }
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
-        return RS_OK;
-    };
-    auto by_set = [](const SetCand &x, const SetCand &y) {
-        return std::lexicographical_compare(x.J, x.J + x.nj, y.J, y.J + y.nj);
-    };
-
-    for (size_t c0 = 0; c0 < nlist; c0 += chunk) {
-        const size_t n = std::min(chunk, nlist - c0);
-        const uint32_t *zs = stripes + c0;
-        int32_t *cnt = count + c0, *sh = shards + c0 * (size_t)stride;
-        int slot = 0;
-        uint8_t *h = nullptr, *g = nullptr;
-        if (int e = ring_acquire(c, 4 * n, slot, h, g)) return e;
-        std::memcpy(h, zs, 4 * n);
-        HIP_TRY(hipMemcpyAsync(g, h, 4 * n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(dev, 0xff, 8 * n, s));
-        HIP_TRY(hipMemsetAsync(dev + o_rowbad, 0, scan_bytes - o_rowbad, s));
-        for (size_t e = 0; e < n; e++) {
-            const RowSet data{nullptr, base + (size_t)zs[e] * stripe_stride, ds};
-            const RowSet par{nullptr, q + e * slot_bytes, p > 1 ? qs : 0};
-            if (int err = encode_device(c, data, par, S, 0, 1, nullptr, s)) return err;
-        }
-        a.list = (const uint32_t *)g;
-        a.nlist = (int)n;
-        HIP_TRY(launch_syndrome_scan_list(c->bits, a, s));
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
-        HIP_TRY(hipMemcpyAsync((void *)host, dev, scan_bytes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        g_set_passes++, g_set_waits++;
-        conf.clear(), pick.clear(), good.clear();
-        const volatile uint64_t *first = (const volatile uint64_t *)host;
-        for (size_t e = 0; e < n; e++) {
-            const volatile int *rowbad = (const volatile int *)(host + o_rowbad) + e * p;
-            SetCand cd;
-            cd.e = (uint32_t)e;
-            int nb = 0;
-            for (int i = 0; i < p; i++)
-                if (rowbad[i]) {
-                    if (nb < cap) cd.J[nb] = k + i;
-                    nb++;
-                }
-            if (!nb) {
-                cnt[e] = 0;
-            } else if (nb <= cap && nb < p) {  // still confirmed
-                cd.nj = nb;
-                conf.push_back(cd);
-            } else if (first[e] < S) {
-                cd.pos = first[e];
-                pick.push_back(cd);
-            }
-        }
-        std::vector<uint32_t> wr;
-        while (true) {
-            if (!pick.empty()) {
-                // all p syndrome symbols at each candidate's position, decoded on the host
-                const size_t np = pick.size();
-                if (int e = ring_acquire(c, 4 * kScrubPickDescDwords * np, slot, h, g)) return e;
-                uint32_t *d = (uint32_t *)h;
-                for (size_t i = 0; i < np; i++, d += kScrubPickDescDwords)
-                    d[0] = zs[pick[i].e], d[1] = pick[i].e, d[2] = (uint32_t)pick[i].pos, d[3] = (uint32_t)(pick[i].pos >> 32);
-                HIP_TRY(hipMemcpyAsync(g, h, 4 * kScrubPickDescDwords * np, hipMemcpyHostToDevice, s));
-                b.list = (const uint32_t *)g;
-                b.nlist = (int)np;
-                HIP_TRY(launch_syndrome_pick_rows(c->bits, b, s));
-                HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-                c->ring_used[slot] = true;
-                HIP_TRY(hipMemcpyAsync((void *)(shost + o_sym), sdev + o_sym, 4 * np * p, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                g_set_waits++;
-                const volatile uint32_t *hs = (const volatile uint32_t *)(shost + o_sym);
-                for (size_t i = 0; i < np; i++) {
-                    SetCand cd = pick[i];
-                    for (int r = 0; r < p; r++) sym[r] = hs[i * p + r];
-                    int32_t found[kLocateSetMax];
-                    const int nf = locate_set_decode(*c->F, ls, sym.data(), cap, found);
-                    if (nf <= 0) continue;  // unlocated
-                    int merged[2 * kLocateSetMax];
-                    const int nm = (int)(std::set_union(cd.J, cd.J + cd.nj, found, found + nf, merged) - merged);
-                    if (nm == cd.nj || nm > cap) continue;  // a decode must add a shard, within cap
-                    std::copy(merged, merged + nm, cd.J);
-                    cd.nj = nm;
-                    conf.push_back(cd);
-                }
-                pick.clear();
-            }
-            if (conf.empty()) break;
-            std::stable_sort(conf.begin(), conf.end(), by_set);
-            const size_t nc = conf.size();
-            HIP_TRY(hipMemsetAsync(sdev, 0, o_fail, s));
-            HIP_TRY(hipMemsetAsync(sdev + o_fail, 0xff, 8 * nc, s));
-            if (int e = for_pieces(conf, zs, nullptr, false)) return e;
-            HIP_TRY(hipMemcpyAsync((void *)shost, sdev, o_fail + 8 * nc, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            g_set_rounds++, g_set_waits++;
-            const volatile int *bad = (const volatile int *)shost;
-            const volatile int *used = (const volatile int *)(shost + o_used);
-            const volatile uint64_t *fail = (const volatile uint64_t *)(shost + o_fail);
-            for (size_t i = 0; i < nc; i++) {
-                SetCand cd = conf[i];
-                if (!bad[i]) {
-                    // located: the shards that really change, and their write bits for the fix
-                    const int sd = cd.nd(k);
-                    uint32_t w = 0;
-                    int c1 = 0;
-                    int32_t *out = sh + (size_t)cd.e * stride;
-                    for (int x = 0; x < cd.nj; x++) {
-                        const int word = x < sd ? x : 4 + (x - sd);
-                        if (!used[8 * i + word]) continue;
-                        w |= 1u << word;
-                        out[c1++] = cd.J[x];
-                    }
-                    if (!c1) continue;  // (the scan said bad: cannot happen)
-                    cnt[cd.e] = c1;
-                    good.push_back(cd);
-                    wr.push_back(w);
-                } else if (cd.nj < cap && fail[i] < S) {
-                    cd.pos = fail[i];
-                    pick.push_back(cd);
-                }
-            }
-            conf.clear();
-            if (pick.empty()) break;
-        }
-        if (repair && !good.empty()) {
-            // (good is in confirm order round by round; the fix sorts it again with its write bits)
-            std::vector<size_t> idx(good.size());
-            for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
-            std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return by_set(good[x], good[y]); });
-            std::vector<SetCand> gs;
-            std::vector<uint32_t> ws;
-            for (size_t i : idx) gs.push_back(good[i]), ws.push_back(wr[i]);
-            if (int e = for_pieces(gs, zs, ws.data(), true)) return e;
-        }
-    }
-    return RS_OK;
-}
-
-// The set locate of a list on stream s inside the caller's scratch_acquire /
-// scratch_release: cap == 1 is the one-shard route unchanged.
-int locate_set_device(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, const uint32_t *stripes,
-                      size_t nlist, uint64_t S, int max_shards, int repair, hipStream_t s, int32_t *count,
-                      int32_t *shards) {
-    const int cap = locate_set_cap(c, max_shards);
-    int err = RS_OK;
-    if (cap == 1) {
-        // the one-shard route unchanged, its verdicts re-encoded
-        std::vector<int32_t> v(nlist);
-        err = locate_list_device(c, base, row_stride, stripe_stride, stripes, nlist, S, repair != 0, s, v.data());
-        for (size_t e = 0; e < nlist && !err; e++) {
-            std::fill(shards + e * (size_t)max_shards, shards + (e + 1) * (size_t)max_shards, -1);
-            count[e] = v[e] == RS_SCRUB_CLEAN ? 0 : v[e] >= 0 ? 1 : RS_SCRUB_UNLOCATED;
-            if (v[e] >= 0) shards[e * (size_t)max_shards] = v[e];
-        }
-    } else {
-        err = locate_set_list_device(c, base, row_stride, stripe_stride, stripes, nlist, S, cap, max_shards, repair != 0, s,
-                                     count, shards);
-    }
-    return err;
-}
-
-// rs_locate_set_dev_batch after its argument checks.  Complete on return.
-int locate_set_call(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, const uint32_t *stripes,
-                    size_t nlist, uint64_t S, int max_shards, int repair, int32_t *count, int32_t *shards, void *stream) {
-    DevCall dc(c, stream);
-    if (dc.err) return dc.err;
-    const hipStream_t s = dc.s;
-    if (int e = scratch_acquire(c, s)) return e;
-    const int err = locate_set_device(c, base, row_stride, stripe_stride, stripes, nlist, S, max_shards, repair, s, count, shards);
-    if (int e = scratch_release(c, s)) return err ? err : e;
-    if (err) return err;
-    HIP_TRY(hipStreamSynchronize(s));  // the queued repairs
-    return RS_OK;
-}
-
-// rs_scrub_set_dev_batch after its argument checks: the map, then the set
-// locate over the bad stripes.  Complete on return.
-int scrub_set_call(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, int nstripes, uint64_t S,
-                   int max_shards, int repair, int32_t *count, int32_t *shards, int *nbad, void *stream) {
-    DevCall dc(c, stream);
-    if (dc.err) return dc.err;
-    const hipStream_t s = dc.s;
-    if (int e = scratch_acquire(c, s)) return e;
-    std::vector<uint32_t> zs;
-    std::vector<int32_t> cn, sh;
-    const int *flags = nullptr;
-    int err = verify_map_device(c, base, row_stride, stripe_stride, nstripes, S, s, &flags);
-    for (int z = 0; z < nstripes && !err; z++)
-        if (((const volatile int *)flags)[z] != 0) zs.push_back((uint32_t)z);
-    if (!err && !zs.empty()) {
-        cn.resize(zs.size()), sh.resize(zs.size() * (size_t)max_shards);
-        err = locate_set_device(c, base, row_stride, stripe_stride, zs.data(), zs.size(), S, max_shards, repair, s, cn.data(),
-                                sh.data());
-    }
-    if (int e = scratch_release(c, s)) return err ? err : e;
-    if (err) return err;
-    HIP_TRY(hipStreamSynchronize(s));  // the queued repairs
-    std::fill(count, count + nstripes, 0);
-    std::fill(shards, shards + (size_t)nstripes * max_shards, -1);
-    for (size_t t = 0; t < zs.size(); t++) {
-        // (the map said bad; a clean scan cannot follow on unchanged rows)
-        count[zs[t]] = cn[t] == 0 ? RS_SCRUB_UNLOCATED : cn[t];
-        if (cn[t] > 0)
-            std::copy(sh.begin() + t * max_shards, sh.begin() + (t + 1) * max_shards, shards + (size_t)zs[t] * max_shards);
-    }
-    if (nbad) *nbad = (int)zs.size();
-    return RS_OK;
-}
-
-// The three scrub calls after their argument checks.  d != nullptr: one stripe
-// by row pointers (verdict[0]); else the slab at `base`: the map (bad != nullptr:
-// one byte per stripe), then, with verdict != nullptr, the locate of each bad
-// stripe: one at a time, or through locate_list_device ("scrub_batch" knob).
-// Complete on return (the results are read back).
-int scrub_call(rs_codec *c, uint8_t *const *d, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride, int nstripes,
-               uint64_t S, int repair, uint8_t *bad, int32_t *verdict, int *nbad, void *stream) {
-    DevCall dc(c, stream);
-    if (dc.err) return dc.err;
-    const hipStream_t s = dc.s;
-    if (int e = scratch_acquire(c, s)) return e;
-    int count = 0, err = RS_OK;
-    if (d) {
-        int v = RS_SCRUB_UNLOCATED;
-        err = locate_stripe(c, d, S, repair != 0, s, &v);
-        verdict[0] = v;
-    } else {
-        const int *flags = nullptr;
-        err = verify_map_device(c, base, row_stride, stripe_stride, nstripes, S, s, &flags);
-        std::vector<int> todo;
-        for (int z = 0; z < nstripes && !err; z++) {
-            const bool b = ((const volatile int *)flags)[z] != 0;
-            count += b;
-            if (bad) bad[z] = b;
-            if (verdict) verdict[z] = b ? RS_SCRUB_UNLOCATED : RS_SCRUB_CLEAN;
-            if (b && verdict) todo.push_back(z);
-        }
-        const int knob = g_path_scrub_batch.load(std::memory_order_relaxed);
-        if (!err && !todo.empty() && (knob == 1 || (knob < 0 && todo.size() >= kScrubBatchMin))) {
-            const std::vector<uint32_t> zs(todo.begin(), todo.end());
-            std::vector<int32_t> v(zs.size());
-            err = locate_list_device(c, base, row_stride, stripe_stride, zs.data(), zs.size(), S, repair != 0, s, v.data());
-            for (size_t t = 0; t < zs.size() && !err; t++)
-                verdict[zs[t]] = v[t] == RS_SCRUB_CLEAN ? RS_SCRUB_UNLOCATED : v[t];
-            todo.clear();
-        }
-        std::vector<uint8_t *> rows((size_t)c->total);
-        for (size_t t = 0; t < todo.size() && !err; t++) {
-            uint8_t *sb = base + (size_t)todo[t] * stripe_stride;
-            for (int i = 0; i < c->total; i++) rows[i] = sb + (size_t)i * row_stride;
-            int v = RS_SCRUB_UNLOCATED;
-            err = locate_stripe(c, rows.data(), S, repair != 0, s, &v);
-            // (the map said bad; a clean scan cannot follow on unchanged rows)
-            verdict[todo[t]] = v == RS_SCRUB_CLEAN ? RS_SCRUB_UNLOCATED : v;
-        }
-    }
-    if (int e = scratch_release(c, s)) return err ? err : e;
-    if (err) return err;
-    HIP_TRY(hipStreamSynchronize(s));  // a queued repair copy
-    if (nbad) *nbad = count;
-    return RS_OK;
-}
-
 // The rules rs_reconstruct_dev, rs_reconstruct_dev_batch and the host
 // reconstructs share (leopard16.go:390-430), on the shards marked present.
 // done: `return` is the call's result (an error, or RS_OK with nothing to rebuild).
@@ -3187,6 +1711,100 @@ int pattern_set(rs_codec *c, const std::vector<const uint8_t *> &pats, bool all,
     return RS_OK;
 }
 
+// What a call with a pattern table does per stripe range (cut_ranges).
+struct RangeCut {
+    std::function<void()> begin;                                      // a new range: forget the last one's stripes
+    std::function<std::vector<uint8_t>(size_t q)> key;                // table row q's flags: rows with equal keys share a descriptor
+    std::function<bool(size_t q)> skip;                               // nothing to do for a stripe of row q (noted by skip itself)
+    std::function<size_t(size_t q, int cq)> cost;                     // table bytes a new member adds
+    std::function<int(size_t q, int cq)> add;                         // a new member: its number in the range
+    std::function<void(size_t at, size_t q, int cq, int id)> stripe;  // stripe `at` of the range takes member `id`
+    std::function<int(size_t z0, size_t z1)> launch;                  // the range [z0, z1), which has members
+};
+
+// Cuts the stripes into ranges [z0, z1), each within the table budget
+// (kPatSetBudget) and the stripe limit (kPatMaxStripes), each with a set of
+// its own.  Equal rows of the table share a member: the canonical row of q is
+// the first referenced row with q's key.
+int cut_ranges(size_t npat, size_t nstripes, const uint32_t *pattern_of, const RangeCut &rc) {
+    std::vector<int> canon(npat, -1);  // -1: not looked at yet
+    std::map<std::vector<uint8_t>, int> seen;
+    std::vector<int> id_of(npat, -1);  // a canonical row's number in the current range
+    std::vector<int> members;
+    for (size_t z0 = 0; z0 < nstripes;) {
+        size_t bytes = 0, z1 = z0;
+        members.clear();
+        rc.begin();
+        for (; z1 < nstripes && z1 - z0 < kPatMaxStripes; z1++) {
+            const size_t q = pattern_of[z1];
+            if (rc.skip(q)) continue;
+            if (canon[q] < 0) canon[q] = seen.emplace(rc.key(q), (int)q).first->second;
+            const int cq = canon[q];
+            if (id_of[cq] < 0) {
+                const size_t need = rc.cost(q, cq);
+                if (!members.empty() && bytes + need > kPatSetBudget) break;
+                bytes += need;
+                id_of[cq] = rc.add(q, cq);
+                members.push_back(cq);
+            }
+            rc.stripe(z1 - z0, q, cq, id_of[cq]);
+        }
+        for (int cq : members) id_of[cq] = -1;
+        if (!members.empty())
+            if (int e = rc.launch(z0, z1)) return e;
+        z0 = z1;
+    }
+    return RS_OK;
+}
+
+// The restricted tier's launch of a range takes the bit-sliced decoder where
+// the codec has one (rs_debug_set_path "pat_tier" 1: the LDS-resident kernel
+// there too).
+bool pattern_set_bs(const PatternSet *ps) { return ps->bs_ok && g_path_pat_tier.load(std::memory_order_relaxed) != 1; }
+// What that launch reads, into the ring slot's host half: the stripes with
+// something to rebuild, each with its descriptor (bit-sliced), else the
+// descriptor of every stripe of the range (-1: none).  Returns the former's number.
+int pattern_range_list(bool bs, const std::vector<int> &idx, uint8_t *h) {
+    int na = 0;
+    if (bs) {
+        RecStripe *list = (RecStripe *)h;
+        for (size_t i = 0; i < idx.size(); i++)
+            if (idx[i] >= 0) list[na++] = RecStripe{(int)i, idx[i]};
+    } else {
+        std::memcpy(h, idx.data(), idx.size() * sizeof(int));
+    }
+    return na;
+}
+// The launch over the nstripes stripes at rb, with that list at g.
+int launch_pattern_range(rs_codec *c, PatternSet *ps, bool bs, const uint8_t *g, int nactive, uint8_t *rb, size_t row_stride,
+                         size_t stripe_stride, size_t nstripes, size_t S, hipStream_t s) {
+    DevPlan none;  // the shared fields only: the descriptors carry the pattern's
+    RecArgs ra = rec_args(c, &none, S);
+    ra.base = rb;
+    ra.stride = row_stride;
+    ra.stripe_stride = stripe_stride;
+    ra.nstripes = (int)nstripes;
+    if (bs) {
+        RecBsPatArgs ba{};
+        ba.a = ra;
+        ba.pat = ps->desc;
+        ba.tiles = (const RecStripe *)g;
+        ba.nactive = nactive;
+        std::memcpy(ba.code1, ps->code1, sizeof(ba.code1));
+        HIP_TRY(launch_rec_bs256_patterns(ba, s));
+    } else {
+        RecPatArgs pa{};
+        pa.a = ra;
+        pa.pat = ps->desc;
+        pa.pat_of = (const int *)g;
+        HIP_TRY(launch_rec_lds_patterns(c->bits, c->logn, c->dec_sub, pa, s));
+    }
+    HIP_TRY(ps->mark_used(s));
+    return RS_OK;
+}
+
+}  // namespace
+namespace rs {
 // rs_reconstruct_dev_batch_patterns after its NULL checks.
 int reconstruct_patterns_call(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
                               const uint8_t *present, size_t npat, const uint32_t *pattern_of, size_t S, bool all,
@@ -3234,530 +1852,44 @@ int reconstruct_patterns_call(rs_codec *c, uint8_t *base, size_t row_stride, siz
         }
         return RS_OK;
     }
-    // Equal rows of the table share a descriptor: canon[q] is the first
-    // referenced row with q's flags (-1: not looked at yet).
-    std::vector<int> canon(npat, -1);
-    std::map<std::vector<uint8_t>, int> seen;
-    auto canon_of = [&](size_t q) {
-        if (canon[q] < 0) {
-            std::vector<uint8_t> f(total);
-            for (int i = 0; i < total; i++) f[i] = present[q * total + i] != 0;
-            canon[q] = seen.emplace(std::move(f), (int)q).first->second;
-        }
-        return canon[q];
+    // Per range one launch over a pattern set of its own.
+    std::vector<const uint8_t *> pats;
+    std::vector<int> idx;  // descriptor per stripe of the range, -1: nothing to rebuild
+    RangeCut rc;
+    rc.begin = [&] { pats.clear(), idx.clear(); };
+    rc.key = [&](size_t q) {
+        std::vector<uint8_t> f(total);
+        for (int i = 0; i < total; i++) f[i] = present[q * total + i] != 0;
+        return f;
     };
-    // Stripe ranges [z0, z1), each within the table budget and the stripe
-    // limit, each one launch over a pattern set of its own.
-    std::vector<int> desc_of(npat, -1);  // descriptor of a canonical pattern in the current range
-    std::vector<int> idx;
-    for (size_t z0 = 0; z0 < nstripes;) {
-        std::vector<const uint8_t *> pats;
-        std::vector<int> members;
-        size_t bytes = 0, z1 = z0;
-        idx.clear();
-        for (; z1 < nstripes && z1 - z0 < kPatMaxStripes; z1++) {
-            const size_t q = pattern_of[z1];
-            if (!todo[q]) {
-                idx.push_back(-1);
-                continue;
-            }
-            const int cq = canon_of(q);
-            if (desc_of[cq] < 0) {
-                const size_t need = pattern_layout(c, todo[cq]).total + sizeof(RecPattern);
-                if (!pats.empty() && bytes + need > kPatSetBudget) break;
-                bytes += need;
-                desc_of[cq] = (int)pats.size();
-                pats.push_back(present + (size_t)cq * total);
-                members.push_back(cq);
-            }
-            idx.push_back(desc_of[cq]);
-        }
-        for (int cq : members) desc_of[cq] = -1;
-        if (!pats.empty()) {
-            PatternSet *ps = nullptr;
-            if (int e = pattern_set(c, pats, all, &ps)) return e;
-            // the bit-sliced decoder where the codec has one (rs_debug_set_path
-            // "pat_tier" 1: the LDS-resident kernel there too)
-            const bool bs = ps->bs_ok && g_path_pat_tier.load(std::memory_order_relaxed) != 1;
-            int slot = 0;
-            uint8_t *h = nullptr, *g = nullptr;
-            const size_t ib = idx.size() * (bs ? sizeof(RecStripe) : sizeof(int));
-            if (int e = ring_acquire(c, ib, slot, h, g)) return e;
-            DevPlan none;  // the shared fields only: the descriptors carry the pattern's
-            RecArgs ra = rec_args(c, &none, S);
-            ra.base = base + z0 * stripe_stride;
-            ra.stride = row_stride;
-            ra.stripe_stride = stripe_stride;
-            ra.nstripes = (int)(z1 - z0);
-            if (bs) {
-                // the stripes with something to rebuild, each with its descriptor
-                RecStripe *list = (RecStripe *)h;
-                int na = 0;
-                for (size_t i = 0; i < idx.size(); i++)
-                    if (idx[i] >= 0) list[na++] = RecStripe{(int)i, idx[i]};
-                HIP_TRY(hipMemcpyAsync(g, h, (size_t)na * sizeof(RecStripe), hipMemcpyHostToDevice, s));
-                RecBsPatArgs ba{};
-                ba.a = ra;
-                ba.pat = ps->desc;
-                ba.tiles = (const RecStripe *)g;
-                ba.nactive = na;
-                std::memcpy(ba.code1, ps->code1, sizeof(ba.code1));
-                HIP_TRY(launch_rec_bs256_patterns(ba, s));
-            } else {
-                std::memcpy(h, idx.data(), ib);
-                HIP_TRY(hipMemcpyAsync(g, h, ib, hipMemcpyHostToDevice, s));
-                RecPatArgs pa{};
-                pa.a = ra;
-                pa.pat = ps->desc;
-                pa.pat_of = (const int *)g;
-                HIP_TRY(launch_rec_lds_patterns(c->bits, c->logn, c->dec_sub, pa, s));
-            }
-            HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-            c->ring_used[slot] = true;
-            HIP_TRY(ps->mark_used(s));
-        }
-        z0 = z1;
-    }
-    return dc.finish(RS_OK);
-}
-
-// ---- Checked rebuild (rs_reconstruct_checked_dev_batch_patterns)
-// Passes, confirm rounds and host waits of the checked locate so far (rs_debug_checked_stats).
-std::atomic<uint64_t> g_chk_passes{0}, g_chk_rounds{0}, g_chk_waits{0};
-
-// An erasure pattern of the call with a bad stripe: its coefficient rows,
-// built once per call, and the check columns asked for so far.
-constexpr size_t kChkCacheBytes = 64u << 20;
-struct ChkPattern {
-    std::vector<uint8_t> present;
-    std::shared_ptr<const PresentPattern> ppp;
-    int cap = 0;  // cap_z of its stripes
-    std::map<int, std::vector<uint32_t>> H;
-    const std::vector<uint32_t> &column(rs_codec *c, int t) {
-        auto it = H.find(t);
-        if (it == H.end()) {
-            std::vector<uint32_t> h((size_t)c->p);
-            check_column(*c->F, c->k, c->p, *ppp, t, c->enc_ifft_logs, c->enc_fft_logs, h.data());
-            it = H.emplace(t, std::move(h)).first;
-        }
-        return it->second;
-    }
-};
-
-// A candidate set of corrupt survivors of a listed stripe: nj shards J, ascending.
-struct ChkCand {
-    uint32_t e = 0;  // entry of the pass (its scratch slot)
-    int pat = 0;     // its ChkPattern
-    int nj = 0;
-    int J[kLocateSetMax] = {};
-    uint64_t pos = 0;  // where the next decode reads its symbols
-};
-
-// count[e] and shards[e * stride ..] for stripes[0..nlist), each with missing
-// rows already filled from its survivors and with cap_z >= 1, on the caller's
-// stream s inside the caller's scratch_acquire / scratch_release, with
-// locate_set_list_device's pass rules.  Per pass: the recompute and the list
-// scan with one readback (host wait 1); every bad entry is decoded at its
-// first differing position (errors and erasures); then rounds of
-// k_syndrome_confirm_set over all candidates, the check columns H[.][t] as its
-// column tables and no J_p (one readback), and for those that fail with room
-// left a pick at the first failing position (one readback) and a decode that
-// must add a survivor: at most cap rounds, 1 + 2 cap host waits.  The repairs
-// of the confirmed sets are one k_syndrome_fix_present launch, left to the
-// caller's final wait.
-int locate_present_list_device(rs_codec *c, uint8_t *base, uint64_t row_stride, uint64_t stripe_stride,
-                               const uint32_t *stripes, const int *pat_of, size_t nlist, std::vector<ChkPattern> &pats,
-                               uint64_t S, int stride, bool repair, hipStream_t s, int32_t *count, int32_t *shards) {
-    const int k = c->k, p = c->p;
-    const LocatePresent &lp = c->locate_present;
-    for (size_t e = 0; e < nlist; e++) count[e] = RS_SCRUB_UNLOCATED;
-    std::fill(shards, shards + nlist * (size_t)stride, -1);
-    if (!nlist) return RS_OK;
-    uint64_t qs = S;  // locate_list_device's scratch rule
-    const uint64_t ds = k > 1 ? row_stride : 0;
-    if (c->bs_ok && ds >= S && ds <= 2 * S && encode_bs_fits(k, p, ds, S)) qs = ds;
-    const size_t slot_bytes = align256((size_t)p * qs);
-    const size_t twb = (size_t)c->twd * 4, db = 4 * (size_t)kScrubSetDescDwords;
-    size_t chunk = std::min<size_t>(nlist, (size_t)kScrubMaxList);
-    chunk = std::min(chunk, std::max<size_t>(1, kScrubListScratch / slot_bytes));
-    // a candidate's tables: up to four check columns of p entries, and as many fix coefficients per missing row
-    chunk = std::min(chunk, std::max<size_t>(1, (64u << 20) / (2 * kLocateSetMax * (size_t)p * twb)));
-    if (const int knob = g_path_scrub_chunk.load(std::memory_order_relaxed)) chunk = std::min(chunk, (size_t)knob);
-    if (int e = scratch_ensure(c, c->scrub_rows, chunk * slot_bytes)) return e;
-    const size_t o_rowbad = align256(8 * chunk), scan_bytes = o_rowbad + align256(4 * chunk * p);
-    if (int e = scratch_ensure(c, c->scrub_list_dev, scan_bytes)) return e;
-    if (scan_bytes > c->scrub_list_host.n) {
-        if (int e = scratch_host_wait(c)) return e;
-        HIP_TRY(c->scrub_list_host.ensure(scan_bytes));
-    }
-    // confirm and pick results, as locate_set_list_device
-    const size_t o_used = align256(4 * chunk), o_fail = o_used + align256(32 * chunk);
-    const size_t o_sym = o_fail + align256(8 * chunk), set_bytes = o_sym + align256(4 * chunk * p);
-    if (int e = scratch_ensure(c, c->scrub_set_dev, set_bytes)) return e;
-    if (set_bytes > c->scrub_set_host.n) {
-        if (int e = scratch_host_wait(c)) return e;
-        HIP_TRY(c->scrub_set_host.ensure(set_bytes));
-    }
-    uint8_t *q = c->scrub_rows.p, *dev = c->scrub_list_dev.p, *sdev = c->scrub_set_dev.p;
-    uint8_t *host = c->scrub_list_host.p, *shost = c->scrub_set_host.p;
-    ScrubListArgs a{};
-    a.base = base;
-    a.row_stride = row_stride;
-    a.stripe_stride = stripe_stride;
-    a.fresh = q;
-    a.fresh_stride = qs;
-    a.fresh_slot_stride = slot_bytes;
-    a.S = S;
-    a.k = k;
-    a.p = p;
-    a.first = (unsigned long long *)dev;
-    a.rowbad = (int *)(dev + o_rowbad);
-    ScrubSetArgs b{};
-    b.base = base;
-    b.row_stride = row_stride;
-    b.stripe_stride = stripe_stride;
-    b.fresh = q;
-    b.fresh_stride = qs;
-    b.fresh_slot_stride = slot_bytes;
-    b.S = S;
-    b.k = k;
-    b.p = p;
-    b.sym = (uint32_t *)(sdev + o_sym);
-    b.bad = (int *)sdev;
-    b.used = (int *)(sdev + o_used);
-    b.fail = (unsigned long long *)(sdev + o_fail);
-    std::vector<ChkCand> conf, pick, good;
-    std::vector<uint32_t> sym((size_t)p);
-    std::vector<int> order((size_t)p);
-    auto log_of = [&](uint32_t v) { return v ? c->F->log[v] : c->F->mod; };
-    auto same = [](const ChkCand &x, const ChkCand &y) {
-        return x.pat == y.pat && x.nj == y.nj && std::equal(x.J, x.J + x.nj, y.J);
+    rc.skip = [&](size_t q) {
+        if (!todo[q]) idx.push_back(-1);
+        return !todo[q];
     };
-    auto by_set = [](const ChkCand &x, const ChkCand &y) {
-        if (x.pat != y.pat) return x.pat < y.pat;
-        return std::lexicographical_compare(x.J, x.J + x.nj, y.J, y.J + y.nj);
+    rc.cost = [&](size_t, int cq) { return pattern_layout(c, todo[cq]).total + sizeof(RecPattern); };
+    rc.add = [&](size_t, int cq) {
+        pats.push_back(present + (size_t)cq * total);
+        return (int)pats.size() - 1;
     };
-
-    // One launch over cand (sorted by by_set): the confirm, or with wr (the
-    // write bits, one word per candidate) the fix.  Candidates with equal
-    // (pattern, T) share their tables.  Image of the ring slot: descriptors,
-    // A^-1 tables, then the check columns (confirm) or the missing rows' numbers
-    // and the fix coefficients (fix).
-    auto launch = [&](const std::vector<ChkCand> &cand, const uint32_t *zs, const uint32_t *wr) -> int {
-        const size_t nc = cand.size();
-        size_t ninv = 0, ncol = 0, nrow = 0, nfix = 0;
-        for (size_t i = 0; i < nc; i++) {
-            if (i && same(cand[i - 1], cand[i])) continue;
-            const size_t sj = (size_t)cand[i].nj, ne = pats[cand[i].pat].ppp->E.size();
-            ninv += sj * sj, ncol += sj, nrow += ne, nfix += ne * sj;
-        }
-        const size_t o_inv = align256(db * nc), o_col = o_inv + align256(ninv * twb);
-        const size_t o_rows = o_col, o_fix = o_rows + align256(4 * nrow);
-        const size_t need = wr ? o_fix + std::max<size_t>(1, nfix) * twb : o_col + ncol * (size_t)p * twb;
+    rc.stripe = [&](size_t, size_t, int, int id) { idx.push_back(id); };
+    rc.launch = [&](size_t z0, size_t z1) -> int {
+        PatternSet *ps = nullptr;
+        if (int e = pattern_set(c, pats, all, &ps)) return e;
+        const bool bs = pattern_set_bs(ps);
         int slot = 0;
         uint8_t *h = nullptr, *g = nullptr;
-        if (int e = ring_acquire(c, need, slot, h, g)) return e;
-        size_t tinv = 0, tcol = 0, trow = 0, tfix = 0;
-        for (size_t i = 0; i < nc; i++) {
-            const ChkCand &cd = cand[i];
-            uint32_t *d = (uint32_t *)(h + db * i);
-            if (i && same(cand[i - 1], cd)) {
-                std::copy(d - kScrubSetDescDwords, d, d);
-            } else {
-                ChkPattern &pt = pats[cd.pat];
-                std::fill(d, d + kScrubSetDescDwords, 0u);
-                const uint32_t *cols[kLocateSetMax] = {};
-                for (int j = 0; j < cd.nj; j++) cols[j] = pt.column(c, cd.J[j]).data();
-                // R: rows of surviving parity shards outside T first, so that a
-                // row D is formed from is written only where nothing else works
-                check_row_order(k, p, pt.present.data(), cd.J, cd.nj, order.data());
-                int R[kLocateSetMax] = {};
-                uint32_t inv[kLocateSetMax * kLocateSetMax];
-                // (|T| <= p - e: the punctured code's distance gives the columns full rank)
-                if (!pick_check_rows(*c->F, p, cd.nj, cols, order.data(), R, inv)) return RS_ERR_DEVICE;
-                d[3] = (uint32_t)cd.nj;
-                for (int x = 0; x < kScrubSetMax; x++) d[12 + x] = 0xffffffffu;  // the confirm: no J_p
-                d[16] = (uint32_t)tinv;
-                for (int x = 0; x < cd.nj * cd.nj; x++, tinv++)
-                    make_twiddle(*c->F, log_of(inv[x]), (uint32_t *)(h + o_inv + tinv * twb), true);
-                for (int j = 0; j < cd.nj; j++) {
-                    d[8 + j] = (uint32_t)R[j];
-                    d[17 + j] = (uint32_t)cd.J[j];
-                    if (!wr) {
-                        d[4 + j] = (uint32_t)tcol;
-                        for (int i2 = 0; i2 < p; i2++)
-                            make_twiddle(*c->F, log_of(cols[j][i2]), (uint32_t *)(h + o_col + (tcol * p + i2) * twb), true);
-                        tcol++;
-                    }
-                }
-                if (wr) {
-                    const size_t ne = pt.ppp->E.size();
-                    d[12] = (uint32_t)ne;
-                    d[13] = (uint32_t)trow;
-                    d[14] = (uint32_t)tfix;
-                    for (size_t x = 0; x < ne; x++) {
-                        ((uint32_t *)(h + o_rows))[trow++] = (uint32_t)pt.ppp->E[x];
-                        for (int j = 0; j < cd.nj; j++, tfix++)
-                            make_twiddle(*c->F, log_of(pt.ppp->co[x][cd.J[j]]), (uint32_t *)(h + o_fix + tfix * twb), true);
-                    }
-                }
-            }
-            d[0] = zs[cd.e];
-            d[1] = cd.e;
-            d[2] = (uint32_t)i;
-            d[21] = wr ? wr[i] : 0;
-        }
-        HIP_TRY(hipMemcpyAsync(g, h, need, hipMemcpyHostToDevice, s));
-        b.list = (const uint32_t *)g;
-        b.nlist = (int)nc;
-        b.inv_tw = (const uint32_t *)(g + o_inv);
-        if (wr) {
-            ScrubPresentArgs pa{};
-            pa.set = b;
-            pa.rows = (const uint32_t *)(g + o_rows);
-            pa.fix_tw = (const uint32_t *)(g + o_fix);
-            HIP_TRY(launch_syndrome_fix_present(c->bits, pa, s));
-        } else {
-            b.col_tw = (const uint32_t *)(g + o_col);
-            HIP_TRY(launch_syndrome_confirm_set(c->bits, b, s));
-        }
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
-        return RS_OK;
+        const size_t ib = idx.size() * (bs ? sizeof(RecStripe) : sizeof(int));
+        if (int e = ring_acquire(c, ib, slot, h, g)) return e;
+        const int na = pattern_range_list(bs, idx, h);
+        HIP_TRY(hipMemcpyAsync(g, h, bs ? (size_t)na * sizeof(RecStripe) : ib, hipMemcpyHostToDevice, s));
+        if (int e = launch_pattern_range(c, ps, bs, g, na, base + z0 * stripe_stride, row_stride, stripe_stride, z1 - z0, S, s))
+            return e;
+        return ring_post(c, slot, s);
     };
-
-    for (size_t c0 = 0; c0 < nlist; c0 += chunk) {
-        const size_t n = std::min(chunk, nlist - c0);
-        const uint32_t *zs = stripes + c0;
-        int32_t *cnt = count + c0, *sh = shards + c0 * (size_t)stride;
-        int slot = 0;
-        uint8_t *h = nullptr, *g = nullptr;
-        if (int e = ring_acquire(c, 4 * n, slot, h, g)) return e;
-        std::memcpy(h, zs, 4 * n);
-        HIP_TRY(hipMemcpyAsync(g, h, 4 * n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(dev, 0xff, 8 * n, s));
-        HIP_TRY(hipMemsetAsync(dev + o_rowbad, 0, scan_bytes - o_rowbad, s));
-        for (size_t e = 0; e < n; e++) {
-            const RowSet data{nullptr, base + (size_t)zs[e] * stripe_stride, ds};
-            const RowSet par{nullptr, q + e * slot_bytes, p > 1 ? qs : 0};
-            if (int err = encode_device(c, data, par, S, 0, 1, nullptr, s)) return err;
-        }
-        a.list = (const uint32_t *)g;
-        a.nlist = (int)n;
-        HIP_TRY(launch_syndrome_scan_list(c->bits, a, s));
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
-        HIP_TRY(hipMemcpyAsync((void *)host, dev, scan_bytes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        g_chk_passes++, g_chk_waits++;
-        conf.clear(), pick.clear(), good.clear();
-        const volatile uint64_t *first = (const volatile uint64_t *)host;
-        for (size_t e = 0; e < n; e++) {
-            // a corrupt survivor reaches the parity rows through the rebuilt
-            // rows too: no shortcut from the rows that differ, every entry is decoded
-            ChkCand cd;
-            cd.e = (uint32_t)e;
-            cd.pat = pat_of[c0 + e];
-            if (first[e] >= S) {
-                cnt[e] = 0;  // (the map said bad: cannot happen)
-                continue;
-            }
-            cd.pos = first[e];
-            pick.push_back(cd);
-        }
-        std::vector<uint32_t> wr;
-        while (true) {
-            if (!pick.empty()) {
-                const size_t np = pick.size();
-                if (int e = ring_acquire(c, 4 * kScrubPickDescDwords * np, slot, h, g)) return e;
-                uint32_t *d = (uint32_t *)h;
-                for (size_t i = 0; i < np; i++, d += kScrubPickDescDwords)
-                    d[0] = zs[pick[i].e], d[1] = pick[i].e, d[2] = (uint32_t)pick[i].pos, d[3] = (uint32_t)(pick[i].pos >> 32);
-                HIP_TRY(hipMemcpyAsync(g, h, 4 * kScrubPickDescDwords * np, hipMemcpyHostToDevice, s));
-                b.list = (const uint32_t *)g;
-                b.nlist = (int)np;
-                HIP_TRY(launch_syndrome_pick_rows(c->bits, b, s));
-                HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-                c->ring_used[slot] = true;
-                HIP_TRY(hipMemcpyAsync((void *)(shost + o_sym), sdev + o_sym, 4 * np * p, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                g_chk_waits++;
-                const volatile uint32_t *hs = (const volatile uint32_t *)(shost + o_sym);
-                for (size_t i = 0; i < np; i++) {
-                    ChkCand cd = pick[i];
-                    const ChkPattern &pt = pats[cd.pat];
-                    for (int r = 0; r < p; r++) sym[r] = hs[i * p + r];
-                    int32_t found[kLocateSetMax];
-                    const int nf = locate_set_decode_present(*c->F, lp, pt.present.data(), sym.data(), pt.cap, found);
-                    if (nf <= 0) continue;  // unlocated
-                    int merged[2 * kLocateSetMax];
-                    const int nm = (int)(std::set_union(cd.J, cd.J + cd.nj, found, found + nf, merged) - merged);
-                    if (nm == cd.nj || nm > pt.cap) continue;  // a decode must add a survivor, within cap_z
-                    std::copy(merged, merged + nm, cd.J);
-                    cd.nj = nm;
-                    conf.push_back(cd);
-                }
-                pick.clear();
-            }
-            if (conf.empty()) break;
-            std::stable_sort(conf.begin(), conf.end(), by_set);
-            const size_t nc = conf.size();
-            HIP_TRY(hipMemsetAsync(sdev, 0, o_fail, s));
-            HIP_TRY(hipMemsetAsync(sdev + o_fail, 0xff, 8 * nc, s));
-            if (int e = launch(conf, zs, nullptr)) return e;
-            HIP_TRY(hipMemcpyAsync((void *)shost, sdev, o_fail + 8 * nc, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            g_chk_rounds++, g_chk_waits++;
-            const volatile int *bad = (const volatile int *)shost;
-            const volatile int *used = (const volatile int *)(shost + o_used);
-            const volatile uint64_t *fail = (const volatile uint64_t *)(shost + o_fail);
-            for (size_t i = 0; i < nc; i++) {
-                ChkCand cd = conf[i];
-                if (!bad[i]) {
-                    // located: the survivors that really change, and their write bits for the fix
-                    uint32_t w = 0;
-                    int c1 = 0;
-                    int32_t *out = sh + (size_t)cd.e * stride;
-                    for (int x = 0; x < cd.nj; x++) {
-                        if (!used[8 * i + x]) continue;
-                        w |= 1u << x;
-                        out[c1++] = cd.J[x];
-                    }
-                    if (!c1) continue;  // (the scan said bad: cannot happen)
-                    cnt[cd.e] = c1;
-                    good.push_back(cd);
-                    wr.push_back(w);
-                } else if (cd.nj < pats[cd.pat].cap && fail[i] < S) {
-                    cd.pos = fail[i];
-                    pick.push_back(cd);
-                }
-            }
-            conf.clear();
-            if (pick.empty()) break;
-        }
-        if (repair && !good.empty()) {
-            std::vector<size_t> idx(good.size());
-            for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
-            std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return by_set(good[x], good[y]); });
-            std::vector<ChkCand> gs;
-            std::vector<uint32_t> ws;
-            for (size_t i : idx) gs.push_back(good[i]), ws.push_back(wr[i]);
-            if (int e = launch(gs, zs, ws.data())) return e;
-        }
-    }
-    return RS_OK;
+    return dc.finish(cut_ranges(npat, nstripes, pattern_of, rc));
 }
-
-// rs_reconstruct_checked_dev_batch_patterns after its argument checks: the
-// patterns reconstruct and the per-stripe map, unchanged; then the stripes the
-// map calls bad, those with nothing missing through the set locate, the others
-// through locate_present_list_device.  Complete on return.
-int reconstruct_checked_call(rs_codec *c, uint8_t *base, size_t row_stride, size_t stripe_stride, size_t nstripes,
-                             const uint8_t *present, size_t npat, const uint32_t *pattern_of, size_t S, int max_shards,
-                             int repair, int32_t *count, int32_t *shards, int *nbad, void *stream) {
-    const int total = c->total, k = c->k, p = c->p;
-    const int stride = std::max(max_shards, 1);
-    std::fill(count, count + nstripes, 0);
-    std::fill(shards, shards + nstripes * (size_t)stride, -1);
-    if (!nstripes) return RS_OK;
-    if (int e = reconstruct_patterns_call(c, base, row_stride, stripe_stride, nstripes, present, npat, pattern_of, S, true,
-                                          stream))
-        return e;
-    DevCall dc(c, stream);
-    if (dc.err) return dc.err;
-    const hipStream_t s = dc.s;
-    if (int e = scratch_acquire(c, s)) return e;
-    std::vector<uint32_t> zfull, zpres;  // bad stripes with nothing missing / with missing rows and cap_z >= 1
-    std::vector<int> pat_of;             // the ChkPattern of each entry of zpres
-    std::vector<ChkPattern> pats;
-    std::vector<int> chk_of(npat, -1);
-    std::map<std::vector<uint8_t>, int> seen;
-    std::vector<int32_t> cn, sh;
-    int bad = 0;
-    auto body = [&]() -> int {
-        const int *flags = nullptr;
-        if (int e = verify_map_device(c, base, row_stride, stripe_stride, (int)nstripes, S, s, &flags)) return e;
-        for (size_t z = 0; z < nstripes; z++) {
-            if (((const volatile int *)flags)[z] == 0) continue;
-            bad++;
-            count[z] = RS_SCRUB_UNLOCATED;
-            const size_t qn = pattern_of[z];
-            const uint8_t *pr = present + qn * total;
-            int ne = 0;
-            for (int i = 0; i < total; i++) ne += pr[i] ? 0 : 1;
-            if (!ne) {
-                if (max_shards >= 1) zfull.push_back((uint32_t)z);
-                continue;
-            }
-            const int capz = std::min(max_shards, (p - ne) / 2);
-            if (capz < 1) continue;
-            if (!c->locate_present_built) {
-                make_locate_present(*c->F, k, p, c->locate_present);
-                c->locate_present_built = true;
-            }
-            if (!c->locate_present.shift) continue;  // no shift point: nothing is located
-            if (chk_of[qn] < 0) {
-                std::vector<uint8_t> f(total);
-                for (int i = 0; i < total; i++) f[i] = pr[i] != 0;
-                auto ins = seen.emplace(f, (int)pats.size());
-                if (ins.second) {
-                    if (int e = build_decode_plan(c)) return e;
-                    if (!c->dec_ok) return RS_ERR_PANIC;
-                    pats.emplace_back();
-                    ChkPattern &pt = pats.back();
-                    pt.present = std::move(f);
-                    pt.cap = capz;
-                    auto hit = c->chk_cache.find(pt.present);
-                    if (hit == c->chk_cache.end()) {
-                        auto pp = std::make_shared<PresentPattern>();
-                        if (!make_present_pattern(*c->F, k, p, pt.present.data(), c->enc_ifft_logs, c->enc_fft_logs,
-                                                  c->dec_ifft_logs, c->dec_fft_logs, *pp))
-                            return RS_ERR_PANIC;
-                        const size_t bytes = total + (size_t)ne * 4 * ((size_t)total + p);
-                        if (c->chk_cache_bytes + bytes > kChkCacheBytes) c->chk_cache.clear(), c->chk_cache_bytes = 0;
-                        c->chk_cache_bytes += bytes;
-                        hit = c->chk_cache.emplace(pt.present, std::move(pp)).first;
-                    }
-                    pt.ppp = hit->second;
-                }
-                chk_of[qn] = ins.first->second;
-            }
-            zpres.push_back((uint32_t)z);
-            pat_of.push_back(chk_of[qn]);
-        }
-        if (!zfull.empty()) {
-            cn.assign(zfull.size(), 0), sh.assign(zfull.size() * (size_t)max_shards, -1);
-            if (int e = locate_set_device(c, base, row_stride, stripe_stride, zfull.data(), zfull.size(), S, max_shards, repair,
-                                          s, cn.data(), sh.data()))
-                return e;
-            for (size_t t = 0; t < zfull.size(); t++) {
-                // (the map said bad; a clean scan cannot follow on unchanged rows)
-                count[zfull[t]] = cn[t] == 0 ? RS_SCRUB_UNLOCATED : cn[t];
-                if (cn[t] > 0)
-                    std::copy(sh.begin() + t * max_shards, sh.begin() + (t + 1) * max_shards,
-                              shards + (size_t)zfull[t] * stride);
-            }
-        }
-        if (!zpres.empty()) {
-            cn.assign(zpres.size(), 0), sh.assign(zpres.size() * (size_t)stride, -1);
-            if (int e = locate_present_list_device(c, base, row_stride, stripe_stride, zpres.data(), pat_of.data(), zpres.size(),
-                                                   pats, S, stride, repair != 0, s, cn.data(), sh.data()))
-                return e;
-            for (size_t t = 0; t < zpres.size(); t++) {
-                count[zpres[t]] = cn[t] == 0 ? RS_SCRUB_UNLOCATED : cn[t];
-                if (cn[t] > 0)
-                    std::copy(sh.begin() + t * stride, sh.begin() + (t + 1) * stride, shards + (size_t)zpres[t] * stride);
-            }
-        }
-        return RS_OK;
-    };
-    const int err = body();
-    if (int e = scratch_release(c, s)) return err ? err : e;
-    if (err) return err;
-    HIP_TRY(hipStreamSynchronize(s));  // the queued repairs
-    if (nbad) *nbad = bad;
-    return RS_OK;
-}
+}  // namespace rs
+namespace {
 
 // ---- A (present, required) pair per stripe (rs_reconstruct_rows_dev_batch_patterns)
 static_assert(sizeof(RowsSetDesc) == sizeof(RowsPattern) && offsetof(RowsSetDesc, tw) == offsetof(RowsPattern, tw) &&
@@ -3875,148 +2007,93 @@ int rows_patterns_launch(rs_codec *c, uint8_t *base, size_t row_stride, size_t s
         }
         return RS_OK;
     }
-    // Equal pairs share a descriptor: canon[q] is the first referenced table
-    // row with q's present and wanted flags (-1: not looked at yet).
-    std::vector<int> canon(npat, -1);
-    std::map<std::vector<uint8_t>, int> seen;
-    auto canon_of = [&](size_t q) {
-        if (canon[q] < 0) {
-            std::vector<uint8_t> f(pres.begin() + q * total, pres.begin() + (q + 1) * total);
-            f.insert(f.end(), want.begin() + q * total, want.begin() + (q + 1) * total);
-            canon[q] = seen.emplace(std::move(f), (int)q).first->second;
-        }
-        return canon[q];
+    // Stripe ranges within the table budget (direct and restricted tables
+    // together).  Per range: one rows set and one launch per wanted-row count
+    // for the direct stripes, one pattern set and one launch for the others.
+    std::vector<RowsSetPair> pairs;
+    std::vector<const uint8_t *> pats, wants;
+    std::vector<int> idx;           // restricted tier: descriptor per stripe of the range, -1: not its stripe
+    std::vector<RecStripe> direct;  // direct tier: (stripe of the range, pair of the range)
+    RangeCut rc;
+    rc.begin = [&] { pairs.clear(), pats.clear(), wants.clear(), idx.clear(), direct.clear(); };
+    rc.key = [&](size_t q) {
+        std::vector<uint8_t> f(pres.begin() + q * total, pres.begin() + (q + 1) * total);
+        f.insert(f.end(), want.begin() + q * total, want.begin() + (q + 1) * total);
+        return f;
     };
-    // Stripe ranges [z0, z1), each within the table budget (direct and
-    // restricted tables together) and the stripe limit.  Per range: one rows
-    // set and one launch per wanted-row count for the direct stripes, one
-    // pattern set and one launch for the others.
-    std::vector<int> id_of(npat, -1);  // a canonical pair's number in the current range (pair or pattern)
-    std::vector<int> idx;              // restricted tier: descriptor per stripe of the range, -1: not its stripe
-    std::vector<RecStripe> direct;     // direct tier: (stripe of the range, pair of the range)
-    for (size_t z0 = 0; z0 < nstripes;) {
-        std::vector<RowsSetPair> pairs;
-        std::vector<const uint8_t *> pats, wants;
-        std::vector<int> members;
-        size_t bytes = 0, z1 = z0;
-        int nrest = 0;
-        idx.clear();
-        direct.clear();
-        for (; z1 < nstripes && z1 - z0 < kPatMaxStripes; z1++) {
-            const size_t q = pattern_of[z1];
-            if (!todo[q]) {
-                idx.push_back(-1);
-                continue;
-            }
-            const int cq = canon_of(q);
-            const bool dir = rows_pat_direct(c, todo[cq]);
-            if (id_of[cq] < 0) {
-                const size_t need = dir ? rows_set_pair_bytes(c->bits, npres[cq], todo[cq], kDecGroup)
-                                        : pattern_layout(c, todo[cq]).total + sizeof(RecPattern);
-                if (!members.empty() && bytes + need > kPatSetBudget) break;
-                bytes += need;
-                if (dir) {
-                    id_of[cq] = (int)pairs.size();
-                    pairs.push_back(RowsSetPair{pres.data() + (size_t)cq * total, want.data() + (size_t)cq * total});
-                } else {
-                    id_of[cq] = (int)pats.size();
-                    pats.push_back(pres.data() + (size_t)cq * total);
-                    wants.push_back(want.data() + (size_t)cq * total);
-                }
-                members.push_back(cq);
-            }
-            if (dir) {
-                direct.push_back(RecStripe{(int)(z1 - z0), id_of[cq]});
-                idx.push_back(-1);
-            } else {
-                idx.push_back(id_of[cq]);
-                nrest++;
-            }
+    rc.skip = [&](size_t q) {
+        if (!todo[q]) idx.push_back(-1);
+        return !todo[q];
+    };
+    rc.cost = [&](size_t, int cq) {
+        return rows_pat_direct(c, todo[cq]) ? rows_set_pair_bytes(c->bits, npres[cq], todo[cq], kDecGroup)
+                                            : pattern_layout(c, todo[cq]).total + sizeof(RecPattern);
+    };
+    rc.add = [&](size_t, int cq) {
+        if (rows_pat_direct(c, todo[cq])) {
+            pairs.push_back(RowsSetPair{pres.data() + (size_t)cq * total, want.data() + (size_t)cq * total});
+            return (int)pairs.size() - 1;
         }
-        for (int cq : members) id_of[cq] = -1;
-        if (!members.empty()) {
-            RowsSet *rs = nullptr;
-            PatternSet *ps = nullptr;
-            // direct stripes by wanted-row count: one list, one launch each; a
-            // pair of more than kDecGroup rows is in several lists
-            std::vector<RecStripe> lists[kDecGroup + 1];
-            if (!pairs.empty()) {
-                if (int e = rows_set(c, pairs, &rs)) return e;
-                for (const RecStripe &st : direct)
-                    for (int d = rs->first_desc[st.pat]; d < rs->first_desc[st.pat + 1]; d++)
-                        lists[rs->desc_t[d]].push_back(RecStripe{st.stripe, d});
-            }
-            if (!pats.empty())
-                if (int e = pattern_set(c, pats, false, &ps, &wants)) return e;
-            const bool bs = ps && ps->bs_ok && g_path_pat_tier.load(std::memory_order_relaxed) != 1;
-            // one ring slot: the restricted tier's list, then the direct lists
-            size_t off[kDecGroup + 1] = {};
-            size_t ib = ps ? align256(bs ? (size_t)nrest * sizeof(RecStripe) : idx.size() * sizeof(int)) : 0;
-            for (int t = 1; t <= kDecGroup; t++) {
-                off[t] = ib;
-                ib += align256(lists[t].size() * sizeof(RecStripe));
-            }
-            int slot = 0;
-            uint8_t *h = nullptr, *g = nullptr;
-            if (int e = ring_acquire(c, ib, slot, h, g)) return e;
-            if (ps) {
-                if (bs) {
-                    RecStripe *list = (RecStripe *)h;
-                    int na = 0;
-                    for (size_t i = 0; i < idx.size(); i++)
-                        if (idx[i] >= 0) list[na++] = RecStripe{(int)i, idx[i]};
-                } else {
-                    std::memcpy(h, idx.data(), idx.size() * sizeof(int));
-                }
-            }
-            for (int t = 1; t <= kDecGroup; t++)
-                if (!lists[t].empty()) std::memcpy(h + off[t], lists[t].data(), lists[t].size() * sizeof(RecStripe));
-            HIP_TRY(hipMemcpyAsync(g, h, ib, hipMemcpyHostToDevice, s));
-            uint8_t *rb = base + z0 * stripe_stride;
-            for (int t = 1; t <= kDecGroup; t++) {
-                if (lists[t].empty()) continue;
-                DecodeRowsPatArgs da{};
-                da.base = rb;
-                da.row_stride = row_stride;
-                da.stripe_stride = stripe_stride;
-                da.pat = rs->desc;
-                da.list = (const RecStripe *)(g + off[t]);
-                da.S = S;
-                da.nlist = (int)lists[t].size();
-                da.nt = t;
-                HIP_TRY(launch_decode_rows_patterns(c->bits, da, s));
-            }
-            if (ps) {
-                DevPlan none;  // the shared fields only: the descriptors carry the pattern's
-                RecArgs ra = rec_args(c, &none, S);
-                ra.base = rb;
-                ra.stride = row_stride;
-                ra.stripe_stride = stripe_stride;
-                ra.nstripes = (int)(z1 - z0);
-                if (bs) {
-                    RecBsPatArgs ba{};
-                    ba.a = ra;
-                    ba.pat = ps->desc;
-                    ba.tiles = (const RecStripe *)g;
-                    ba.nactive = nrest;
-                    std::memcpy(ba.code1, ps->code1, sizeof(ba.code1));
-                    HIP_TRY(launch_rec_bs256_patterns(ba, s));
-                } else {
-                    RecPatArgs pa{};
-                    pa.a = ra;
-                    pa.pat = ps->desc;
-                    pa.pat_of = (const int *)g;
-                    HIP_TRY(launch_rec_lds_patterns(c->bits, c->logn, c->dec_sub, pa, s));
-                }
-                HIP_TRY(ps->mark_used(s));
-            }
-            HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-            c->ring_used[slot] = true;
-            if (rs) HIP_TRY(rs->mark_used(s));
+        pats.push_back(pres.data() + (size_t)cq * total);
+        wants.push_back(want.data() + (size_t)cq * total);
+        return (int)pats.size() - 1;
+    };
+    rc.stripe = [&](size_t at, size_t, int cq, int id) {
+        const bool dir = rows_pat_direct(c, todo[cq]);
+        if (dir) direct.push_back(RecStripe{(int)at, id});
+        idx.push_back(dir ? -1 : id);
+    };
+    rc.launch = [&](size_t z0, size_t z1) -> int {
+        RowsSet *rs = nullptr;
+        PatternSet *ps = nullptr;
+        // direct stripes by wanted-row count: one list, one launch each; a
+        // pair of more than kDecGroup rows is in several lists
+        std::vector<RecStripe> lists[kDecGroup + 1];
+        if (!pairs.empty()) {
+            if (int e = rows_set(c, pairs, &rs)) return e;
+            for (const RecStripe &st : direct)
+                for (int d = rs->first_desc[st.pat]; d < rs->first_desc[st.pat + 1]; d++)
+                    lists[rs->desc_t[d]].push_back(RecStripe{st.stripe, d});
         }
-        z0 = z1;
-    }
-    return RS_OK;
+        if (!pats.empty())
+            if (int e = pattern_set(c, pats, false, &ps, &wants)) return e;
+        const bool bs = ps && pattern_set_bs(ps);
+        const size_t nrest = idx.size() - std::count(idx.begin(), idx.end(), -1);
+        // one ring slot: the restricted tier's list, then the direct lists
+        size_t off[kDecGroup + 1] = {};
+        size_t ib = ps ? align256(bs ? nrest * sizeof(RecStripe) : idx.size() * sizeof(int)) : 0;
+        for (int t = 1; t <= kDecGroup; t++) {
+            off[t] = ib;
+            ib += align256(lists[t].size() * sizeof(RecStripe));
+        }
+        int slot = 0;
+        uint8_t *h = nullptr, *g = nullptr;
+        if (int e = ring_acquire(c, ib, slot, h, g)) return e;
+        if (ps) pattern_range_list(bs, idx, h);
+        for (int t = 1; t <= kDecGroup; t++)
+            if (!lists[t].empty()) std::memcpy(h + off[t], lists[t].data(), lists[t].size() * sizeof(RecStripe));
+        HIP_TRY(hipMemcpyAsync(g, h, ib, hipMemcpyHostToDevice, s));
+        uint8_t *rb = base + z0 * stripe_stride;
+        for (int t = 1; t <= kDecGroup; t++) {
+            if (lists[t].empty()) continue;
+            DecodeRowsPatArgs da{};
+            da.base = rb;
+            da.row_stride = row_stride;
+            da.stripe_stride = stripe_stride;
+            da.pat = rs->desc;
+            da.list = (const RecStripe *)(g + off[t]);
+            da.S = S;
+            da.nlist = (int)lists[t].size();
+            da.nt = t;
+            HIP_TRY(launch_decode_rows_patterns(c->bits, da, s));
+        }
+        if (ps)
+            if (int e = launch_pattern_range(c, ps, bs, g, (int)nrest, rb, row_stride, stripe_stride, z1 - z0, S, s)) return e;
+        if (int e = ring_post(c, slot, s)) return e;
+        if (rs) HIP_TRY(rs->mark_used(s));
+        return RS_OK;
+    };
+    return cut_ranges(npat, nstripes, pattern_of, rc);
 }
 
 // rs_reconstruct_rows_dev_batch_patterns after its NULL checks.
@@ -4145,8 +2222,7 @@ int rows_list_launches(rs_codec *c, const rs_stripe *st, const std::vector<RowsS
             a.nt = t;
             HIP_TRY(launch_decode_rows_list(c->bits, a, s));
         }
-        HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-        c->ring_used[slot] = true;
+        if (int e = ring_post(c, slot, s)) return e;
     }
     HIP_TRY(rs->mark_used(s));
     return RS_OK;
@@ -4322,80 +2398,70 @@ int reconstruct_rows_checked_call(rs_codec *c, uint8_t *base, size_t row_stride,
     HIP_TRY(c->rchk_bad.ensure(nstripes));
     HIP_TRY(c->rchk_host.ensure(nstripes * sizeof(int)));
     HIP_TRY(hipMemsetAsync(c->rchk_bad.p, 0, nstripes * sizeof(int), s));
-    // Equal (present, rows the fused kernel rebuilds) pairs share a descriptor.
-    std::vector<int> canon(npat, -1), id_of(npat, -1);
-    std::map<std::vector<uint8_t>, int> seen;
-    auto canon_of = [&](size_t q) {
-        if (canon[q] < 0) {
-            std::vector<uint8_t> f(tb.pres.begin() + q * total, tb.pres.begin() + (q + 1) * total);
-            if (fused[q]) f.insert(f.end(), tb.want.begin() + q * total, tb.want.begin() + (q + 1) * total);
-            canon[q] = seen.emplace(std::move(f), (int)q).first->second;
-        }
-        return canon[q];
-    };
-    // Stripe ranges as in rows_patterns_launch; per range one checked rows set
-    // and one launch per (rows, checks) count, rows == 0: check-only.
+    // Stripe ranges as in rows_patterns_launch; equal (present, rows the fused
+    // kernel rebuilds) pairs share a descriptor.  Per range one checked rows
+    // set and one launch per (rows, checks) count, rows == 0: check-only.
     constexpr int kMaxT = kDecGroup - kDecChecksMax;
-    for (size_t z0 = 0; z0 < nstripes;) {
-        std::vector<RowsChkPair> pairs;
-        std::vector<int> members;
-        std::vector<RecStripe> lists[kMaxT + 1][kDecChecksMax + 1];
-        size_t bytes = 0, z1 = z0;
-        for (; z1 < nstripes && z1 - z0 < kPatMaxStripes; z1++) {
-            const size_t q = pattern_of[z1];
-            if (!cz[q]) continue;
-            const int cq = canon_of(q), t = fused[q] ? tb.todo[q] : 0;
-            if (id_of[cq] < 0) {
-                const size_t need = rows_chk_pair_bytes(c->bits, tb.npres[cq], t, cz[cq]);
-                if (!members.empty() && bytes + need > kPatSetBudget) break;
-                bytes += need;
-                id_of[cq] = (int)pairs.size();
-                pairs.push_back(RowsChkPair{tb.pres.data() + (size_t)cq * total,
-                                            t ? tb.want.data() + (size_t)cq * total : nullptr, cz[cq]});
-                members.push_back(cq);
+    std::vector<RowsChkPair> pairs;
+    std::vector<RecStripe> lists[kMaxT + 1][kDecChecksMax + 1];
+    auto rows_of = [&](size_t q) { return fused[q] ? tb.todo[q] : 0; };
+    RangeCut rc;
+    rc.begin = [&] {
+        pairs.clear();
+        for (auto &lt : lists)
+            for (auto &l : lt) l.clear();
+    };
+    rc.key = [&](size_t q) {
+        std::vector<uint8_t> f(tb.pres.begin() + q * total, tb.pres.begin() + (q + 1) * total);
+        if (fused[q]) f.insert(f.end(), tb.want.begin() + q * total, tb.want.begin() + (q + 1) * total);
+        return f;
+    };
+    rc.skip = [&](size_t q) { return !cz[q]; };
+    rc.cost = [&](size_t q, int cq) { return rows_chk_pair_bytes(c->bits, tb.npres[cq], rows_of(q), cz[cq]); };
+    rc.add = [&](size_t q, int cq) {
+        pairs.push_back(RowsChkPair{tb.pres.data() + (size_t)cq * total,
+                                    rows_of(q) ? tb.want.data() + (size_t)cq * total : nullptr, cz[cq]});
+        return (int)pairs.size() - 1;
+    };
+    rc.stripe = [&](size_t at, size_t q, int cq, int id) { lists[rows_of(q)][cz[cq]].push_back(RecStripe{(int)at, id}); };
+    rc.launch = [&](size_t z0, size_t) -> int {
+        RowsChkSet *rs = nullptr;
+        if (int e = rows_chk_set(c, pairs, checks, &rs)) return e;
+        size_t off[kMaxT + 1][kDecChecksMax + 1] = {}, ib = 0;
+        for (int t = 0; t <= kMaxT; t++)
+            for (int nc = 1; nc <= kDecChecksMax; nc++) {
+                off[t][nc] = ib;
+                ib += align256(lists[t][nc].size() * sizeof(RecStripe));
             }
-            lists[t][cz[cq]].push_back(RecStripe{(int)(z1 - z0), id_of[cq]});
-        }
-        for (int cq : members) id_of[cq] = -1;
-        if (!members.empty()) {
-            RowsChkSet *rs = nullptr;
-            if (int e = rows_chk_set(c, pairs, checks, &rs)) return e;
-            size_t off[kMaxT + 1][kDecChecksMax + 1] = {}, ib = 0;
-            for (int t = 0; t <= kMaxT; t++)
-                for (int nc = 1; nc <= kDecChecksMax; nc++) {
-                    off[t][nc] = ib;
-                    ib += align256(lists[t][nc].size() * sizeof(RecStripe));
-                }
-            int slot = 0;
-            uint8_t *h = nullptr, *g = nullptr;
-            if (int e = ring_acquire(c, ib, slot, h, g)) return e;
-            for (int t = 0; t <= kMaxT; t++)
-                for (int nc = 1; nc <= kDecChecksMax; nc++)
-                    if (!lists[t][nc].empty())
-                        std::memcpy(h + off[t][nc], lists[t][nc].data(), lists[t][nc].size() * sizeof(RecStripe));
-            HIP_TRY(hipMemcpyAsync(g, h, ib, hipMemcpyHostToDevice, s));
-            for (int t = 0; t <= kMaxT; t++)
-                for (int nc = 1; nc <= kDecChecksMax; nc++) {
-                    if (lists[t][nc].empty()) continue;
-                    DecodeRowsChkArgs da{};
-                    da.base = base + z0 * stripe_stride;
-                    da.row_stride = row_stride;
-                    da.stripe_stride = stripe_stride;
-                    da.pat = rs->desc;
-                    da.list = (const RecStripe *)(g + off[t][nc]);
-                    da.bad = c->rchk_bad.p + z0;
-                    da.S = S;
-                    da.nlist = (int)lists[t][nc].size();
-                    da.nt = t;
-                    da.nc = nc;
-                    HIP_TRY(launch_decode_rows_checked(c->bits, da, s));
-                }
-            HIP_TRY(hipEventRecord(c->ring_ev[slot], s));
-            c->ring_used[slot] = true;
-            HIP_TRY(rs->mark_used(s));
-        }
-        z0 = z1;
-    }
+        int slot = 0;
+        uint8_t *h = nullptr, *g = nullptr;
+        if (int e = ring_acquire(c, ib, slot, h, g)) return e;
+        for (int t = 0; t <= kMaxT; t++)
+            for (int nc = 1; nc <= kDecChecksMax; nc++)
+                if (!lists[t][nc].empty())
+                    std::memcpy(h + off[t][nc], lists[t][nc].data(), lists[t][nc].size() * sizeof(RecStripe));
+        HIP_TRY(hipMemcpyAsync(g, h, ib, hipMemcpyHostToDevice, s));
+        for (int t = 0; t <= kMaxT; t++)
+            for (int nc = 1; nc <= kDecChecksMax; nc++) {
+                if (lists[t][nc].empty()) continue;
+                DecodeRowsChkArgs da{};
+                da.base = base + z0 * stripe_stride;
+                da.row_stride = row_stride;
+                da.stripe_stride = stripe_stride;
+                da.pat = rs->desc;
+                da.list = (const RecStripe *)(g + off[t][nc]);
+                da.bad = c->rchk_bad.p + z0;
+                da.S = S;
+                da.nlist = (int)lists[t][nc].size();
+                da.nt = t;
+                da.nc = nc;
+                HIP_TRY(launch_decode_rows_checked(c->bits, da, s));
+            }
+        if (int e = ring_post(c, slot, s)) return e;
+        HIP_TRY(rs->mark_used(s));
+        return RS_OK;
+    };
+    if (int e = cut_ranges(npat, nstripes, pattern_of, rc)) return e;
     HIP_TRY(hipMemcpyAsync(c->rchk_host.p, c->rchk_bad.p, nstripes * sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));  // the call's one host wait
     const int *flag = (const int *)c->rchk_host.p;

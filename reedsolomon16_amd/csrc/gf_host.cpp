@@ -947,6 +947,30 @@ bool invert_matrix(const Field &F, int s, const uint32_t *A, uint32_t *inv) {
     return true;
 }
 
+ScrubPassPlan scrub_pass_plan(int k, int p, uint64_t S, uint64_t row_stride, bool bs_fits, size_t nlist, int knob,
+                              size_t cand_bytes) {
+    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    ScrubPassPlan pl;
+    const uint64_t ds = k > 1 ? row_stride : 0;
+    pl.qs = bs_fits && ds >= S && ds <= 2 * S ? ds : S;
+    pl.slot_bytes = a256((size_t)p * pl.qs);
+    pl.chunk = std::min(nlist, kScrubPassMaxList);
+    pl.chunk = std::min(pl.chunk, std::max<size_t>(1, kScrubPassScratch / pl.slot_bytes));
+    if (cand_bytes) pl.chunk = std::min(pl.chunk, std::max<size_t>(1, kScrubPassTables / cand_bytes));
+    if (knob) pl.chunk = std::min(pl.chunk, (size_t)knob);
+    const size_t n = pl.chunk;
+    pl.o_rowbad = a256(8 * n);
+    pl.scan_bytes = pl.o_rowbad + a256(4 * n * p);
+    pl.o_pair = pl.scan_bytes;
+    pl.o_conf = pl.o_pair + a256(8 * n);
+    pl.list_bytes = pl.o_conf + a256(4 * n);
+    pl.o_used = a256(4 * n);
+    pl.o_fail = pl.o_used + a256(32 * n);
+    pl.o_sym = pl.o_fail + a256(8 * n);
+    pl.set_bytes = pl.o_sym + a256(4 * n * p);
+    return pl;
+}
+
 bool make_locate_present(const Field &F, int k, int p, LocatePresent &lp) {
     lp = LocatePresent{};
     if (k <= 0 || p <= 0) return false;

@@ -137,7 +137,7 @@ void make_update_tables(const Field &F, int k, int p, const int *idx, int t, con
                         const std::vector<uint32_t> &fft_logs, uint32_t *out);
 
 // ---- Update list: a list of changed rows, a different set per stripe
-// (rs_update_dev_batch_list, codec.cpp UpdColSet, kernels.hpp UpdateListArgs).
+// (rs_update_dev_batch_list, codec_impl.hpp UpdColSet, kernels.hpp UpdateListArgs).
 // Column tables: slot s holds make_update_tables' p x 1 output for idx =
 // {cols[s]}, table (s, i) at out + (s * p + i) * tw_dwords.
 void make_update_columns(const Field &F, int k, int p, const int *cols, int ncols, const std::vector<uint32_t> &ifft_logs,
@@ -310,7 +310,7 @@ void make_decode_tables(const Field &F, int k, int p, const uint8_t *erased, con
                         int t, uint32_t *out);
 
 // ---- Rows set: the decode tables of several (present, wanted rows) pairs in
-// one blob (rs_reconstruct_rows_dev_batch_patterns, codec.cpp RowsSet).
+// one blob (rs_reconstruct_rows_dev_batch_patterns, codec_impl.hpp RowsSet).
 // Layout: the descriptor array, then per pair its t x np tables
 // (make_decode_tables from the pair's exact error_locators), its np present
 // shard indices and its t wanted ones, each part 256-byte aligned.  A pair
@@ -398,6 +398,37 @@ int locate_set_decode(const Field &F, const LocateSet &ls, const uint32_t *e, in
 // inv = A^-1 for the s x s matrix A (row-major, s <= kLocateSetMax); false when singular.
 bool invert_matrix(const Field &F, int s, const uint32_t *A, uint32_t *inv);
 
+// ---- Scrub: the geometry of one pass of the list locates (rs_locate_dev_batch,
+// rs_locate_set_dev_batch, rs_reconstruct_checked_dev_batch_patterns).  A pass
+// recomputes the p parity rows of `chunk` listed stripes into scratch slots of
+// slot_bytes each, the rows of a slot qs apart: at the data rows' own stride
+// where that keeps the bit-sliced encode eligible (bs_fits, and S <= stride
+// <= 2 S; one stride for data and parity), else packed (qs = S).  It takes as
+// many stripes as fit kScrubPassScratch (always at least one), at most
+// kScrubPassMaxList (one per blockIdx.y), at most the "scrub_chunk" knob
+// (0: unset), and on the checked rebuild's route at most what keeps the
+// candidates' tables within kScrubPassTables (cand_bytes each, 0: no bound).
+// The device writes its results through these offsets and the host reads them
+// back through the same ones; every region is 256-byte aligned.
+//   scan buffer: [first differing position, 8 bytes per entry][rowbad, p ints
+//     per entry] = scan_bytes; the one-shard route adds [symbols, 2 dwords per
+//     entry][confirm word, 1 int per candidate] = list_bytes
+//   set buffer:  [bad, 1 int per candidate][used, 8 ints][fail, 8 bytes]
+//     [symbols, p dwords per pick] = set_bytes
+constexpr size_t kScrubPassMaxList = 32768;         // kernels.hpp kScrubMaxList
+constexpr size_t kScrubPassScratch = (size_t)1 << 30;
+constexpr size_t kScrubPassTables = (size_t)64 << 20;
+struct ScrubPassPlan {
+    uint64_t qs = 0;
+    size_t slot_bytes = 0, chunk = 0;
+    size_t o_rowbad = 0, scan_bytes = 0;            // scan buffer (first at 0)
+    size_t o_pair = 0, o_conf = 0, list_bytes = 0;  // ... the one-shard route's symbols and confirm words
+    size_t o_used = 0, o_fail = 0, o_sym = 0, set_bytes = 0;  // set buffer (bad at 0)
+};
+// row_stride: the distance of the data rows; k == 1 has none and packs.
+ScrubPassPlan scrub_pass_plan(int k, int p, uint64_t S, uint64_t row_stride, bool bs_fits, size_t nlist, int knob,
+                              size_t cand_bytes);
+
 // ---- Checked rebuild: which corrupt survivors explain the syndrome of a
 // stripe whose missing rows were filled from all survivors
 // (rs_reconstruct_checked_dev_batch_patterns).  With E the
@@ -481,7 +512,7 @@ bool make_check_weights(const Field &F, int k, int p, const uint8_t *present, in
 void make_check_tables(const Field &F, int k, int p, const uint8_t *present, int c, const uint32_t *w, uint32_t *out);
 
 // ---- Checked rows set: make_rows_set's blob with the check tables of each
-// pair behind its decode tables (codec.cpp RowsChkSet, kernels.hpp
+// pair behind its decode tables (codec_impl.hpp RowsChkSet, kernels.hpp
 // RowsChkPattern).  A pair rebuilds t >= 0 rows (wanted == nullptr or nothing
 // wanted and missing: the check-only form) with c >= 1 checks, t + c <= group:
 // one descriptor per pair, tables (t + c) x np.

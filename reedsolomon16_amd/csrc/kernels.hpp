@@ -193,7 +193,7 @@ hipError_t launch_rec_bs256(const RecArgs &a, hipStream_t s);
 
 // ---- A slab of stripes, each with an erasure pattern of its own
 // (rs_reconstruct_dev_batch_patterns).  Everything of RecArgs that depends on
-// the pattern, as one descriptor per pattern in HBM (codec.cpp PatternSet).
+// the pattern, as one descriptor per pattern in HBM (codec_impl.hpp PatternSet).
 struct RecPattern {
     const int *src_idx, *dst_idx;
     const uint32_t *tw_in, *tw_out;
@@ -334,7 +334,7 @@ hipError_t launch_decode_rows(int bits, const DecodeRowsArgs &a, hipStream_t s);
 
 // The same with a (present, wanted rows) pair per stripe
 // (rs_reconstruct_rows_dev_batch_patterns): what DecodeRowsArgs holds per
-// pair, as one descriptor in HBM (codec.cpp RowsSet; gf_host.hpp RowsSetDesc
+// pair, as one descriptor in HBM (codec_impl.hpp RowsSet; gf_host.hpp RowsSetDesc
 // is its host image), and a launch over a device list of (stripe, descriptor)
 // entries whose descriptors all rebuild nt rows.  Strided form only.
 struct RowsPattern {

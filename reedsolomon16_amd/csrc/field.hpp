@@ -1,9 +1,12 @@
 // What the transform kernels (kernels.hip) and the stream kernels
 // (stream_kernels.hip) share: the lane unit's loads and stores, the two
-// fields' byte-permute multiplies, the scalar-loaded twiddle table and the
-// grid helpers.  Everything but pick_narrow has internal linkage: each
+// fields' byte-permute multiplies, the scalar-loaded twiddle table, the grid
+// helpers and the launcher toolkit (with_field, with_count, with_bool).
+// Everything but pick_narrow has internal linkage: each
 // translation unit instantiates what it uses.
 #pragma once
+#include <type_traits>
+
 #include "kernels.hpp"
 
 namespace rs {
@@ -86,7 +89,7 @@ struct F16 {
     struct Vec {
         uint32_t l[W], h[W];
     };
-    __device__ static uint64_t units(uint64_t S) { return (S >> 6) * UPB; }
+    __host__ __device__ static uint64_t units(uint64_t S) { return (S >> 6) * UPB; }
     __device__ static uint64_t off(uint64_t u) { return (u / UPB) * 64 + (u % UPB) * (4 * W); }
     __device__ static Vec load(const uint8_t *row, uint64_t u) {
         Vec v;
@@ -173,7 +176,7 @@ struct F8 {
     struct Vec {
         uint32_t b[W];
     };
-    __device__ static uint64_t units(uint64_t S) { return S / (4 * W); }
+    __host__ __device__ static uint64_t units(uint64_t S) { return S / (4 * W); }
     __device__ static uint64_t off(uint64_t u) { return u * (4 * W); }
     __device__ static Vec load(const uint8_t *row, uint64_t u) {
         Vec v;
@@ -263,6 +266,27 @@ hipError_t for_y(int total, Fn body) {
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// ---------------------------------------------------------------- launcher toolkit
+// fn(F{}) for the field and unit width of a launch.
+template <class Fn>
+hipError_t with_field(int bits, bool narrow, Fn fn) {
+    if (bits == 16) return narrow ? fn(F16<2>{}) : fn(F16<4>{});
+    return narrow ? fn(F8<2>{}) : fn(F8<4>{});
+}
+// fn(std::integral_constant<int, n>{}) for n in [Lo, Hi]: the instantiations of
+// a kernel over a row count.  The launchers' argument checks refuse any other n.
+template <int Lo, int Hi, class Fn>
+hipError_t with_count(int n, Fn fn) {
+    if constexpr (Lo > Hi) return hipErrorInvalidValue;
+    else return n == Lo ? fn(std::integral_constant<int, Lo>{}) : with_count<Lo + 1, Hi>(n, fn);
+}
+// fn(std::true_type{}) or fn(std::false_type{}): a launch flag (verify, row
+// table, direction) as a template argument.
+template <class Fn>
+auto with_bool(bool b, Fn fn) {
+    return b ? fn(std::true_type{}) : fn(std::false_type{});
 }
 
 }  // namespace

@@ -16,6 +16,7 @@
 // Butterflies (reference semantics, galois_noasm.go:58-76, leopard16.go:660-772):
 //   IFFT: y ^= x; x ^= y*m        FFT: x ^= y*m; y ^= x
 //   log_m == modulus means a zero twiddle: XOR only (wave-uniform branch).
+#include <algorithm>
 #include <type_traits>
 #include <cstdlib>
 #include <utility>
@@ -314,11 +315,97 @@ __device__ __forceinline__ uint32_t vgpr_lds_addr(const uint8_t *p) {
 __device__ __forceinline__ void wait_vm0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 __device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
 
-template <bool ROWTAB>
-__device__ __forceinline__ uint8_t *rowp(const RowSet &rs, int i, uint64_t soff) {
-    if constexpr (ROWTAB) return rs.table[i];
-    else return rs.base + (uint64_t)i * rs.stride + soff;
+// Chunk geometry of the fused encodes (k_encode_reg*, k_encode_split): a wave
+// stages ROWB bytes of each of a chunk's M rows into its private LDS image by
+// 1 KiB LDS-DMA wave-instructions; behind the four images sit two table
+// buffers of TABB bytes, one read while the other is staged.
+template <int LOGM, int ROWB_, int TABB_>
+struct ChunkGeom {
+    static constexpr int M = 1 << LOGM;
+    static constexpr int ROWB = ROWB_;               // bytes of a row covered by one wave
+    static constexpr int NDMA = M * ROWB / 1024;     // DMA wave-instructions per chunk
+    static_assert(NDMA * 1024 == M * ROWB, "chunk must be whole DMA instructions");
+    static constexpr int TABB = TABB_;               // bytes per table buffer
+    static constexpr int TABS = 4 * M * ROWB;        // the table buffers' offset
+    static constexpr int LDS = TABS + 2 * TABB;
+};
+template <class F, int LOGM>
+struct RegGeom : ChunkGeom<LOGM, F::ROWB, (std::max(ifft_slot_count(LOGM), fft_slot_count(LOGM)) * F::TWD * 4 + 15) / 16 * 16> {
+    static constexpr int PPR = F::ROWB / 16;  // 16-byte pieces per row
+    static constexpr int TB = F::TWD * 4;     // bytes per twiddle table
+    static constexpr int IS = ifft_slot_count(LOGM), FS = fft_slot_count(LOGM);
+};
+
+// Stage nbytes (whole 16-byte pieces) of twiddle tables from src into table
+// buffer b of the two at ltab (tabb bytes each); the workgroup's four waves
+// split the pieces.
+__device__ __forceinline__ void stage_tab(uint8_t *ltab, int tabb, int b, const uint32_t *src, int nbytes, int wave,
+                                          int lane) {
+    const int npieces = nbytes / 16;
+    const int P = wave * 64 + lane;
+    const __amdgpu_buffer_rsrc_t trsrc = __builtin_amdgcn_make_buffer_rsrc((void *)src, 0, nbytes, 0x00020000);
+    for (int base = 0; base < npieces; base += 256) {
+        if (base + P < npieces)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(trsrc, (lvoid_t *)(ltab + b * tabb + base * 16 + wave * 1024), 16,
+                                                     (base + P) * 16, 0, 0, 0);
+    }
 }
+
+// Where a workgroup of the register encode works: the stripe's rows, the
+// workgroup's first column unit and the verify word, all wave-uniform.  Three
+// forms: a row table (data_row(i), a null descriptor), and two strided ones
+// that read data row i at i * stride() through a 32-bit buffer descriptor over
+// [desc_base, desc_base + desc_bytes).
+typedef __attribute__((address_space(4))) const EncListStripe enc_cstripe_t;
+
+// k_encode_reg: rows by pointer table (one stripe), or at a constant row stride with the stripe in grid.y
+template <bool ROWTAB_>
+struct RegStripe {
+    static constexpr bool ROWTAB = ROWTAB_;
+    const EncodeArgs &a;
+    const uint64_t soff = (uint64_t)blockIdx.y * a.stripe_stride;  // strided: the stripe's byte offset
+    __device__ uint64_t shard_size() const { return a.shard_size; }
+    __device__ uint64_t unit0() const { return (uint64_t)blockIdx.x * 256; }
+    __device__ void *desc_base() const { return ROWTAB ? nullptr : (void *)(a.data.base + soff); }
+    // Strided: right only while (k-1)*stride + shard_size < 2^32, which the host does NOT check
+    // (known defect, DESIGN.md section 4, range limits).
+    __device__ uint32_t desc_bytes() const {
+        return ROWTAB ? 0 : (uint32_t)((uint64_t)(a.k - 1) * a.data.stride + a.shard_size);
+    }
+    __device__ uint64_t stride() const { return a.data.stride; }
+    __device__ const uint8_t *data_row(int i) const { return a.data.table[i]; }
+    __device__ uint8_t *parity_row(int r) const {
+        return ROWTAB ? a.parity.table[r] : a.parity.base + (uint64_t)r * a.parity.stride + soff;
+    }
+    __device__ int *mismatch() const { return a.mismatch + (uint64_t)blockIdx.y * a.mismatch_stride; }
+};
+// k_encode_reg_list: the stripe z with first_wg[z] <= blockIdx.x < first_wg[z + 1]
+// (gf_host.hpp encode_list_find) and its descriptor.  Prefix and descriptors
+// are the same for the whole workgroup and read-only for the launch: scalar
+// loads through the constant address space (as k_decode_rows_pat reads its
+// list entry), SGPRs and no VGPRs.
+struct RegListEntry {
+    static constexpr bool ROWTAB = false;
+    const EncodeListArgs &a;
+    uint32_t z, wg0;  // the stripe, the workgroup's index within it
+    uint8_t *base;
+    uint64_t row_stride, size;
+    __device__ __forceinline__ RegListEntry(const EncodeListArgs &a_) : a(a_) {
+        cu32_t *fw = (cu32_t *)a.first_wg;
+        z = list_entry_of(fw, a.nstripes, blockIdx.x);
+        wg0 = blockIdx.x - fw[z];
+        enc_cstripe_t &d = ((enc_cstripe_t *)a.stripes)[z];
+        base = d.base, row_stride = d.row_stride, size = d.shard_size;
+    }
+    __device__ uint64_t shard_size() const { return size; }
+    __device__ uint64_t unit0() const { return (uint64_t)wg0 * 256; }
+    __device__ void *desc_base() const { return (void *)base; }
+    // (k-1)*stride + shard_size < 2^32: checked by the host (gf_host.hpp encode_list_fits)
+    __device__ uint32_t desc_bytes() const { return (uint32_t)((uint64_t)(a.k - 1) * row_stride + size); }
+    __device__ uint64_t stride() const { return row_stride; }
+    __device__ uint8_t *parity_row(int r) const { return base + (uint64_t)a.k * row_stride + (uint64_t)r * row_stride; }
+    __device__ int *mismatch() const { return a.mismatch + z; }
+};
 
 // Fused encode (leopard16.go:128-224 / leopard8.go:153-277) for m = 2^LOGM <= 32.
 // Every lane owns one column unit of all k+p rows; the m-row accumulator and
@@ -326,81 +413,69 @@ __device__ __forceinline__ uint8_t *rowp(const RowSet &rs, int i, uint64_t soff)
 // rows stream HBM -> LDS (global_load_lds_dwordx4, 16 B/lane, no VGPRs) into
 // the wave's private image, and its twiddle tables into the block's other
 // table buffer.  HBM sees exactly k row reads and p row writes (p reads for
-// verify) per unit.
-template <class F, int LOGM, bool VERIFY, bool ROWTAB>
-__global__ void __launch_bounds__(256, 2) k_encode_reg(EncodeArgs a) {
-    constexpr int M = 1 << LOGM;
-    constexpr int ROWB = F::ROWB;          // bytes of a row covered by one wave
-    constexpr int PPR = ROWB / 16;         // 16-byte pieces per row
-    constexpr int NDMA = M * PPR / 64;     // DMA wave-instructions per chunk
-    static_assert(NDMA * 64 == M * PPR, "chunk must be whole DMA instructions");
-    constexpr int IS = ifft_slot_count(LOGM), FS = fft_slot_count(LOGM);
-    constexpr int TB = F::TWD * 4;                      // bytes per twiddle table
-    constexpr int TABB = ((IS > FS ? IS : FS) * TB + 15) / 16 * 16;  // bytes per table buffer
+// verify) per unit.  The one body of k_encode_reg and k_encode_reg_list: `a`
+// is either's arguments, `wh` says where the workgroup works.  A workgroup
+// never straddles two stripes: the waves of a stripe's last workgroup past
+// the row end are dead and still join the barriers.
+template <class F, int LOGM, bool VERIFY, class A, class WH>
+__device__ __forceinline__ void encode_reg_body(const A &a, const WH &wh) {
+    typedef RegGeom<F, LOGM> G;
+    constexpr int M = G::M, ROWB = G::ROWB, PPR = G::PPR, NDMA = G::NDMA, IS = G::IS, FS = G::FS, TB = G::TB, TABB = G::TABB;
     typedef typename F::Vec V;
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    __shared__ __attribute__((aligned(16))) uint8_t lds[4 * M * ROWB + 2 * TABB];
-    uint8_t *ltab = lds + 4 * M * ROWB;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[G::LDS];
+    uint8_t *ltab = lds + G::TABS;
 
+    const uint64_t stride = wh.stride(), shard_size = wh.shard_size();
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform (SGPR)
-    const uint64_t units = F::units(a.shard_size);
-    const uint64_t u0 = (uint64_t)blockIdx.x * 256 + wave * 64;
+    const uint64_t units = F::units(shard_size);
+    const uint64_t u0 = wh.unit0() + wave * 64;
     const bool wave_live = u0 < units;  // waves past the row end still join the barriers
     const uint64_t u = u0 + lane;
-    const uint64_t soff = (uint64_t)blockIdx.y * a.stripe_stride;
     const uint64_t span = F::span_off(u0);
     uint8_t *img = lds + wave * (M * ROWB);
 
-    // Stage chunk c's rows: rows past the chunk's count and pieces past the
-    // row end are zero-filled.
-    // Buffer descriptor over this stripe's data rows (strided mode): right only while (k-1)*stride +
-    // shard_size < 2^32, which the host does NOT check (known defect, DESIGN.md section 4, range limits).
-    const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(
-        ROWTAB ? nullptr : (void *)(a.data.base + soff), 0,
-        ROWTAB ? 0 : (int)(uint32_t)((uint64_t)(a.k - 1) * a.data.stride + a.shard_size), 0x00020000);
-    // One DMA wave-instruction (piece group j) of chunk c's rows.
-    auto stage_one = [&](int c, int j) {
+    // Buffer descriptor over this stripe's data rows (strided forms): 32-bit offsets, so right
+    // only while the data span stays below 2^32 (see desc_bytes of the two forms).
+    const __amdgpu_buffer_rsrc_t drsrc =
+        __builtin_amdgcn_make_buffer_rsrc(wh.desc_base(), 0, (int)wh.desc_bytes(), 0x00020000);
+    // One DMA wave-instruction (piece group j) of chunk c's rows: rows past the
+    // chunk's count and pieces past the row end are zero-filled.  The staging
+    // lambdas are always inlined: left to the inliner, the list form of F16<4>
+    // at m = 8 kept stage_one as a call, with its captures and the arguments in
+    // scratch.
+    auto stage_one = [&](int c, int j) __attribute__((always_inline)) {
         const int row0 = c * M, cnt = a.k - row0;
-        {
-            const int P = j * 64 + lane;
-            const int r = P / PPR;
-            const uint64_t go = span + F::piece_goff(P % PPR);
-            if (wave_live && r < cnt && go < a.shard_size) {
-                if constexpr (ROWTAB) {
-                    const uint8_t *src = rowp<ROWTAB>(a.data, row0 + r, soff) + go;
-                    __builtin_amdgcn_global_load_lds((gvoid_t *)src, (lvoid_t *)(img + j * 1024), 16, 0, 0);
-                } else {
-                    // MUBUF LDS-DMA: with a FLAT global_load_lds in flight the compiler's
-                    // waitcnt model turns every LDS table wait into lgkmcnt(0).
-                    const uint32_t voff = (uint32_t)((uint64_t)(row0 + r) * a.data.stride + go);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(drsrc, (lvoid_t *)(img + j * 1024), 16, voff, 0, 0, 0);
-                }
+        const int P = j * 64 + lane;
+        const int r = P / PPR;
+        const uint64_t go = span + F::piece_goff(P % PPR);
+        if (wave_live && r < cnt && go < shard_size) {
+            if constexpr (WH::ROWTAB) {
+                const uint8_t *src = wh.data_row(row0 + r) + go;
+                __builtin_amdgcn_global_load_lds((gvoid_t *)src, (lvoid_t *)(img + j * 1024), 16, 0, 0);
             } else {
-                *(__attribute__((address_space(3))) u32x4 *)(img + j * 1024 + lane * 16) = u32x4{0, 0, 0, 0};
+                // MUBUF LDS-DMA: with a FLAT global_load_lds in flight the compiler's
+                // waitcnt model turns every LDS table wait into lgkmcnt(0).
+                const uint32_t voff = (uint32_t)((uint64_t)(row0 + r) * stride + go);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(drsrc, (lvoid_t *)(img + j * 1024), 16, voff, 0, 0, 0);
             }
+        } else {
+            *(__attribute__((address_space(3))) u32x4 *)(img + j * 1024 + lane * 16) = u32x4{0, 0, 0, 0};
         }
     };
-    auto stage = [&](int c) {
+    auto stage = [&](int c) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < NDMA; j++) stage_one(c, j);
     };
-
-    // Stage `nslot` twiddle tables into table buffer b (waves split the pieces).
-    auto stage_tab = [&](const uint32_t *src, int nslot, int b) {
-        const int npieces = nslot * TB / 16;
-        const int P = wave * 64 + lane;
-        const __amdgpu_buffer_rsrc_t trsrc = __builtin_amdgcn_make_buffer_rsrc((void *)src, 0, npieces * 16, 0x00020000);
-        for (int base = 0; base < npieces; base += 256) {
-            if (base + P < npieces)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(trsrc, (lvoid_t *)(ltab + b * TABB + base * 16 + wave * 1024),
-                                                         16, (base + P) * 16, 0, 0, 0);
-        }
+    // `nslot` twiddle tables into table buffer b
+    auto stage_tabs = [&](const uint32_t *src, int nslot, int b) __attribute__((always_inline)) {
+        stage_tab(ltab, TABB, b, src, nslot * TB, wave, lane);
     };
 
     V acc[M];
     stage(0);
-    stage_tab(a.tw_ifft, IS, 0);
+    stage_tabs(a.tw_ifft, IS, 0);
     for (int c = 0; c < a.nchunks; ++c) {
         wait_vm0();  // this wave's DMAs for chunk c have landed
         __syncthreads();  // every wave's table pieces landed; buffer (c+1)&1 is no longer read
@@ -409,8 +484,8 @@ __global__ void __launch_bounds__(256, 2) k_encode_reg(EncodeArgs a) {
         for (int r = 0; r < M; r++) cur[r] = F::lds_load(img + r * ROWB, lane);
         wait_lgkm0();  // reads done before the image is overwritten
         const bool more = c + 1 < a.nchunks;
-        if (more) stage_tab(a.tw_ifft + (uint64_t)(c + 1) * IS * F::TWD, IS, (c + 1) & 1);
-        else stage_tab(a.tw_fft, FS, (c + 1) & 1);
+        if (more) stage_tabs(a.tw_ifft + (uint64_t)(c + 1) * IS * F::TWD, IS, (c + 1) & 1);
+        else stage_tabs(a.tw_fft, FS, (c + 1) & 1);
         // The next chunk's row DMAs are issued spread through the IFFT (one
         // every SPREAD ops): issued back to back while the whole GPU streams,
         // they stall the wave at issue before any butterfly starts.
@@ -436,151 +511,49 @@ __global__ void __launch_bounds__(256, 2) k_encode_reg(EncodeArgs a) {
         uint32_t bad = 0;
 #pragma unroll
         for (int r = 0; r < M; r++)
-            if (r < a.p) bad |= F::diff(acc[r], F::load(rowp<ROWTAB>(a.parity, r, soff), u));
-        flag_mismatch(a.mismatch + (uint64_t)blockIdx.y * a.mismatch_stride, bad != 0);
+            if (r < a.p) bad |= F::diff(acc[r], F::load(wh.parity_row(r), u));
+        flag_mismatch(wh.mismatch(), bad != 0);
     } else {
 #pragma unroll
         for (int r = 0; r < M; r++)
-            if (r < a.p) F::store(rowp<ROWTAB>(a.parity, r, soff), u, acc[r]);
+            if (r < a.p) F::store(wh.parity_row(r), u, acc[r]);
     }
 }
 
-// ---------------------------------------------------------------- register encode over a list of stripes
-// k_encode_reg's strided form over stripes of different sizes, each in a
-// buffer of its own (kernels.hpp EncodeListArgs, rs_encode_dev_list).  A copy:
-// k_encode_reg and its instantiations keep their registers.  The grid is
-// one-dimensional over the column blocks of all stripes; a workgroup finds its
-// stripe by a binary search over the prefix first_wg and reads the stripe's
-// descriptor.  Prefix and descriptors are the same for the whole workgroup and
-// read-only for the launch: scalar loads through the constant address space
-// (as k_decode_rows_pat reads its list entry), SGPRs and no VGPRs.  A
-// workgroup never straddles two stripes: the waves of a stripe's last
-// workgroup past the row end are dead and still join the barriers.  The data
-// rows go through a 32-bit buffer descriptor over the stripe's data span,
+template <class F, int LOGM, bool VERIFY, bool ROWTAB>
+__global__ void __launch_bounds__(256, 2) k_encode_reg(EncodeArgs a) {
+    encode_reg_body<F, LOGM, VERIFY>(a, RegStripe<ROWTAB>{a});
+}
+
+// The strided form over a list of stripes of different sizes, each in a buffer
+// of its own (kernels.hpp EncodeListArgs, rs_encode_dev_list).  The grid is
+// one-dimensional over the column blocks of all stripes (RegListEntry).  The
+// data rows go through a 32-bit buffer descriptor over the stripe's data span,
 // which the host keeps below 2^32 (gf_host.hpp encode_list_fits); the parity
 // rows through 64-bit pointers.
-typedef __attribute__((address_space(4))) const EncListStripe enc_cstripe_t;
-
 template <class F, int LOGM, bool VERIFY>
 __global__ void __launch_bounds__(256, 2) k_encode_reg_list(EncodeListArgs a) {
-    constexpr int M = 1 << LOGM;
-    constexpr int ROWB = F::ROWB;          // bytes of a row covered by one wave
-    constexpr int PPR = ROWB / 16;         // 16-byte pieces per row
-    constexpr int NDMA = M * PPR / 64;     // DMA wave-instructions per chunk
-    static_assert(NDMA * 64 == M * PPR, "chunk must be whole DMA instructions");
-    constexpr int IS = ifft_slot_count(LOGM), FS = fft_slot_count(LOGM);
-    constexpr int TB = F::TWD * 4;                      // bytes per twiddle table
-    constexpr int TABB = ((IS > FS ? IS : FS) * TB + 15) / 16 * 16;  // bytes per table buffer
-    typedef typename F::Vec V;
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    __shared__ __attribute__((aligned(16))) uint8_t lds[4 * M * ROWB + 2 * TABB];
-    uint8_t *ltab = lds + 4 * M * ROWB;
-
-    // the stripe z with first_wg[z] <= blockIdx.x < first_wg[z + 1] (gf_host.hpp encode_list_find)
-    cu32_t *fw = (cu32_t *)a.first_wg;
-    const uint32_t wg = blockIdx.x;
-    const uint32_t z = list_entry_of(fw, a.nstripes, wg);
-    enc_cstripe_t &d = ((enc_cstripe_t *)a.stripes)[z];
-    uint8_t *const sbase = d.base;
-    const uint64_t stride = d.row_stride, shard_size = d.shard_size;
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform (SGPR)
-    const uint64_t units = F::units(shard_size);
-    const uint64_t u0 = (uint64_t)(wg - fw[z]) * 256 + wave * 64;
-    const bool wave_live = u0 < units;  // waves past the row end still join the barriers
-    const uint64_t u = u0 + lane;
-    const uint64_t span = F::span_off(u0);
-    uint8_t *img = lds + wave * (M * ROWB);
-
-    // Buffer descriptor over this stripe's data rows: (k-1)*stride + shard_size < 2^32 (checked by the host).
-    const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)sbase, 0, (int)(uint32_t)((uint64_t)(a.k - 1) * stride + shard_size), 0x00020000);
-    // One DMA wave-instruction (piece group j) of chunk c's rows: rows past the
-    // chunk's count and pieces past the row end are zero-filled.  The staging
-    // lambdas are always inlined: left to the inliner, F16<4> at m = 8 kept
-    // stage_one as a call, with its captures and the arguments in scratch.
-    auto stage_one = [&](int c, int j) __attribute__((always_inline)) {
-        const int row0 = c * M, cnt = a.k - row0;
-        const int P = j * 64 + lane;
-        const int r = P / PPR;
-        const uint64_t go = span + F::piece_goff(P % PPR);
-        if (wave_live && r < cnt && go < shard_size) {
-            const uint32_t voff = (uint32_t)((uint64_t)(row0 + r) * stride + go);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(drsrc, (lvoid_t *)(img + j * 1024), 16, voff, 0, 0, 0);
-        } else {
-            *(__attribute__((address_space(3))) u32x4 *)(img + j * 1024 + lane * 16) = u32x4{0, 0, 0, 0};
-        }
-    };
-    auto stage = [&](int c) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < NDMA; j++) stage_one(c, j);
-    };
-
-    // Stage `nslot` twiddle tables into table buffer b (waves split the pieces).
-    auto stage_tab = [&](const uint32_t *src, int nslot, int b) __attribute__((always_inline)) {
-        const int npieces = nslot * TB / 16;
-        const int P = wave * 64 + lane;
-        const __amdgpu_buffer_rsrc_t trsrc = __builtin_amdgcn_make_buffer_rsrc((void *)src, 0, npieces * 16, 0x00020000);
-        for (int base = 0; base < npieces; base += 256) {
-            if (base + P < npieces)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(trsrc, (lvoid_t *)(ltab + b * TABB + base * 16 + wave * 1024),
-                                                         16, (base + P) * 16, 0, 0, 0);
-        }
-    };
-
-    V acc[M];
-    stage(0);
-    stage_tab(a.tw_ifft, IS, 0);
-    for (int c = 0; c < a.nchunks; ++c) {
-        wait_vm0();  // this wave's DMAs for chunk c have landed
-        __syncthreads();  // every wave's table pieces landed; buffer (c+1)&1 is no longer read
-        V cur[M];
-#pragma unroll
-        for (int r = 0; r < M; r++) cur[r] = F::lds_load(img + r * ROWB, lane);
-        wait_lgkm0();  // reads done before the image is overwritten
-        const bool more = c + 1 < a.nchunks;
-        if (more) stage_tab(a.tw_ifft + (uint64_t)(c + 1) * IS * F::TWD, IS, (c + 1) & 1);
-        else stage_tab(a.tw_fft, FS, (c + 1) & 1);
-        // the next chunk's row DMAs spread through the IFFT, as in k_encode_reg
-        constexpr int NOPS = ifft_op_count<LOGM>();
-        constexpr int SPREAD = NOPS >= NDMA ? NOPS / NDMA : 0;
-        if (!SPREAD && more) stage(c + 1);
-        ifft_reg<F, LOGM>(cur, vgpr_lds_addr(ltab + (c & 1) * TABB), [&](int i) {
-            if (SPREAD && i % SPREAD == 0 && i / SPREAD < NDMA && more) stage_one(c + 1, i / SPREAD);
-        });
-        if (c == 0) {
-#pragma unroll
-            for (int r = 0; r < M; r++) acc[r] = cur[r];
-        } else {
-#pragma unroll
-            for (int r = 0; r < M; r++) F::xor_into(acc[r], cur[r]);
-        }
-    }
-    wait_vm0();
-    __syncthreads();
-    fft_reg<F, LOGM>(acc, vgpr_lds_addr(ltab + (a.nchunks & 1) * TABB));
-    if (!wave_live || u >= units) return;
-    uint8_t *const par = sbase + (uint64_t)a.k * stride;
-    if constexpr (VERIFY) {
-        uint32_t bad = 0;
-#pragma unroll
-        for (int r = 0; r < M; r++)
-            if (r < a.p) bad |= F::diff(acc[r], F::load(par + (uint64_t)r * stride, u));
-        flag_mismatch(a.mismatch + z, bad != 0);
-    } else {
-#pragma unroll
-        for (int r = 0; r < M; r++)
-            if (r < a.p) F::store(par + (uint64_t)r * stride, u, acc[r]);
-    }
+    encode_reg_body<F, LOGM, VERIFY>(a, RegListEntry{a});
 }
 
+template <class F, int LOGM>
+hipError_t enc_reg(bool verify, const EncodeArgs &a, hipStream_t s) {
+    const dim3 grid(grid_x(F::units(a.shard_size)).x, (unsigned)a.nstripes);
+    const bool table = a.data.table != nullptr || a.parity.table != nullptr;
+    with_bool(verify, [&](auto v) {
+        with_bool(table, [&](auto t) {
+            hipLaunchKernelGGL((k_encode_reg<F, LOGM, decltype(v)::value, decltype(t)::value>), grid, dim3(256), 0, s, a);
+        });
+    });
+    return hipGetLastError();
+}
 template <class F, int LOGM>
 hipError_t enc_reg_list(bool verify, const EncodeListArgs &a, hipStream_t s) {
     constexpr uint32_t kWg = 256 * (F::SYM16 ? 8 : 4) * F::W;  // bytes of a row per workgroup
     if (a.wg_bytes != kWg) return hipErrorInvalidValue;
-    if (verify) hipLaunchKernelGGL((k_encode_reg_list<F, LOGM, true>), dim3(a.nwg), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_encode_reg_list<F, LOGM, false>), dim3(a.nwg), dim3(256), 0, s, a);
+    with_bool(verify, [&](auto v) {
+        hipLaunchKernelGGL((k_encode_reg_list<F, LOGM, decltype(v)::value>), dim3(a.nwg), dim3(256), 0, s, a);
+    });
     return hipGetLastError();
 }
 
@@ -658,16 +631,13 @@ __device__ __forceinline__ void run_split(F16<1>::Vec *w, uint32_t ltab) {
     }
 }
 
+// A wave covers 256 bytes of a row (32 units x 8 B); a table buffer holds both halves' tables.
 template <int LOGM>
-struct SplitGeom {
+struct SplitGeom : ChunkGeom<LOGM, 256, 2 * std::max(EncodeSplit<LOGM>::ifft.ntab, EncodeSplit<LOGM>::fft.ntab) * F16<1>::TWD * 4> {
     typedef EncodeSplit<LOGM> ES;
-    static constexpr int M = 1 << LOGM, HM = M / 2;
-    static constexpr int ROWB = 256;                 // bytes of a row per wave (32 units x 8 B)
-    static constexpr int NDMA = M * ROWB / 1024;     // LDS-DMA wave-instructions per chunk
+    static constexpr int HM = (1 << LOGM) / 2;
     static constexpr int TB = F16<1>::TWD * 4;
     static constexpr int NTI = ES::ifft.ntab, NTF = ES::fft.ntab;
-    static constexpr int TABB = 2 * (NTI > NTF ? NTI : NTF) * TB;  // one table buffer
-    static constexpr int LDS = 4 * M * ROWB + 2 * TABB;
 };
 
 template <int LOGM, bool VERIFY>
@@ -683,7 +653,7 @@ __global__ void __launch_bounds__(256, 4) k_encode_split(EncodeArgs a) {
     constexpr int H0 = SI.h0, HF = SF.hend;
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) uint8_t lds[G::LDS];
-    uint8_t *ltab = lds + 4 * M * ROWB;
+    uint8_t *ltab = lds + G::TABS;
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -721,21 +691,13 @@ __global__ void __launch_bounds__(256, 4) k_encode_split(EncodeArgs a) {
             *(__attribute__((address_space(3))) u32x4 *)(img + j * 1024 + lane * 16) = u32x4{0, 0, 0, 0};
         }
     };
-    auto stage_tab = [&](const uint32_t *src, int nbytes, int b) {
-        const int npieces = nbytes / 16;
-        const int P = wave * 64 + lane;
-        const __amdgpu_buffer_rsrc_t trsrc = __builtin_amdgcn_make_buffer_rsrc((void *)src, 0, nbytes, 0x00020000);
-        for (int base = 0; base < npieces; base += 256)
-            if (base + P < npieces)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(trsrc, (lvoid_t *)(ltab + b * TABB + base * 16 + wave * 1024),
-                                                         16, (base + P) * 16, 0, 0, 0);
-    };
+    auto stage_tabs = [&](const uint32_t *src, int nbytes, int b) { stage_tab(ltab, TABB, b, src, nbytes, wave, lane); };
     constexpr int IMGB = 2 * NTI * TB, FMGB = 2 * NTF * TB;  // bytes of one chunk's / the FFT's table image
 
     V acc[HM];
 #pragma unroll
     for (int j = 0; j < NDMA; j++) stage_one(0, j);
-    stage_tab(a.tw_ifft, IMGB, 0);
+    stage_tabs(a.tw_ifft, IMGB, 0);
     // lane's LDS read base: register k holds row row0[k] (lower) / row0[k] | 1 << H0 (upper)
     const uint8_t *rd = img + half * ((1 << H0) * ROWB) + colb;
     for (int c = 0; c < a.nchunks; ++c) {
@@ -750,8 +712,8 @@ __global__ void __launch_bounds__(256, 4) k_encode_split(EncodeArgs a) {
         }
         wait_lgkm0();  // reads done before the image is overwritten
         const bool more = c + 1 < a.nchunks;
-        if (more) stage_tab(a.tw_ifft + (uint64_t)(c + 1) * (IMGB / 4), IMGB, (c + 1) & 1);
-        else stage_tab(a.tw_fft, FMGB, (c + 1) & 1);
+        if (more) stage_tabs(a.tw_ifft + (uint64_t)(c + 1) * (IMGB / 4), IMGB, (c + 1) & 1);
+        else stage_tabs(a.tw_fft, FMGB, (c + 1) & 1);
         if (more) {
 #pragma unroll
             for (int j = 0; j < NDMA; j++) stage_one(c + 1, j);
@@ -915,23 +877,6 @@ __global__ void __launch_bounds__(256) k_reveal(uint8_t *const *dst, const uint8
     typename F::Vec v = F::zero();
     F::mul_add(v, F::load(work + (uint64_t)pos[i] * S, u), tw + (uint64_t)i * F::TWD);
     F::store(dst[i], u, v);
-}
-
-template <class F, int LOGM>
-hipError_t enc_reg(bool verify, const EncodeArgs &a, hipStream_t s) {
-    uint64_t nunits;
-    if constexpr (F::SYM16) nunits = (a.shard_size >> 6) * (8 / F::W);
-    else nunits = a.shard_size / (4 * F::W);
-    dim3 grid((unsigned)((nunits + 255) / 256), (unsigned)a.nstripes);
-    const bool table = a.data.table != nullptr || a.parity.table != nullptr;
-    if (table) {
-        if (verify) hipLaunchKernelGGL((k_encode_reg<F, LOGM, true, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_encode_reg<F, LOGM, false, true>), grid, dim3(256), 0, s, a);
-    } else {
-        if (verify) hipLaunchKernelGGL((k_encode_reg<F, LOGM, true, false>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_encode_reg<F, LOGM, false, false>), grid, dim3(256), 0, s, a);
-    }
-    return hipGetLastError();
 }
 
 
@@ -1734,29 +1679,13 @@ hipError_t rec_lds_t(const A &a, hipStream_t s) {
 }
 template <class F, class FT = F, class A>
 hipError_t rec_lds_f(int logn, const A &a, hipStream_t s) {
-    switch (logn) {
-        case 1: return rec_lds_t<F, FT, 1>(a, s);
-        case 2: return rec_lds_t<F, FT, 2>(a, s);
-        case 3: return rec_lds_t<F, FT, 3>(a, s);
-        case 4: return rec_lds_t<F, FT, 4>(a, s);
-        case 5: return rec_lds_t<F, FT, 5>(a, s);
-        case 6: return rec_lds_t<F, FT, 6>(a, s);
-        case 7: return rec_lds_t<F, FT, 7>(a, s);
-        case 8: return rec_lds_t<F, FT, 8>(a, s);
-    }
+    // n = 2 .. 256: every field and tile width.  Full-field F16<2> only:
     // n = 512 .. 2048: GF(2^16), 64-byte tiles (the packed n x 64-byte image
     // takes 128 KB at n = 2048); n = 4096: 32-byte half tiles (128 KB);
     // n = 8192: 16-byte quarter tiles (128 KB)
-    if constexpr (std::is_same<F, F16<2>>::value && std::is_same<FT, F>::value) {
-        switch (logn) {
-            case 9: return rec_lds_t<F, FT, 9>(a, s);
-            case 10: return rec_lds_t<F, FT, 10>(a, s);
-            case 11: return rec_lds_t<F, FT, 11>(a, s);
-            case 12: return rec_lds_t<F, FT, 12>(a, s);
-            case 13: return rec_lds_t<F, FT, 13>(a, s);
-        }
-    }
-    return hipErrorInvalidValue;
+    constexpr int kHi = std::is_same<F, F16<2>>::value && std::is_same<FT, F>::value ? 13 : 8;
+    static_assert(kMaxLdsRecLogN16 == 13, "with_count's bound: k_rec_lds is built up to n = 8192");
+    return with_count<1, kHi>(logn, [&](auto ln) { return rec_lds_t<F, FT, decltype(ln)::value>(a, s); });
 }
 
 template <class F, int LOGM, class FT>
@@ -1772,13 +1701,11 @@ hipError_t enc_lds_tt(bool verify, const EncodeArgs &a, hipStream_t s) {
     const bool isub = !std::is_same<F, FT>::value && a.tw_ifft_sub && a.ifft_nff;
     if constexpr (!std::is_same<F, FT>::value) {
         if (isub) {
-            if (verify) go(std::true_type{}, std::true_type{});
-            else go(std::false_type{}, std::true_type{});
+            with_bool(verify, [&](auto v) { go(v, std::true_type{}); });
             return hipGetLastError();
         }
     }
-    if (verify) go(std::true_type{}, std::false_type{});
-    else go(std::false_type{}, std::false_type{});
+    with_bool(verify, [&](auto v) { go(v, std::false_type{}); });
     return hipGetLastError();
 }
 template <class F>
@@ -1798,106 +1725,74 @@ hipError_t enc_lds_t(bool verify, const EncodeArgs &a, hipStream_t s) {
 }
 template <class F>
 hipError_t enc_lds_f(int logm, bool verify, const EncodeArgs &a, hipStream_t s) {
-    switch (logm) {
-        case 2: return enc_lds_t<F, 2>(verify, a, s);
-        case 3: return enc_lds_t<F, 3>(verify, a, s);
-        case 4: return enc_lds_t<F, 4>(verify, a, s);
-        case 5: return enc_lds_t<F, 5>(verify, a, s);
-        case 6: return enc_lds_t<F, 6>(verify, a, s);
-        case 7: return enc_lds_t<F, 7>(verify, a, s);
-        case 8: return enc_lds_t<F, 8>(verify, a, s);
-    }
-    if constexpr (std::is_same<F, F16<2>>::value) {  // m = 512, 1024: 64-byte tiles; 2048: half, 4096: quarter tiles
-        switch (logm) {
-            case 9: return enc_lds_t<F, 9>(verify, a, s);
-            case 10: return enc_lds_t<F, 10>(verify, a, s);
-            case 11: return enc_lds_t<F, 11>(verify, a, s);
-            case 12: return enc_lds_t<F, 12>(verify, a, s);
-        }
-    }
-    return hipErrorInvalidValue;
+    // m = 4 .. 256; F16<2> only: m = 512, 1024: 64-byte tiles; 2048: half, 4096: quarter tiles
+    constexpr int kHi = std::is_same<F, F16<2>>::value ? 12 : 8;
+    static_assert(kMaxLdsEncLogM16 == 12, "with_count's bound: k_enc_lds is built up to m = 4096");
+    return with_count<2, kHi>(logm, [&](auto lm) { return enc_lds_t<F, decltype(lm)::value>(verify, a, s); });
+}
+
+// The register encode's lane width per (field, log2 m): keep acc + work +
+// prefetch <= ~192 VGPRs (2 waves/SIMD) while using the widest coalesced
+// access that fits.  narrow: GF(2^8) at m = 4..16 in 4-byte units.
+constexpr int reg_unit_w(int bits, int logm, bool narrow) {
+    if (bits == 16) return logm <= 3 ? 4 : logm == 4 ? 2 : 1;
+    return logm == 5 ? 2 : narrow && logm >= 2 ? 1 : 4;
+}
+// fn(F{}, std::integral_constant<int, logm>{}) for a register encode; logm in [0, 5]
+template <class Fn>
+hipError_t with_reg_unit(int bits, int logm, bool narrow, Fn fn) {
+    return with_count<0, 5>(logm, [&](auto lm) {
+        constexpr int L = decltype(lm)::value;
+        if (bits == 16) return fn(F16<reg_unit_w(16, L, false)>{}, lm);
+        return narrow ? fn(F8<reg_unit_w(8, L, true)>{}, lm) : fn(F8<reg_unit_w(8, L, false)>{}, lm);
+    });
+}
+// fn(F{}, grid) for the multi-pass kernels' unit and their grid over ny rows
+// of S bytes: 8-byte GF(2^16) units, 16-byte GF(2^8) ones.
+template <class Fn>
+void with_pass_unit(int bits, uint64_t S, int ny, Fn fn) {
+    if (bits == 16) fn(F16<1>{}, dim3(grid_x((S >> 6) * 8).x, ny));
+    else fn(F8<4>{}, dim3(grid_x(S / 16).x, ny));
 }
 
 }  // namespace
 
-// Lane width per (field, log2 m): keep acc + work + prefetch <= ~192 VGPRs
-// (2 waves/SIMD) while using the widest coalesced access that fits.
 template <int LOGM>
 hipError_t launch_split_t(bool verify, const EncodeArgs &a, hipStream_t s) {
     const uint64_t units = a.shard_size >> 3;
-    dim3 grid((unsigned)((units + 127) / 128), (unsigned)a.nstripes);
-    if (verify) hipLaunchKernelGGL((k_encode_split<LOGM, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_encode_split<LOGM, false>), grid, dim3(256), 0, s, a);
+    const dim3 grid((unsigned)((units + 127) / 128), (unsigned)a.nstripes);
+    with_bool(verify, [&](auto v) {
+        hipLaunchKernelGGL((k_encode_split<LOGM, decltype(v)::value>), grid, dim3(256), 0, s, a);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_encode_reg(int bits, int logm, bool verify, const EncodeArgs &a, hipStream_t s) {
-    if (bits == 16) {
-        switch (logm) {
-            case 0: return enc_reg<F16<4>, 0>(verify, a, s);
-            case 1: return enc_reg<F16<4>, 1>(verify, a, s);
-            case 2: return enc_reg<F16<4>, 2>(verify, a, s);
-            case 3: return enc_reg<F16<4>, 3>(verify, a, s);
-            case 4: return enc_reg<F16<2>, 4>(verify, a, s);
-            case 5: return enc_reg<F16<1>, 5>(verify, a, s);
-        }
-    } else {
-        // Small GF(2^8) stripes (C2: 10+4 x 1 MiB is 256 workgroups of 16-byte
-        // units, one per CU, latency-bound): 4-byte units give 4x the
-        // workgroups and 4x the loads in flight per CU.
+    // Small GF(2^8) stripes (C2: 10+4 x 1 MiB is 256 workgroups of 16-byte
+    // units, one per CU, latency-bound): 4-byte units give 4x the
+    // workgroups and 4x the loads in flight per CU.
 #ifndef RS_F8_NARROW
 #define RS_F8_NARROW 1
 #endif
-        const bool narrow = pick_narrow(RS_F8_NARROW && (a.shard_size / 16 + 255) / 256 * (uint64_t)a.nstripes < 1024);
-        switch (logm) {
-            case 0: return enc_reg<F8<4>, 0>(verify, a, s);
-            case 1: return enc_reg<F8<4>, 1>(verify, a, s);
-            case 2: return narrow ? enc_reg<F8<1>, 2>(verify, a, s) : enc_reg<F8<4>, 2>(verify, a, s);
-            case 3: return narrow ? enc_reg<F8<1>, 3>(verify, a, s) : enc_reg<F8<4>, 3>(verify, a, s);
-            case 4: return narrow ? enc_reg<F8<1>, 4>(verify, a, s) : enc_reg<F8<4>, 4>(verify, a, s);
-            case 5: return enc_reg<F8<2>, 5>(verify, a, s);
-        }
-    }
-    return hipErrorInvalidValue;
+    const bool narrow =
+        bits != 16 && pick_narrow(RS_F8_NARROW && (a.shard_size / 16 + 255) / 256 * (uint64_t)a.nstripes < 1024);
+    return with_reg_unit(bits, logm, narrow, [&](auto f, auto lm) {
+        return enc_reg<decltype(f), decltype(lm)::value>(verify, a, s);
+    });
 }
 
-// launch_encode_reg's (field, log2 m) table; the unit width comes with the
-// launch (gf_host.hpp make_encode_list_plan applies pick_narrow's rule to the
-// launch's total workgroup count).
+// The unit width comes with the launch (gf_host.hpp make_encode_list_plan
+// applies pick_narrow's rule to the launch's total workgroup count).
 hipError_t launch_encode_reg_list(int bits, int logm, bool verify, const EncodeListArgs &a, hipStream_t s) {
     if (!a.stripes || !a.first_wg || !a.nstripes || !a.nwg || a.nwg > 0x7fffffffu) return hipErrorInvalidValue;
     if (verify && !a.mismatch) return hipErrorInvalidValue;
-    if (bits == 16) {
-        switch (logm) {
-            case 0: return enc_reg_list<F16<4>, 0>(verify, a, s);
-            case 1: return enc_reg_list<F16<4>, 1>(verify, a, s);
-            case 2: return enc_reg_list<F16<4>, 2>(verify, a, s);
-            case 3: return enc_reg_list<F16<4>, 3>(verify, a, s);
-            case 4: return enc_reg_list<F16<2>, 4>(verify, a, s);
-            case 5: return enc_reg_list<F16<1>, 5>(verify, a, s);
-        }
-    } else {
-        const bool narrow = a.wg_bytes == 1024;
-        switch (logm) {
-            case 0: return enc_reg_list<F8<4>, 0>(verify, a, s);
-            case 1: return enc_reg_list<F8<4>, 1>(verify, a, s);
-            case 2: return narrow ? enc_reg_list<F8<1>, 2>(verify, a, s) : enc_reg_list<F8<4>, 2>(verify, a, s);
-            case 3: return narrow ? enc_reg_list<F8<1>, 3>(verify, a, s) : enc_reg_list<F8<4>, 3>(verify, a, s);
-            case 4: return narrow ? enc_reg_list<F8<1>, 4>(verify, a, s) : enc_reg_list<F8<4>, 4>(verify, a, s);
-            case 5: return enc_reg_list<F8<2>, 5>(verify, a, s);
-        }
-    }
-    return hipErrorInvalidValue;
+    return with_reg_unit(bits, logm, a.wg_bytes == 1024, [&](auto f, auto lm) {
+        return enc_reg_list<decltype(f), decltype(lm)::value>(verify, a, s);
+    });
 }
 
 hipError_t launch_encode_split(int logm, bool verify, const EncodeArgs &a, hipStream_t s) {
-    switch (logm) {
-        case 2: return launch_split_t<2>(verify, a, s);
-        case 3: return launch_split_t<3>(verify, a, s);
-        case 4: return launch_split_t<4>(verify, a, s);
-        case 5: return launch_split_t<5>(verify, a, s);
-    }
-    return hipErrorInvalidValue;
+    return with_count<2, 5>(logm, [&](auto lm) { return launch_split_t<decltype(lm)::value>(verify, a, s); });
 }
 
 const char *encode_reg_name(int bits, int logm) {
@@ -1917,31 +1812,16 @@ hipError_t launch_gather(int bits, uint8_t *work, uint64_t S, RowSet src, int ro
 hipError_t launch_pass(int bits, bool inverse, uint8_t *work, uint64_t S, int dist, int radix, int groups_active,
                        const uint32_t *tw, hipStream_t s) {
     if (groups_active <= 0) return hipSuccess;
-    if (radix == 4) {
-        const int quads = groups_active * dist;
-        return for_y(quads, [&](int y0, int ny) {
-            if (bits == 16) {
-                dim3 g(grid_x((S >> 6) * 8).x, ny);
-                if (inverse) hipLaunchKernelGGL((k_pass4<F16<1>, true>), g, dim3(256), 0, s, work, S, dist, tw, y0);
-                else hipLaunchKernelGGL((k_pass4<F16<1>, false>), g, dim3(256), 0, s, work, S, dist, tw, y0);
-            } else {
-                dim3 g(grid_x(S / 16).x, ny);
-                if (inverse) hipLaunchKernelGGL((k_pass4<F8<4>, true>), g, dim3(256), 0, s, work, S, dist, tw, y0);
-                else hipLaunchKernelGGL((k_pass4<F8<4>, false>), g, dim3(256), 0, s, work, S, dist, tw, y0);
-            }
+    const int quads = groups_active * dist, pairs = inverse ? dist : groups_active;
+    return for_y(radix == 4 ? quads : pairs, [&](int y0, int ny) {
+        with_pass_unit(bits, S, ny, [&](auto f, dim3 g) {
+            with_bool(inverse, [&](auto inv) {
+                typedef decltype(f) F;
+                constexpr bool INV = decltype(inv)::value;
+                if (radix == 4) hipLaunchKernelGGL((k_pass4<F, INV>), g, dim3(256), 0, s, work, S, dist, tw, y0);
+                else hipLaunchKernelGGL((k_pass2<F, INV>), g, dim3(256), 0, s, work, S, dist, tw, y0);
+            });
         });
-    }
-    const int pairs = inverse ? dist : groups_active;
-    return for_y(pairs, [&](int y0, int ny) {
-        if (bits == 16) {
-            dim3 g(grid_x((S >> 6) * 8).x, ny);
-            if (inverse) hipLaunchKernelGGL((k_pass2<F16<1>, true>), g, dim3(256), 0, s, work, S, dist, tw, y0);
-            else hipLaunchKernelGGL((k_pass2<F16<1>, false>), g, dim3(256), 0, s, work, S, dist, tw, y0);
-        } else {
-            dim3 g(grid_x(S / 16).x, ny);
-            if (inverse) hipLaunchKernelGGL((k_pass2<F8<4>, true>), g, dim3(256), 0, s, work, S, dist, tw, y0);
-            else hipLaunchKernelGGL((k_pass2<F8<4>, false>), g, dim3(256), 0, s, work, S, dist, tw, y0);
-        }
     });
 }
 
@@ -1972,8 +1852,9 @@ hipError_t launch_zc_copy(const ZcRows &r, uint8_t *slab, uint64_t pitch, uint64
     if (r.n <= 0) return hipSuccess;
     if (r.n > kZcMax || (w & 15)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((w + 16383) / 16384), (unsigned)r.n);
-    if (to_host) hipLaunchKernelGGL(k_zc_copy<true>, grid, dim3(256), 0, s, r, slab, pitch, off, w);
-    else hipLaunchKernelGGL(k_zc_copy<false>, grid, dim3(256), 0, s, r, slab, pitch, off, w);
+    with_bool(to_host, [&](auto th) {
+        hipLaunchKernelGGL(k_zc_copy<decltype(th)::value>, grid, dim3(256), 0, s, r, slab, pitch, off, w);
+    });
     return hipGetLastError();
 }
 
@@ -1988,21 +1869,19 @@ hipError_t launch_copy_out(int bits, RowSet out, const uint8_t *work, uint64_t S
                            hipStream_t s) {
     (void)bits;
     return for_y(rows, [&](int y0, int ny) {
-        if (mismatch)
-            hipLaunchKernelGGL(k_copy_out<true>, dim3(grid_x(S / 16).x, ny), dim3(256), 0, s, out, work, S, mismatch, y0);
-        else
-            hipLaunchKernelGGL(k_copy_out<false>, dim3(grid_x(S / 16).x, ny), dim3(256), 0, s, out, work, S, mismatch,
-                               y0);
+        with_bool(mismatch != nullptr, [&](auto v) {
+            hipLaunchKernelGGL(k_copy_out<decltype(v)::value>, dim3(grid_x(S / 16).x, ny), dim3(256), 0, s, out, work, S,
+                               mismatch, y0);
+        });
     });
 }
 
 hipError_t launch_scale_in(int bits, uint8_t *work, uint64_t S, const uint8_t *const *src, const uint32_t *tw, int rows,
                            hipStream_t s) {
     return for_y(rows, [&](int y0, int ny) {
-        if (bits == 16)
-            hipLaunchKernelGGL(k_scale_in<F16<1>>, dim3(grid_x((S >> 6) * 8).x, ny), dim3(256), 0, s, work, S, src, tw, y0);
-        else
-            hipLaunchKernelGGL(k_scale_in<F8<4>>, dim3(grid_x(S / 16).x, ny), dim3(256), 0, s, work, S, src, tw, y0);
+        with_pass_unit(bits, S, ny, [&](auto f, dim3 g) {
+            hipLaunchKernelGGL(k_scale_in<decltype(f)>, g, dim3(256), 0, s, work, S, src, tw, y0);
+        });
     });
 }
 
@@ -2015,11 +1894,9 @@ hipError_t launch_formal_derivative(int bits, uint8_t *work, uint64_t S, int n, 
 hipError_t launch_reveal(int bits, uint8_t *const *dst, const uint8_t *work, uint64_t S, const int *pos,
                          const uint32_t *tw, int count, hipStream_t s) {
     return for_y(count, [&](int y0, int ny) {
-        if (bits == 16)
-            hipLaunchKernelGGL(k_reveal<F16<1>>, dim3(grid_x((S >> 6) * 8).x, ny), dim3(256), 0, s, dst, work, S, pos, tw,
-                               y0);
-        else
-            hipLaunchKernelGGL(k_reveal<F8<4>>, dim3(grid_x(S / 16).x, ny), dim3(256), 0, s, dst, work, S, pos, tw, y0);
+        with_pass_unit(bits, S, ny, [&](auto f, dim3 g) {
+            hipLaunchKernelGGL(k_reveal<decltype(f)>, g, dim3(256), 0, s, dst, work, S, pos, tw, y0);
+        });
     });
 }
 
@@ -2053,8 +1930,7 @@ hipError_t launch_rec_lds_patterns(int bits, int logn, bool sub, const RecPatArg
 hipError_t launch_encode_lds(int bits, int logm, bool verify, const EncodeArgs &a, hipStream_t s) {
     if (logm > 8) return bits == 16 ? enc_lds_f<F16<2>>(logm, verify, a, s) : hipErrorInvalidValue;
     const bool narrow = pick_narrow((a.shard_size + 127) / 128 * (uint64_t)a.nstripes < kLdsMinGrid);
-    if (narrow) return bits == 16 ? enc_lds_f<F16<2>>(logm, verify, a, s) : enc_lds_f<F8<2>>(logm, verify, a, s);
-    return bits == 16 ? enc_lds_f<F16<4>>(logm, verify, a, s) : enc_lds_f<F8<4>>(logm, verify, a, s);
+    return with_field(bits, narrow, [&](auto f) { return enc_lds_f<decltype(f)>(logm, verify, a, s); });
 }
 
 }  // namespace rs

@@ -30,19 +30,7 @@ bool stream_narrow(int bits, uint64_t S, uint64_t count) {
     const uint64_t wide_blocks = (S / (bits == 16 ? 32 : 16) + 255) / 256 * count;
     return pick_narrow(wide_blocks < kStreamMinBlocks);
 }
-// fn(F{}) for the field and unit width of a launch.
-template <class Fn>
-hipError_t with_field(int bits, bool narrow, Fn fn) {
-    if (bits == 16) return narrow ? fn(F16<2>{}) : fn(F16<4>{});
-    return narrow ? fn(F8<2>{}) : fn(F8<4>{});
-}
-// fn(std::integral_constant<int, n>{}) for n in [Lo, Hi]: the instantiations of
-// a kernel over a row count.  The launchers' argument checks refuse any other n.
-template <int Lo, int Hi, class Fn>
-hipError_t with_count(int n, Fn fn) {
-    if constexpr (Lo > Hi) return hipErrorInvalidValue;
-    else return n == Lo ? fn(std::integral_constant<int, Lo>{}) : with_count<Lo + 1, Hi>(n, fn);
-}
+// with_field, with_count: field.hpp
 
 }  // namespace
 
